@@ -54,7 +54,7 @@ dist.destroy_process_group()
 
 
 def test_bench_distributed_gloo_world2():
-    out = run_torchrun(["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1"])
+    out = run_torchrun(["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"])
     assert out.returncode == 0, out.stderr[-3000:]
     result = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert result["n_gpus"] == 2
@@ -63,11 +63,47 @@ def test_bench_distributed_gloo_world2():
 
 
 def test_bench_single_process():
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1"],
+    out = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=300, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     result = json.loads(out.stdout.strip().splitlines()[-1])
     assert result["config"]["vc_safety_violations"] == 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run carries only the headline (the --full extras are absent)
+    and --dump-outputs writes the last timed step's decisions, identical to
+    the same round driven in-process (same seed, same inputs)."""
+    import numpy as np
+
+    out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2",
+                          "--warmup", "1", "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=300, cwd=REPO)
+    assert out.returncode == 0, out.stderr[-2000:]
+    result = json.loads(out.stdout.strip().splitlines()[-1])
+    assert result["steps"] == 2 and result["ms_per_step"] > 0 and result["value"] > 0
+    for key in ("vc_safety_violations", "rccl_busbw_gbps", "hbm_copy_gbps", "gpu_health"):
+        assert key not in result["config"], key
+
+    sys.path.insert(0, REPO)
+    import bench
+
+    sim = bench.make_sim()
+    requests = bench.build_requests(seed=0, count=64)
+    expected = []
+    for _ in range(3):
+        expected.clear()
+        bench.run_round(sim, requests, [], expected)
+    bench.dump_outputs(str(tmp_path / "expected"), sim, expected)
+    names = sorted(os.listdir(tmp_path / "dump"))
+    assert names == ["decision_kind.npy", "leaf_cells.npy", "node_index.npy"]
+    for name in names:
+        got = np.load(tmp_path / "dump" / name)
+        want = np.load(tmp_path / "expected" / name)
+        assert got.dtype == np.float32 and got.shape[0] == 64
+        np.testing.assert_array_equal(got, want)
+    kind = np.load(tmp_path / "dump" / "decision_kind.npy")
+    assert (kind == 1).sum() == result["config"]["binds_per_step"] > 0
 
 
 def test_cell_probe_subgroups_gloo_world2(tmp_path):

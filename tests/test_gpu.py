@@ -210,7 +210,7 @@ def test_smoke_entry():
 
 @needs_gpu
 def test_bench_on_gpu():
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1"],
+    out = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-3000:]
     result = json.loads(out.stdout.strip().splitlines()[-1])
