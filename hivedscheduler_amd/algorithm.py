@@ -10,6 +10,7 @@ from __future__ import annotations
 import threading
 from typing import Dict, List, Optional
 
+from . import hivedcore
 from .api import constants
 from .api.types import (
     Config,
@@ -78,8 +79,6 @@ class HivedAlgorithm:
     reference's algorithmLock (hived_algorithm.go:104)."""
 
     def __init__(self, config: Config):
-        from . import hivedcore
-
         self._lock = threading.RLock()
         try:
             self._core = hivedcore.HivedCore(normalize_spec(config))
@@ -88,8 +87,6 @@ class HivedAlgorithm:
         self._config = config
 
     def _call(self, fn, *args):
-        from . import hivedcore
-
         with self._lock:
             try:
                 return fn(*args)
@@ -136,6 +133,8 @@ class HivedAlgorithm:
         return self._call(self._core.bad_nodes)
 
     # --- scheduling ---
+    # The core reads PodSchedulingSpec / PodBindInfo objects by attribute, so
+    # they cross the boundary as they are (no to_dict() round trip).
     def schedule(
         self,
         spec: PodSchedulingSpec,
@@ -143,20 +142,20 @@ class HivedAlgorithm:
         suggested_nodes: List[str],
         phase: str = FILTERING,
     ) -> ScheduleResult:
-        raw = self._call(self._core.schedule, spec.to_dict(), pod_key, suggested_nodes, phase)
+        raw = self._call(self._core.schedule, spec, pod_key, suggested_nodes, phase)
         return ScheduleResult(raw)
 
     def add_unallocated_pod(self, spec: PodSchedulingSpec, pod_key: str) -> None:
         pass  # parity: reference AddUnallocatedPod is a no-op
 
     def delete_unallocated_pod(self, spec: PodSchedulingSpec, pod_key: str) -> None:
-        self._call(self._core.delete_unallocated_pod, spec.to_dict(), pod_key)
+        self._call(self._core.delete_unallocated_pod, spec, pod_key)
 
     def add_allocated_pod(self, spec: PodSchedulingSpec, info: PodBindInfo, pod_key: str) -> None:
-        self._call(self._core.add_allocated_pod, spec.to_dict(), info.to_dict(), pod_key)
+        self._call(self._core.add_allocated_pod, spec, info, pod_key)
 
     def delete_allocated_pod(self, spec: PodSchedulingSpec, info: PodBindInfo, pod_key: str) -> None:
-        self._call(self._core.delete_allocated_pod, spec.to_dict(), info.to_dict(), pod_key)
+        self._call(self._core.delete_allocated_pod, spec, info, pod_key)
 
     # --- inspect ---
     def get_all_affinity_groups(self) -> List[dict]:

@@ -18,6 +18,8 @@ bool mapDebugRelease() {
 }
 
 namespace {
+// longest wait reason plus slack: one allocation, then appended to in place
+constexpr size_t kWaitReasonReserve = 128;
 
 // node -> victim pod keys; overlapping Preempting groups touching the placement
 struct Victims {
@@ -167,6 +169,7 @@ ScheduleResult HivedCore::schedule(const PodSpec& s, const std::string& podKey,
   bool hasVirtual = true;
   std::map<std::string, std::set<std::string>> victims;
   std::string waitReason;
+  waitReason.reserve(kWaitReasonReserve);  // the reason is built by appending in place
   int podIndex = 0;
   bool havePlacement = false;
 
@@ -198,7 +201,11 @@ ScheduleResult HivedCore::generateResult(const Placement<PhysicalCell>& phys, bo
   ScheduleResult r;
   if (phys.empty()) {
     r.kind = ScheduleResult::Kind::Wait;
-    r.waitReason = waitReason.empty() ? "waiting for resources" : waitReason;
+    if (waitReason.empty()) {
+      r.waitReason = "waiting for resources";
+    } else {
+      r.waitReason = waitReason;
+    }
     return r;
   }
   if (!victims.empty()) {
@@ -397,7 +404,7 @@ void HivedCore::validateSchedulingRequest(const SchedulingRequest& sr, const std
   if (!message.empty()) throw HivedError::BadRequest("[" + podKey + "]: " + message);
 }
 
-bool HivedCore::handleSchedulingRequest(const SchedulingRequest& sr, Placement<PhysicalCell>* phys,
+bool HivedCore::handleSchedulingRequest(SchedulingRequest& sr, Placement<PhysicalCell>* phys,
                                         bool* hasVirtual, Placement<VirtualCell>* virt,
                                         std::string* failedReason) {
   if (sr.priority >= kMinGuaranteedPriority) {
@@ -409,9 +416,20 @@ bool HivedCore::handleSchedulingRequest(const SchedulingRequest& sr, Placement<P
   return scheduleOpportunisticGroup(sr, phys, failedReason);
 }
 
-bool HivedCore::scheduleGuaranteedGroup(const SchedulingRequest& srIn, Placement<PhysicalCell>* phys,
+bool HivedCore::scheduleGuaranteedGroup(SchedulingRequest& sr, Placement<PhysicalCell>* phys,
                                         Placement<VirtualCell>* virt, std::string* failedReason) {
-  SchedulingRequest sr = srIn;
+  // The attempts below steer through sr.honorLinksOnly / sr.cleanWorld. The
+  // request is the caller's (copying it costs a map and four strings per
+  // filter), so both fields are put back on every way out.
+  struct RestoreSteering {
+    SchedulingRequest& sr;
+    bool honorLinksOnly;
+    const CleanShapeWorld* cleanWorld;
+    ~RestoreSteering() {
+      sr.honorLinksOnly = honorLinksOnly;
+      sr.cleanWorld = cleanWorld;
+    }
+  } restoreSteering{sr, sr.honorLinksOnly, sr.cleanWorld};
 
   // One full placement attempt: intra-VC schedule -> lazy preemption ->
   // binding-vertex construction -> virtual->physical mapping. honorOnly
@@ -575,8 +593,9 @@ bool HivedCore::scheduleGuaranteedGroup(const SchedulingRequest& srIn, Placement
     sr.cleanWorld = nullptr;
   }
   if (attemptOnce(false)) return true;
-  *failedReason = std::string("Mapping the virtual placement would need to use at least one ") +
-                  (sr.ignoreSuggestedNodes ? "bad" : "bad or non-suggested") + " node";
+  failedReason->assign("Mapping the virtual placement would need to use at least one ")
+      .append(sr.ignoreSuggestedNodes ? "bad" : "bad or non-suggested")
+      .append(" node");
   return false;
 }
 
@@ -614,7 +633,7 @@ bool HivedCore::scheduleOpportunisticGroup(const SchedulingRequest& sr,
   if (!opportunisticSchedulers_.at(sr.chain).Schedule(sr.podLeafCellNums, kOpportunisticPriority,
                                                       *sr.suggestedNodes, sr.ignoreSuggestedNodes,
                                                       &generic, failedReason, sr.hbmBytes)) {
-    *failedReason += " when scheduling in physical cluster";
+    failedReason->append(" when scheduling in physical cluster");
     return false;
   }
   phys->clear();

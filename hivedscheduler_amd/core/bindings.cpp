@@ -1,9 +1,11 @@
-// pybind11 bindings for the scheduler core. Dict-in / dict-out at the API
-// boundary (wire formats match hivedscheduler_amd.api.types); all hot-path
-// work happens in C++.
+// pybind11 bindings for the scheduler core. Requests come in as the wire-format
+// dict or as the API object itself (hivedscheduler_amd.api.types), results go
+// out as dicts in the wire format; all hot-path work happens in C++.
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <climits>
+#include <cstring>
 #include <functional>
 
 #include "core.hpp"
@@ -99,30 +101,208 @@ ClusterSpec parseClusterSpec(const py::dict& d) {
   return spec;
 }
 
-PodSpec parsePodSpec(const py::dict& d) {
-  PodSpec s;
-  s.vc = dstr(d, "virtualCluster");
-  s.priority = static_cast<int>(dint(d, "priority"));
-  s.pinnedCellId = dstr(d, "pinnedCellId");
-  s.leafCellType = dstr(d, "leafCellType");
-  s.leafCellNumber = static_cast<int>(dint(d, "leafCellNumber"));
-  s.gangReleaseEnable = dbool(d, "gangReleaseEnable");
-  s.lazyPreemptionEnable = dbool(d, "lazyPreemptionEnable");
-  s.ignoreK8sSuggestedNodes = dbool(d, "ignoreK8sSuggestedNodes", true);
-  if (d.contains("hbmBytesPerCell") && !d["hbmBytesPerCell"].is_none()) {
-    s.hbmBytesPerCell = py::cast<long long>(d["hbmBytesPerCell"]);
-    if (s.hbmBytesPerCell < 0) {
-      throw HivedError::BadRequest("hbmBytesPerCell must be non-negative");
+// ---------------------------------------------------------------------------
+// Hot-path marshalling (schedule / add / delete). Every decision crosses this
+// boundary, so it avoids temporaries: key strings are interned once, each
+// field costs one lookup, and str values are read in place.
+// ---------------------------------------------------------------------------
+
+// Interned key / attribute names and constant values. Created once at module
+// initialisation (under the GIL) and never released, so interpreter shutdown
+// has nothing to trip over.
+struct Names {
+  // PodSchedulingSpec
+  PyObject* virtualCluster;
+  PyObject* priority;
+  PyObject* pinnedCellId;
+  PyObject* leafCellType;
+  PyObject* leafCellNumber;
+  PyObject* gangReleaseEnable;
+  PyObject* lazyPreemptionEnable;
+  PyObject* ignoreK8sSuggestedNodes;
+  PyObject* hbmBytesPerCell;
+  PyObject* affinityGroup;
+  PyObject* name;
+  PyObject* members;
+  PyObject* podNumber;
+  // PodBindInfo
+  PyObject* node;
+  PyObject* cellChain;
+  PyObject* leafCellIsolation;
+  PyObject* affinityGroupBindInfo;
+  PyObject* podPlacements;
+  PyObject* physicalNode;
+  PyObject* physicalLeafCellIndices;
+  PyObject* preassignedCellTypes;
+  // schedule result
+  PyObject* kind;
+  PyObject* bind;
+  PyObject* preempt;
+  PyObject* wait;
+  PyObject* bindInfo;
+  PyObject* victimNode;
+  PyObject* victimPodKeys;
+  PyObject* reason;
+};
+Names N{};
+
+PyObject* internName(const char* s) {
+  PyObject* o = PyUnicode_InternFromString(s);
+  if (o == nullptr) throw py::error_already_set();
+  return o;
+}
+
+void initNames() {
+#define HIVED_NAME(x) N.x = internName(#x)
+  HIVED_NAME(virtualCluster);
+  HIVED_NAME(priority);
+  HIVED_NAME(pinnedCellId);
+  HIVED_NAME(leafCellType);
+  HIVED_NAME(leafCellNumber);
+  HIVED_NAME(gangReleaseEnable);
+  HIVED_NAME(lazyPreemptionEnable);
+  HIVED_NAME(ignoreK8sSuggestedNodes);
+  HIVED_NAME(hbmBytesPerCell);
+  HIVED_NAME(affinityGroup);
+  HIVED_NAME(name);
+  HIVED_NAME(members);
+  HIVED_NAME(podNumber);
+  HIVED_NAME(node);
+  HIVED_NAME(cellChain);
+  HIVED_NAME(leafCellIsolation);
+  HIVED_NAME(affinityGroupBindInfo);
+  HIVED_NAME(podPlacements);
+  HIVED_NAME(physicalNode);
+  HIVED_NAME(physicalLeafCellIndices);
+  HIVED_NAME(preassignedCellTypes);
+  HIVED_NAME(kind);
+  HIVED_NAME(bind);
+  HIVED_NAME(preempt);
+  HIVED_NAME(wait);
+  HIVED_NAME(bindInfo);
+  HIVED_NAME(victimNode);
+  HIVED_NAME(victimPodKeys);
+  HIVED_NAME(reason);
+#undef HIVED_NAME
+}
+
+// One field of a record. A record is either the wire-format dict, read by key
+// (borrowed reference), or an API object (PodSchedulingSpec, PodBindInfo and
+// their members), read by attribute (owned reference). A missing key and a
+// None value both read as absent; a failing lookup propagates, and so does a
+// missing attribute: the API objects always carry all their fields.
+class Field {
+ public:
+  Field(py::handle rec, PyObject* name) {
+    if (PyDict_Check(rec.ptr())) {
+      p_ = PyDict_GetItemWithError(rec.ptr(), name);
+      if (p_ == nullptr && PyErr_Occurred()) throw py::error_already_set();
+    } else {
+      p_ = PyObject_GetAttr(rec.ptr(), name);
+      if (p_ == nullptr) throw py::error_already_set();
+      owned_ = true;
     }
   }
-  if (d.contains("affinityGroup") && !d["affinityGroup"].is_none()) {
-    py::dict ag = py::cast<py::dict>(d["affinityGroup"]);
-    s.groupName = dstr(ag, "name");
-    if (ag.contains("members") && !ag["members"].is_none()) {
-      for (auto m : py::cast<py::list>(ag["members"])) {
-        py::dict md = py::cast<py::dict>(m);
-        s.groupPodNums[static_cast<int>(dint(md, "leafCellNumber"))] +=
-            static_cast<int>(dint(md, "podNumber"));
+  Field(const Field&) = delete;
+  Field& operator=(const Field&) = delete;
+  ~Field() {
+    if (owned_) Py_DECREF(p_);
+  }
+  explicit operator bool() const { return p_ != nullptr && p_ != Py_None; }
+  py::handle get() const { return p_; }
+
+ private:
+  PyObject* p_ = nullptr;
+  bool owned_ = false;
+};
+
+std::string toStdString(py::handle v) {
+  if (PyUnicode_Check(v.ptr())) {
+    Py_ssize_t n = 0;
+    const char* s = PyUnicode_AsUTF8AndSize(v.ptr(), &n);
+    if (s == nullptr) throw py::error_already_set();
+    return std::string(s, static_cast<size_t>(n));
+  }
+  return py::cast<std::string>(py::str(v));
+}
+long long toLongLong(py::handle v) {
+  if (PyLong_CheckExact(v.ptr())) {
+    int overflow = 0;
+    long long x = PyLong_AsLongLongAndOverflow(v.ptr(), &overflow);
+    if (overflow == 0) {
+      if (x == -1 && PyErr_Occurred()) throw py::error_already_set();
+      return x;
+    }
+  }
+  return py::cast<long long>(v);
+}
+int toInt(py::handle v) {
+  if (PyLong_CheckExact(v.ptr())) {
+    int overflow = 0;
+    long x = PyLong_AsLongAndOverflow(v.ptr(), &overflow);
+    if (overflow == 0 && x >= INT_MIN && x <= INT_MAX) {
+      if (x == -1 && PyErr_Occurred()) throw py::error_already_set();
+      return static_cast<int>(x);
+    }
+  }
+  return py::cast<int>(v);
+}
+bool toBool(py::handle v) {
+  if (v.ptr() == Py_True) return true;
+  if (v.ptr() == Py_False) return false;
+  return py::cast<bool>(v);
+}
+
+std::string fstr(py::handle rec, PyObject* name) {
+  Field f(rec, name);
+  return f ? toStdString(f.get()) : std::string();
+}
+long long fint(py::handle rec, PyObject* name) {
+  Field f(rec, name);
+  return f ? toLongLong(f.get()) : 0;
+}
+bool fbool(py::handle rec, PyObject* name, bool def) {
+  Field f(rec, name);
+  return f ? toBool(f.get()) : def;
+}
+
+// Items of a list-valued field; any iterable is taken, as list(x) would.
+class Items {
+ public:
+  explicit Items(py::handle v) : seq_(PySequence_Fast(v.ptr(), "expected a list")) {
+    if (seq_ == nullptr) throw py::error_already_set();
+  }
+  Items(const Items&) = delete;
+  Items& operator=(const Items&) = delete;
+  ~Items() { Py_DECREF(seq_); }
+  Py_ssize_t size() const { return PySequence_Fast_GET_SIZE(seq_); }
+  py::handle operator[](Py_ssize_t i) const { return PySequence_Fast_GET_ITEM(seq_, i); }
+
+ private:
+  PyObject* seq_;
+};
+
+PodSpec parsePodSpec(py::handle d) {
+  PodSpec s;
+  s.vc = fstr(d, N.virtualCluster);
+  s.priority = static_cast<int>(fint(d, N.priority));
+  s.pinnedCellId = fstr(d, N.pinnedCellId);
+  s.leafCellType = fstr(d, N.leafCellType);
+  s.leafCellNumber = static_cast<int>(fint(d, N.leafCellNumber));
+  s.gangReleaseEnable = fbool(d, N.gangReleaseEnable, false);
+  s.lazyPreemptionEnable = fbool(d, N.lazyPreemptionEnable, false);
+  s.ignoreK8sSuggestedNodes = fbool(d, N.ignoreK8sSuggestedNodes, true);
+  s.hbmBytesPerCell = fint(d, N.hbmBytesPerCell);
+  if (s.hbmBytesPerCell < 0) {
+    throw HivedError::BadRequest("hbmBytesPerCell must be non-negative");
+  }
+  if (Field ag{d, N.affinityGroup}) {
+    s.groupName = fstr(ag.get(), N.name);
+    if (Field members{ag.get(), N.members}) {
+      Items ms(members.get());
+      for (Py_ssize_t i = 0; i < ms.size(); i++) {
+        s.groupPodNums[static_cast<int>(fint(ms[i], N.leafCellNumber))] +=
+            static_cast<int>(fint(ms[i], N.podNumber));
       }
     }
   }
@@ -132,32 +312,37 @@ PodSpec parsePodSpec(const py::dict& d) {
   return s;
 }
 
-BindInfo parseBindInfo(const py::dict& d) {
-  BindInfo info;
-  info.node = dstr(d, "node");
-  info.chain = dstr(d, "cellChain");
-  if (d.contains("leafCellIsolation") && !d["leafCellIsolation"].is_none()) {
-    for (auto i : py::cast<py::list>(d["leafCellIsolation"])) {
-      info.isolation.push_back(py::cast<int>(i));
-    }
+void parseIntList(py::handle rec, PyObject* name, std::vector<int>* out) {
+  if (Field f{rec, name}) {
+    Items items(f.get());
+    out->reserve(static_cast<size_t>(items.size()));
+    for (Py_ssize_t i = 0; i < items.size(); i++) out->push_back(toInt(items[i]));
   }
-  if (d.contains("affinityGroupBindInfo") && !d["affinityGroupBindInfo"].is_none()) {
-    for (auto mbiObj : py::cast<py::list>(d["affinityGroupBindInfo"])) {
-      py::dict mbiD = py::cast<py::dict>(mbiObj);
+}
+
+BindInfo parseBindInfo(py::handle d) {
+  BindInfo info;
+  info.node = fstr(d, N.node);
+  info.chain = fstr(d, N.cellChain);
+  parseIntList(d, N.leafCellIsolation, &info.isolation);
+  if (Field mbis{d, N.affinityGroupBindInfo}) {
+    Items mbiItems(mbis.get());
+    info.memberBindInfo.reserve(static_cast<size_t>(mbiItems.size()));
+    for (Py_ssize_t m = 0; m < mbiItems.size(); m++) {
       std::vector<PodPlacementInfo> placements;
-      if (mbiD.contains("podPlacements") && !mbiD["podPlacements"].is_none()) {
-        for (auto plObj : py::cast<py::list>(mbiD["podPlacements"])) {
-          py::dict plD = py::cast<py::dict>(plObj);
+      if (Field pls{mbiItems[m], N.podPlacements}) {
+        Items plItems(pls.get());
+        placements.reserve(static_cast<size_t>(plItems.size()));
+        for (Py_ssize_t p = 0; p < plItems.size(); p++) {
+          py::handle plD = plItems[p];
           PodPlacementInfo pl;
-          pl.node = dstr(plD, "physicalNode");
-          if (plD.contains("physicalLeafCellIndices") && !plD["physicalLeafCellIndices"].is_none()) {
-            for (auto i : py::cast<py::list>(plD["physicalLeafCellIndices"])) {
-              pl.leafIndices.push_back(py::cast<int>(i));
-            }
-          }
-          if (plD.contains("preassignedCellTypes") && !plD["preassignedCellTypes"].is_none()) {
-            for (auto t : py::cast<py::list>(plD["preassignedCellTypes"])) {
-              pl.preassignedTypes.push_back(t.is_none() ? "" : py::cast<std::string>(py::str(t)));
+          pl.node = fstr(plD, N.physicalNode);
+          parseIntList(plD, N.physicalLeafCellIndices, &pl.leafIndices);
+          if (Field types{plD, N.preassignedCellTypes}) {
+            Items ts(types.get());
+            pl.preassignedTypes.reserve(static_cast<size_t>(ts.size()));
+            for (Py_ssize_t t = 0; t < ts.size(); t++) {
+              pl.preassignedTypes.push_back(ts[t].is_none() ? std::string() : toStdString(ts[t]));
             }
           }
           placements.push_back(std::move(pl));
@@ -169,28 +354,83 @@ BindInfo parseBindInfo(const py::dict& d) {
   return info;
 }
 
+py::object pyStr(const std::string& s) {
+  PyObject* o = PyUnicode_FromStringAndSize(s.data(), static_cast<Py_ssize_t>(s.size()));
+  if (o == nullptr) throw py::error_already_set();
+  return py::reinterpret_steal<py::object>(o);
+}
+py::object pyIntList(const std::vector<int>& v) {
+  py::list l(v.size());
+  for (size_t i = 0; i < v.size(); i++) {
+    PyObject* o = PyLong_FromLong(v[i]);
+    if (o == nullptr) throw py::error_already_set();
+    PyList_SET_ITEM(l.ptr(), static_cast<Py_ssize_t>(i), o);
+  }
+  return std::move(l);
+}
+py::object pyStrList(const std::vector<std::string>& v) {
+  py::list l(v.size());
+  for (size_t i = 0; i < v.size(); i++) {
+    PyList_SET_ITEM(l.ptr(), static_cast<Py_ssize_t>(i), pyStr(v[i]).release().ptr());
+  }
+  return std::move(l);
+}
+void setItem(py::dict& d, PyObject* key, py::handle value) {
+  if (PyDict_SetItem(d.ptr(), key, value.ptr()) != 0) throw py::error_already_set();
+}
+
 py::dict bindInfoToDict(const BindInfo& info) {
   py::dict d;
-  d["node"] = info.node;
-  d["leafCellIsolation"] = info.isolation;
-  d["cellChain"] = info.chain;
-  py::list mbis;
-  for (auto& mbi : info.memberBindInfo) {
-    py::list placements;
-    for (auto& pl : mbi) {
+  setItem(d, N.node, pyStr(info.node));
+  setItem(d, N.leafCellIsolation, pyIntList(info.isolation));
+  setItem(d, N.cellChain, pyStr(info.chain));
+  py::list mbis(info.memberBindInfo.size());
+  for (size_t m = 0; m < info.memberBindInfo.size(); m++) {
+    auto& mbi = info.memberBindInfo[m];
+    py::list placements(mbi.size());
+    for (size_t p = 0; p < mbi.size(); p++) {
+      auto& pl = mbi[p];
       py::dict pd;
-      pd["physicalNode"] = pl.node;
-      pd["physicalLeafCellIndices"] = pl.leafIndices;
-      pd["preassignedCellTypes"] = pl.preassignedTypes;
-      placements.append(pd);
+      setItem(pd, N.physicalNode, pyStr(pl.node));
+      setItem(pd, N.physicalLeafCellIndices, pyIntList(pl.leafIndices));
+      setItem(pd, N.preassignedCellTypes, pyStrList(pl.preassignedTypes));
+      PyList_SET_ITEM(placements.ptr(), static_cast<Py_ssize_t>(p), pd.release().ptr());
     }
     py::dict md;
-    md["podPlacements"] = placements;
-    mbis.append(md);
+    setItem(md, N.podPlacements, placements);
+    PyList_SET_ITEM(mbis.ptr(), static_cast<Py_ssize_t>(m), md.release().ptr());
   }
-  d["affinityGroupBindInfo"] = mbis;
+  setItem(d, N.affinityGroupBindInfo, mbis);
   return d;
 }
+
+// The suggested_nodes argument takes what a std::vector<std::string> argument
+// takes: a sequence other than str / bytes, a generator, a set or a dict view.
+bool isNodeNameCollection(py::handle v) {
+  PyObject* o = v.ptr();
+  if (PySequence_Check(o) != 0) return !PyUnicode_Check(o) && !PyBytes_Check(o);
+  if (PyGen_Check(o) != 0 || PyAnySet_Check(o) != 0) return true;
+  if (PyType_Check(o)) return false;
+  const char* tp = Py_TYPE(o)->tp_name;
+  for (const char* ok : {"dict_keys", "dict_values", "dict_items", "map", "zip"}) {
+    if (std::strcmp(tp, ok) == 0) return true;
+  }
+  return false;
+}
+
+std::set<std::string> toNodeNameSet(py::handle v) {
+  std::set<std::string> out;
+  Items items(v);
+  for (Py_ssize_t i = 0; i < items.size(); i++) {
+    py::handle item = items[i];
+    if (!PyUnicode_Check(item.ptr()) && !PyBytes_Check(item.ptr())) {
+      throw py::type_error("suggested_nodes must contain node names (str)");
+    }
+    out.insert(py::cast<std::string>(item));
+  }
+  return out;
+}
+
 
 py::dict physicalCellStatus(PhysicalCell* c, bool withChildren = true) {
   py::dict d;
@@ -305,7 +545,9 @@ py::dict groupToDict(const Group* g) {
 
 class PyHivedCore {
  public:
-  explicit PyHivedCore(const py::dict& spec) : core_(parseClusterSpec(spec)) {}
+  explicit PyHivedCore(const py::dict& spec) : core_(parseClusterSpec(spec)) {
+    for (auto& node : core_.allNodes()) nodeNames_.push_back(pyStr(node));
+  }
 
   void setNodeHealthy(const std::string& node, bool healthy) { core_.setNodeHealthy(node, healthy); }
   void setLeafCellHealthy(const std::string& node, int leafIndex, bool healthy) {
@@ -326,45 +568,68 @@ class PyHivedCore {
     }
     return out;
   }
-  std::vector<std::string> allNodes() const { return core_.allNodes(); }
+  // The node set is fixed at construction (buildFromSpec is the only writer
+  // of the node table), so the name objects are built once; every call hands
+  // out a fresh list of them.
+  py::list allNodes() const {
+    py::list out(nodeNames_.size());
+    for (size_t i = 0; i < nodeNames_.size(); i++) {
+      PyList_SET_ITEM(out.ptr(), static_cast<Py_ssize_t>(i), py::object(nodeNames_[i]).release().ptr());
+    }
+    return out;
+  }
   std::vector<std::string> badNodes() const {
     auto s = core_.badNodes();
     return {s.begin(), s.end()};
   }
 
-  py::dict schedule(const py::dict& spec, const std::string& podKey,
-                    const std::vector<std::string>& suggestedNodes, const std::string& phase) {
+  // pod_spec / bind_info: the wire-format dict or the API object itself.
+  py::dict schedule(py::handle spec, const std::string& podKey, py::handle suggestedNodes,
+                    const std::string& phase) {
+    if (!isNodeNameCollection(suggestedNodes)) {
+      throw py::type_error("suggested_nodes must be a sequence of node names, not " +
+                           std::string(Py_TYPE(suggestedNodes.ptr())->tp_name));
+    }
     PodSpec s = parsePodSpec(spec);
-    std::set<std::string> suggested(suggestedNodes.begin(), suggestedNodes.end());
+    // The core reads the suggested set only where suggested nodes are not
+    // ignored: for a new group the request's flag decides, for an existing
+    // group of that name the group's own flag does. Otherwise the names are
+    // never converted.
+    bool needSuggested = !s.ignoreK8sSuggestedNodes;
+    if (!needSuggested) {
+      auto it = core_.groups().find(s.groupName);
+      needSuggested = it != core_.groups().end() && !it->second->ignoreK8sSuggestedNodes;
+    }
+    std::set<std::string> suggested;
+    if (needSuggested) suggested = toNodeNameSet(suggestedNodes);
     Phase ph = (phase == "Preempting") ? Phase::Preempting : Phase::Filtering;
     ScheduleResult r = core_.schedule(s, podKey, suggested, ph);
     py::dict d;
     switch (r.kind) {
       case ScheduleResult::Kind::Bind:
-        d["kind"] = "bind";
-        d["bindInfo"] = bindInfoToDict(r.bindInfo);
+        setItem(d, N.kind, N.bind);
+        setItem(d, N.bindInfo, bindInfoToDict(r.bindInfo));
         break;
       case ScheduleResult::Kind::Preempt:
-        d["kind"] = "preempt";
-        d["victimNode"] = r.victimNode;
-        d["victimPodKeys"] = r.victimPodKeys;
+        setItem(d, N.kind, N.preempt);
+        setItem(d, N.victimNode, pyStr(r.victimNode));
+        setItem(d, N.victimPodKeys, pyStrList(r.victimPodKeys));
         break;
       case ScheduleResult::Kind::Wait:
-        d["kind"] = "wait";
-        d["reason"] = r.waitReason;
+        setItem(d, N.kind, N.wait);
+        setItem(d, N.reason, pyStr(r.waitReason));
         break;
     }
     return d;
   }
 
-  void deleteUnallocatedPod(const py::dict& spec, const std::string& podKey) {
+  void deleteUnallocatedPod(py::handle spec, const std::string& podKey) {
     core_.deleteUnallocatedPod(parsePodSpec(spec), podKey);
   }
-  void addAllocatedPod(const py::dict& spec, const py::dict& bindInfo, const std::string& podKey) {
+  void addAllocatedPod(py::handle spec, py::handle bindInfo, const std::string& podKey) {
     core_.addAllocatedPod(parsePodSpec(spec), parseBindInfo(bindInfo), podKey);
   }
-  void deleteAllocatedPod(const py::dict& spec, const py::dict& bindInfo,
-                          const std::string& podKey) {
+  void deleteAllocatedPod(py::handle spec, py::handle bindInfo, const std::string& podKey) {
     core_.deleteAllocatedPod(parsePodSpec(spec), parseBindInfo(bindInfo), podKey);
   }
 
@@ -505,12 +770,14 @@ class PyHivedCore {
 
  private:
   HivedCore core_;
+  std::vector<py::object> nodeNames_;
 };
 
 }  // namespace
 
 PYBIND11_MODULE(hivedcore, m) {
   m.doc() = "MI355X-native gang scheduler core (C++)";
+  initNames();
 
   static py::exception<HivedError> exc(m, "CoreError");
   py::register_exception_translator([](std::exception_ptr p) {

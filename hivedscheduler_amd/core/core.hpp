@@ -488,10 +488,10 @@ class HivedCore {
                                const std::string& podKey, bool typeSpecified,
                                Placement<PhysicalCell>* phys, bool* hasVirtual,
                                Placement<VirtualCell>* virt, std::string* failedReason);
-  bool handleSchedulingRequest(const SchedulingRequest& sr, Placement<PhysicalCell>* phys,
+  bool handleSchedulingRequest(SchedulingRequest& sr, Placement<PhysicalCell>* phys,
                                bool* hasVirtual, Placement<VirtualCell>* virt,
                                std::string* failedReason);
-  bool scheduleGuaranteedGroup(const SchedulingRequest& sr, Placement<PhysicalCell>* phys,
+  bool scheduleGuaranteedGroup(SchedulingRequest& sr, Placement<PhysicalCell>* phys,
                                Placement<VirtualCell>* virt, std::string* failedReason);
   bool chainHasBadLinks(const std::string& chain);
   bool scheduleOpportunisticGroup(const SchedulingRequest& sr, Placement<PhysicalCell>* phys,

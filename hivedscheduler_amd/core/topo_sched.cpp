@@ -950,7 +950,7 @@ bool IntraVCScheduler::schedule(const SchedulingRequest& sr, Placement<VirtualCe
                            sr.ignoreSuggestedNodes, &generic, failedReason, sr.hbmBytes,
                            sr.cleanWorld, sr.honorLinksOnly)) {
     if (failedReason->empty()) *failedReason = "no scheduler for request";
-    *failedReason += " when scheduling in VC " + sr.vc;
+    failedReason->append(" when scheduling in VC ").append(sr.vc);
     return false;
   }
   out->clear();

@@ -15,7 +15,13 @@ from typing import Any, Dict, List, Optional
 import yaml
 
 from ..api import constants
-from ..api.types import PodBindInfo, PodSchedulingSpec, WebServerError
+from ..api.types import (
+    AffinityGroupMemberSpec,
+    AffinityGroupSpec,
+    PodBindInfo,
+    PodSchedulingSpec,
+    WebServerError,
+)
 
 # libyaml C codecs: annotation YAML ser/de is on the filter hot path and the
 # pure-Python loader costs ~1 ms per decision (profiled); the C loader is
@@ -133,8 +139,6 @@ def extract_pod_scheduling_spec(pod: Pod) -> PodSchedulingSpec:
 
 
 def validate_pod_scheduling_spec(spec: PodSchedulingSpec, key: str, err_pfx: str = "") -> None:
-    from ..api.types import AffinityGroupMemberSpec, AffinityGroupSpec
-
     # Defaulting: a pod without a group forms a singleton group "ns/name".
     if spec.affinityGroup is None:
         spec.affinityGroup = AffinityGroupSpec(

@@ -11,6 +11,8 @@ from typing import Dict, List, Optional, Tuple
 
 from ..algorithm import FILTERING, PREEMPTING, HivedAlgorithm, ScheduleResult
 from ..api.types import (
+    AffinityGroupMemberSpec,
+    AffinityGroupSpec,
     Config,
     PhysicalClusterSpec,
     PodBindInfo,
@@ -81,8 +83,6 @@ class SimScheduler:
         ignore_suggested: bool = True,
         hbm_bytes_per_cell: int = 0,
     ) -> PodSchedulingSpec:
-        from ..api.types import AffinityGroupMemberSpec, AffinityGroupSpec
-
         spec = PodSchedulingSpec(
             virtualCluster=vc,
             priority=priority,
