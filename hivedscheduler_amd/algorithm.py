@@ -49,29 +49,10 @@ def normalize_spec(config: Config) -> dict:
     }
 
 
-class ScheduleResult:
-    """One of bind / preempt / wait."""
-
-    def __init__(self, raw: dict):
-        self.kind: str = raw["kind"]
-        self.bind_info: Optional[PodBindInfo] = None
-        self.victim_node: str = ""
-        self.victim_pod_keys: List[str] = []
-        self.wait_reason: str = ""
-        if self.kind == "bind":
-            self.bind_info = PodBindInfo.from_dict(raw["bindInfo"])
-        elif self.kind == "preempt":
-            self.victim_node = raw.get("victimNode", "")
-            self.victim_pod_keys = list(raw.get("victimPodKeys", []))
-        else:
-            self.wait_reason = raw.get("reason", "")
-
-    def __repr__(self) -> str:  # pragma: no cover
-        if self.kind == "bind":
-            return f"ScheduleResult(bind node={self.bind_info.node} cells={self.bind_info.leafCellIsolation})"
-        if self.kind == "preempt":
-            return f"ScheduleResult(preempt victims={self.victim_pod_keys})"
-        return f"ScheduleResult(wait reason={self.wait_reason!r})"
+# One of bind / preempt / wait: the core's native result type. Read-only
+# attributes kind, bind_info (a PodBindInfo built on first access, None unless
+# kind == "bind"), victim_node, victim_pod_keys and wait_reason.
+ScheduleResult = hivedcore.ScheduleResult
 
 
 class HivedAlgorithm:
@@ -142,8 +123,27 @@ class HivedAlgorithm:
         suggested_nodes: List[str],
         phase: str = FILTERING,
     ) -> ScheduleResult:
-        raw = self._call(self._core.schedule, spec, pod_key, suggested_nodes, phase)
-        return ScheduleResult(raw)
+        """Decide only: the spec is taken as it is (already validated and
+        defaulted by the caller), nothing is committed."""
+        if suggested_nodes is None:
+            raise TypeError("suggested_nodes must be a sequence of node names, not NoneType")
+        return self._call(self._core.schedule_pod, spec, pod_key, suggested_nodes, phase,
+                          False, False)
+
+    def schedule_pod(
+        self,
+        spec: PodSchedulingSpec,
+        pod_key: str,
+        suggested_nodes: Optional[List[str]] = None,
+        phase: str = FILTERING,
+        commit: bool = False,
+    ) -> ScheduleResult:
+        """One whole filter decision in one core call: validate and default
+        the spec (as validate_pod_scheduling_spec does), decide, and with
+        commit=True add the pod as allocated on a bind decision.
+        suggested_nodes=None stands for every node of the cluster."""
+        return self._call(self._core.schedule_pod, spec, pod_key, suggested_nodes, phase,
+                          commit, True)
 
     def add_unallocated_pod(self, spec: PodSchedulingSpec, pod_key: str) -> None:
         pass  # parity: reference AddUnallocatedPod is a no-op

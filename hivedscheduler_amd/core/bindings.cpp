@@ -1,6 +1,7 @@
 // pybind11 bindings for the scheduler core. Requests come in as the wire-format
 // dict or as the API object itself (hivedscheduler_amd.api.types), results go
-// out as dicts in the wire format; all hot-path work happens in C++.
+// out as dicts in the wire format, or from schedule_pod as a native
+// ScheduleResult; all hot-path work happens in C++.
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
@@ -184,6 +185,33 @@ void initNames() {
   HIVED_NAME(victimPodKeys);
   HIVED_NAME(reason);
 #undef HIVED_NAME
+}
+
+// API classes (hivedscheduler_amd.api.types) and constants, looked up once at
+// module initialisation and never released, like the names above.
+struct ApiTypes {
+  PyObject* AffinityGroupSpec;
+  PyObject* AffinityGroupMemberSpec;
+  PyObject* PodBindInfo;
+  PyObject* AffinityGroupMemberBindInfo;
+  PyObject* PodPlacementInfo;
+  PyObject* emptyTuple;
+  PyObject* one;
+};
+ApiTypes T{};
+
+void initApiTypes() {
+  py::module_ types = py::module_::import("hivedscheduler_amd.api.types");
+#define HIVED_TYPE(x) T.x = py::object(types.attr(#x)).release().ptr()
+  HIVED_TYPE(AffinityGroupSpec);
+  HIVED_TYPE(AffinityGroupMemberSpec);
+  HIVED_TYPE(PodBindInfo);
+  HIVED_TYPE(AffinityGroupMemberBindInfo);
+  HIVED_TYPE(PodPlacementInfo);
+#undef HIVED_TYPE
+  T.emptyTuple = PyTuple_New(0);
+  T.one = PyLong_FromLong(1);
+  if (T.emptyTuple == nullptr || T.one == nullptr) throw py::error_already_set();
 }
 
 // One field of a record. A record is either the wire-format dict, read by key
@@ -431,6 +459,270 @@ std::set<std::string> toNodeNameSet(py::handle v) {
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// The fused decision (schedule_pod): validation and defaulting happen in the
+// same pass that fills the PodSpec, and the answer goes out as a native
+// ScheduleResult instead of a dict that Python unpacks again.
+// ---------------------------------------------------------------------------
+
+// An instance of a plain (dataclass) API class without running its __init__:
+// object.__new__(cls); the caller then sets every field, in field order.
+py::object newInstance(PyObject* cls) {
+  PyTypeObject* tp = reinterpret_cast<PyTypeObject*>(cls);
+  PyObject* o = tp->tp_new(tp, T.emptyTuple, nullptr);
+  if (o == nullptr) throw py::error_already_set();
+  return py::reinterpret_steal<py::object>(o);
+}
+void setAttr(py::handle o, PyObject* name, py::handle value) {
+  if (PyObject_SetAttr(o.ptr(), name, value.ptr()) != 0) throw py::error_already_set();
+}
+
+// AffinityGroupSpec(name=key, members=[AffinityGroupMemberSpec(1, leafCellNumber)])
+py::object defaultAffinityGroup(py::handle podKey, py::handle leafCellNumber) {
+  py::object member = newInstance(T.AffinityGroupMemberSpec);
+  setAttr(member, N.podNumber, T.one);
+  setAttr(member, N.leafCellNumber, leafCellNumber);
+  py::list members(1);
+  PyList_SET_ITEM(members.ptr(), 0, member.release().ptr());
+  py::object group = newInstance(T.AffinityGroupSpec);
+  setAttr(group, N.name, podKey);
+  setAttr(group, N.members, members);
+  return group;
+}
+
+// parsePodSpec plus what validate_pod_scheduling_spec(spec, key) does, in one
+// pass over the PodSchedulingSpec object: the singleton-group default is set
+// on the spec first, then the same checks run in the same order with the same
+// message texts. Nothing of the core is touched before the last check.
+PodSpec parseValidatedPodSpec(py::handle d, py::handle podKey, const std::string& key) {
+  if (PyDict_Check(d.ptr())) {
+    throw py::type_error("schedule_pod validates a PodSchedulingSpec object, not a dict");
+  }
+  PodSpec s;
+  Field leaf(d, N.leafCellNumber);
+  bool defaulted = false;
+  {
+    Field ag(d, N.affinityGroup);
+    if (!ag) {
+      setAttr(d, N.affinityGroup, defaultAffinityGroup(podKey, leaf.get()));
+      defaulted = true;
+    }
+  }
+  s.vc = fstr(d, N.virtualCluster);
+  if (s.vc.empty()) throw HivedError::BadRequest("VirtualCluster is empty");
+  long long priority = fint(d, N.priority);
+  if (priority < kOpportunisticPriority) {
+    throw HivedError::BadRequest("Priority is less than " + std::to_string(kOpportunisticPriority));
+  }
+  if (priority > kMaxGuaranteedPriority) {
+    throw HivedError::BadRequest("Priority is greater than " +
+                                 std::to_string(kMaxGuaranteedPriority));
+  }
+  s.priority = static_cast<int>(priority);
+  long long leafNum = leaf ? toLongLong(leaf.get()) : 0;
+  if (leafNum <= 0) throw HivedError::BadRequest("LeafCellNumber is non-positive");
+  s.leafCellNumber = static_cast<int>(leafNum);
+  if (defaulted) {
+    s.groupName = key;
+    s.groupPodNums[s.leafCellNumber] = 1;
+  } else {
+    Field ag(d, N.affinityGroup);
+    s.groupName = fstr(ag.get(), N.name);
+    if (s.groupName.empty()) throw HivedError::BadRequest("AffinityGroup.Name is empty");
+    bool podInGroup = false;
+    if (Field members{ag.get(), N.members}) {
+      Items ms(members.get());
+      for (Py_ssize_t i = 0; i < ms.size(); i++) {
+        long long podNumber = fint(ms[i], N.podNumber);
+        if (podNumber <= 0) {
+          throw HivedError::BadRequest("AffinityGroup.Members has non-positive PodNumber");
+        }
+        long long memberLeafNum = fint(ms[i], N.leafCellNumber);
+        if (memberLeafNum <= 0) {
+          throw HivedError::BadRequest("AffinityGroup.Members has non-positive LeafCellNumber");
+        }
+        if (memberLeafNum == leafNum) podInGroup = true;
+        s.groupPodNums[static_cast<int>(memberLeafNum)] += static_cast<int>(podNumber);
+      }
+    }
+    if (!podInGroup) {
+      throw HivedError::BadRequest("AffinityGroup.Members does not contain current Pod");
+    }
+  }
+  s.pinnedCellId = fstr(d, N.pinnedCellId);
+  s.leafCellType = fstr(d, N.leafCellType);
+  s.gangReleaseEnable = fbool(d, N.gangReleaseEnable, false);
+  s.lazyPreemptionEnable = fbool(d, N.lazyPreemptionEnable, false);
+  s.ignoreK8sSuggestedNodes = fbool(d, N.ignoreK8sSuggestedNodes, true);
+  s.hbmBytesPerCell = fint(d, N.hbmBytesPerCell);
+  if (s.hbmBytesPerCell < 0) {
+    throw HivedError::BadRequest("hbmBytesPerCell must be non-negative");
+  }
+  return s;
+}
+
+// C++ BindInfo -> PodBindInfo object, with no dict in between; equal to
+// PodBindInfo.from_dict(bindInfoToDict(info)).
+py::object bindInfoToObject(const BindInfo& info) {
+  py::list mbis(info.memberBindInfo.size());
+  for (size_t m = 0; m < info.memberBindInfo.size(); m++) {
+    auto& mbi = info.memberBindInfo[m];
+    py::list placements(mbi.size());
+    for (size_t p = 0; p < mbi.size(); p++) {
+      auto& pl = mbi[p];
+      py::object po = newInstance(T.PodPlacementInfo);
+      setAttr(po, N.physicalNode, pyStr(pl.node));
+      setAttr(po, N.physicalLeafCellIndices, pyIntList(pl.leafIndices));
+      setAttr(po, N.preassignedCellTypes, pyStrList(pl.preassignedTypes));
+      PyList_SET_ITEM(placements.ptr(), static_cast<Py_ssize_t>(p), po.release().ptr());
+    }
+    py::object mo = newInstance(T.AffinityGroupMemberBindInfo);
+    setAttr(mo, N.podPlacements, placements);
+    PyList_SET_ITEM(mbis.ptr(), static_cast<Py_ssize_t>(m), mo.release().ptr());
+  }
+  py::object o = newInstance(T.PodBindInfo);
+  setAttr(o, N.node, pyStr(info.node));
+  setAttr(o, N.leafCellIsolation, pyIntList(info.isolation));
+  setAttr(o, N.cellChain, pyStr(info.chain));
+  setAttr(o, N.affinityGroupBindInfo, mbis);
+  return o;
+}
+
+// The Python-visible ScheduleResult: a plain C-API type (no pybind11 instance
+// bookkeeping per decision) that keeps the core's result as it is and builds
+// each attribute's Python value when it is first read. kind, victim_node and
+// wait_reason are immutable; bind_info and victim_pod_keys are cached so that
+// every read gives the same object. The type takes no part in cyclic GC: the
+// only way to a cycle is to put the result into its own victim_pod_keys list.
+struct PyScheduleResult {
+  PyObject_HEAD
+  PyObject* bindInfo;
+  PyObject* victimNode;
+  PyObject* victimPodKeys;
+  PyObject* waitReason;
+  hived::ScheduleResult r;
+};
+
+void resultDealloc(PyObject* self) {
+  auto* o = reinterpret_cast<PyScheduleResult*>(self);
+  Py_XDECREF(o->bindInfo);
+  Py_XDECREF(o->victimNode);
+  Py_XDECREF(o->victimPodKeys);
+  Py_XDECREF(o->waitReason);
+  o->r.~ScheduleResult();
+  Py_TYPE(self)->tp_free(self);
+}
+
+// Runs `make` once into *slot and hands out a new reference to the cached
+// object; C++ exceptions become the Python error the getter reports.
+template <class Make>
+PyObject* cachedAttr(PyObject** slot, Make make) {
+  if (*slot == nullptr) {
+    try {
+      *slot = make().release().ptr();
+    } catch (py::error_already_set& e) {
+      e.restore();
+      return nullptr;
+    } catch (const std::exception& e) {
+      PyErr_SetString(PyExc_RuntimeError, e.what());
+      return nullptr;
+    }
+  }
+  Py_INCREF(*slot);
+  return *slot;
+}
+
+PyObject* resultKind(PyObject* self, void*) {
+  PyObject* k = nullptr;
+  switch (reinterpret_cast<PyScheduleResult*>(self)->r.kind) {
+    case hived::ScheduleResult::Kind::Bind: k = N.bind; break;
+    case hived::ScheduleResult::Kind::Preempt: k = N.preempt; break;
+    case hived::ScheduleResult::Kind::Wait: k = N.wait; break;
+  }
+  Py_INCREF(k);
+  return k;
+}
+PyObject* resultBindInfo(PyObject* self, void*) {
+  auto* o = reinterpret_cast<PyScheduleResult*>(self);
+  if (o->r.kind != hived::ScheduleResult::Kind::Bind) Py_RETURN_NONE;
+  return cachedAttr(&o->bindInfo, [o] { return bindInfoToObject(o->r.bindInfo); });
+}
+PyObject* resultVictimNode(PyObject* self, void*) {
+  auto* o = reinterpret_cast<PyScheduleResult*>(self);
+  return cachedAttr(&o->victimNode, [o] { return pyStr(o->r.victimNode); });
+}
+PyObject* resultVictimPodKeys(PyObject* self, void*) {
+  auto* o = reinterpret_cast<PyScheduleResult*>(self);
+  return cachedAttr(&o->victimPodKeys, [o] { return pyStrList(o->r.victimPodKeys); });
+}
+PyObject* resultWaitReason(PyObject* self, void*) {
+  auto* o = reinterpret_cast<PyScheduleResult*>(self);
+  return cachedAttr(&o->waitReason, [o] { return pyStr(o->r.waitReason); });
+}
+
+PyObject* resultRepr(PyObject* self) {
+  auto* o = reinterpret_cast<PyScheduleResult*>(self);
+  switch (o->r.kind) {
+    case hived::ScheduleResult::Kind::Bind: {
+      PyObject* info = resultBindInfo(self, nullptr);
+      if (info == nullptr) return nullptr;
+      PyObject* node = PyObject_GetAttr(info, N.node);
+      PyObject* cells = PyObject_GetAttr(info, N.leafCellIsolation);
+      PyObject* out = (node != nullptr && cells != nullptr)
+                          ? PyUnicode_FromFormat("ScheduleResult(bind node=%S cells=%S)", node, cells)
+                          : nullptr;
+      Py_XDECREF(node);
+      Py_XDECREF(cells);
+      Py_DECREF(info);
+      return out;
+    }
+    case hived::ScheduleResult::Kind::Preempt: {
+      PyObject* keys = resultVictimPodKeys(self, nullptr);
+      if (keys == nullptr) return nullptr;
+      PyObject* out = PyUnicode_FromFormat("ScheduleResult(preempt victims=%S)", keys);
+      Py_DECREF(keys);
+      return out;
+    }
+    case hived::ScheduleResult::Kind::Wait:
+      break;
+  }
+  PyObject* reason = resultWaitReason(self, nullptr);
+  if (reason == nullptr) return nullptr;
+  PyObject* out = PyUnicode_FromFormat("ScheduleResult(wait reason=%R)", reason);
+  Py_DECREF(reason);
+  return out;
+}
+
+PyGetSetDef resultGetSet[] = {
+    {"kind", resultKind, nullptr, "\"bind\", \"preempt\" or \"wait\"", nullptr},
+    {"bind_info", resultBindInfo, nullptr, "PodBindInfo of a bind decision, else None", nullptr},
+    {"victim_node", resultVictimNode, nullptr, "node whose pods a preempt decision evicts", nullptr},
+    {"victim_pod_keys", resultVictimPodKeys, nullptr, "pod keys a preempt decision evicts", nullptr},
+    {"wait_reason", resultWaitReason, nullptr, "why a wait decision waits", nullptr},
+    {nullptr, nullptr, nullptr, nullptr, nullptr},
+};
+
+PyTypeObject ResultType = {PyVarObject_HEAD_INIT(nullptr, 0)};
+
+void initResultType(py::module_& m) {
+  ResultType.tp_name = "hivedscheduler_amd.hivedcore.ScheduleResult";
+  ResultType.tp_doc = "One of bind / preempt / wait.";
+  ResultType.tp_basicsize = sizeof(PyScheduleResult);
+  ResultType.tp_flags = Py_TPFLAGS_DEFAULT;
+  ResultType.tp_dealloc = resultDealloc;
+  ResultType.tp_repr = resultRepr;
+  ResultType.tp_getset = resultGetSet;
+  if (PyType_Ready(&ResultType) != 0) throw py::error_already_set();
+  m.add_object("ScheduleResult", reinterpret_cast<PyObject*>(&ResultType));
+}
+
+py::object makeResult(hived::ScheduleResult&& r) {
+  PyScheduleResult* o = PyObject_New(PyScheduleResult, &ResultType);
+  if (o == nullptr) throw py::error_already_set();
+  o->bindInfo = o->victimNode = o->victimPodKeys = o->waitReason = nullptr;
+  new (&o->r) hived::ScheduleResult(std::move(r));
+  return py::reinterpret_steal<py::object>(reinterpret_cast<PyObject*>(o));
+}
 
 py::dict physicalCellStatus(PhysicalCell* c, bool withChildren = true) {
   py::dict d;
@@ -546,7 +838,10 @@ py::dict groupToDict(const Group* g) {
 class PyHivedCore {
  public:
   explicit PyHivedCore(const py::dict& spec) : core_(parseClusterSpec(spec)) {
-    for (auto& node : core_.allNodes()) nodeNames_.push_back(pyStr(node));
+    for (auto& node : core_.allNodes()) {
+      nodeNames_.push_back(pyStr(node));
+      allNodeSet_.insert(node);
+    }
   }
 
   void setNodeHealthy(const std::string& node, bool healthy) { core_.setNodeHealthy(node, healthy); }
@@ -621,6 +916,44 @@ class PyHivedCore {
         break;
     }
     return d;
+  }
+
+  // One filter decision in one call: validate and default the request
+  // (validate), decide, commit a bind decision (commit), and hand out the
+  // native result. suggested_nodes=None stands for every node of the cluster.
+  py::object schedulePod(py::handle spec, py::handle podKey, py::handle suggestedNodes,
+                         py::handle phase, bool commit, bool validate) {
+    if (!PyUnicode_Check(podKey.ptr())) throw py::type_error("pod_key must be a str");
+    if (!PyUnicode_Check(phase.ptr())) throw py::type_error("phase must be a str");
+    if (!suggestedNodes.is_none() && !isNodeNameCollection(suggestedNodes)) {
+      throw py::type_error("suggested_nodes must be a sequence of node names, not " +
+                           std::string(Py_TYPE(suggestedNodes.ptr())->tp_name));
+    }
+    std::string key = toStdString(podKey);
+    PodSpec s = validate ? parseValidatedPodSpec(spec, podKey, key) : parsePodSpec(spec);
+    // as in schedule(): the suggested set is read only where the request, or
+    // an existing group of that name, does not ignore suggested nodes
+    bool needSuggested = !s.ignoreK8sSuggestedNodes;
+    if (!needSuggested) {
+      auto it = core_.groups().find(s.groupName);
+      needSuggested = it != core_.groups().end() && !it->second->ignoreK8sSuggestedNodes;
+    }
+    std::set<std::string> given;
+    const std::set<std::string>* suggested = &given;
+    if (needSuggested) {
+      if (suggestedNodes.is_none()) {
+        suggested = &allNodeSet_;
+      } else {
+        given = toNodeNameSet(suggestedNodes);
+      }
+    }
+    Phase ph = PyUnicode_CompareWithASCIIString(phase.ptr(), "Preempting") == 0 ? Phase::Preempting
+                                                                               : Phase::Filtering;
+    hived::ScheduleResult r = core_.schedule(s, key, *suggested, ph);
+    if (commit && r.kind == hived::ScheduleResult::Kind::Bind) {
+      core_.addAllocatedPod(s, r.bindInfo, key);
+    }
+    return makeResult(std::move(r));
   }
 
   void deleteUnallocatedPod(py::handle spec, const std::string& podKey) {
@@ -771,6 +1104,8 @@ class PyHivedCore {
  private:
   HivedCore core_;
   std::vector<py::object> nodeNames_;
+  // every node name, for schedule_pod(suggested_nodes=None)
+  std::set<std::string> allNodeSet_;
 };
 
 }  // namespace
@@ -778,6 +1113,8 @@ class PyHivedCore {
 PYBIND11_MODULE(hivedcore, m) {
   m.doc() = "MI355X-native gang scheduler core (C++)";
   initNames();
+  initApiTypes();
+  initResultType(m);
 
   static py::exception<HivedError> exc(m, "CoreError");
   py::register_exception_translator([](std::exception_ptr p) {
@@ -803,6 +1140,9 @@ PYBIND11_MODULE(hivedcore, m) {
       .def("bad_nodes", &PyHivedCore::badNodes)
       .def("schedule", &PyHivedCore::schedule, py::arg("pod_spec"), py::arg("pod_key"),
            py::arg("suggested_nodes"), py::arg("phase"))
+      .def("schedule_pod", &PyHivedCore::schedulePod, py::arg("pod_spec"), py::arg("pod_key"),
+           py::arg("suggested_nodes") = py::none(), py::arg("phase") = "Filtering",
+           py::arg("commit") = false, py::arg("validate") = true)
       .def("delete_unallocated_pod", &PyHivedCore::deleteUnallocatedPod, py::arg("pod_spec"),
            py::arg("pod_key"))
       .def("add_allocated_pod", &PyHivedCore::addAllocatedPod, py::arg("pod_spec"),

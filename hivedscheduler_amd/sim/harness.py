@@ -114,12 +114,8 @@ class SimScheduler:
     ) -> ScheduleResult:
         """Schedule a pod; on a bind decision, optimistically commit it
         (AddAllocatedPod) like scheduler.go:518-539 does."""
-        validate_pod_scheduling_spec(spec, key)
-        if suggested is None:
-            suggested = self.alg.all_nodes()
-        result = self.alg.schedule(spec, key, suggested, phase)
-        if result.kind == "bind" and commit:
-            self.alg.add_allocated_pod(spec, result.bind_info, key)
+        result = self.alg.schedule_pod(spec, key, suggested, phase, commit)
+        if commit and result.kind == "bind":
             self.pods[key] = (spec, result.bind_info)
         return result
 
