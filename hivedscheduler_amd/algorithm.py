@@ -8,7 +8,7 @@ The sequencing contract is the caller's job (HivedScheduler serializes calls).
 from __future__ import annotations
 
 import threading
-from typing import Dict, List, Optional
+from typing import Dict, List
 
 from . import hivedcore
 from .api import constants
@@ -57,7 +57,16 @@ ScheduleResult = hivedcore.ScheduleResult
 
 class HivedAlgorithm:
     """Thread-safe wrapper: a single lock serializes all calls, matching the
-    reference's algorithmLock (hived_algorithm.go:104)."""
+    reference's algorithmLock (hived_algorithm.go:104).
+
+    The one call per decision, `schedule_pod`, is the exception: it is the
+    core's own native method, bound in __init__, with no Python frame, lock or
+    `try` around it. The core holds the GIL from its first read of core state
+    to its last write and runs no Python code in between (see
+    PyHivedCore::schedulePod in core/bindings.cpp), so the lock would serialise
+    nothing there that the GIL does not, and the native method itself turns a
+    core error into the WebServerError that `_call` raises.
+    """
 
     def __init__(self, config: Config):
         self._lock = threading.RLock()
@@ -66,6 +75,13 @@ class HivedAlgorithm:
         except hivedcore.CoreError as e:
             raise WebServerError(getattr(e, "code", 500), str(e)) from e
         self._config = config
+        # schedule_pod(spec, pod_key, suggested_nodes=None, phase=FILTERING,
+        #              commit=False) -> ScheduleResult
+        # One whole filter decision in one core call: validate and default the
+        # spec (as validate_pod_scheduling_spec does), decide, and with
+        # commit=True add the pod as allocated on a bind decision.
+        # suggested_nodes=None stands for every node of the cluster.
+        self.schedule_pod = self._core.schedule_validated_pod
 
     def _call(self, fn, *args):
         with self._lock:
@@ -129,21 +145,6 @@ class HivedAlgorithm:
             raise TypeError("suggested_nodes must be a sequence of node names, not NoneType")
         return self._call(self._core.schedule_pod, spec, pod_key, suggested_nodes, phase,
                           False, False)
-
-    def schedule_pod(
-        self,
-        spec: PodSchedulingSpec,
-        pod_key: str,
-        suggested_nodes: Optional[List[str]] = None,
-        phase: str = FILTERING,
-        commit: bool = False,
-    ) -> ScheduleResult:
-        """One whole filter decision in one core call: validate and default
-        the spec (as validate_pod_scheduling_spec does), decide, and with
-        commit=True add the pod as allocated on a bind decision.
-        suggested_nodes=None stands for every node of the cluster."""
-        return self._call(self._core.schedule_pod, spec, pod_key, suggested_nodes, phase,
-                          commit, True)
 
     def add_unallocated_pod(self, spec: PodSchedulingSpec, pod_key: str) -> None:
         pass  # parity: reference AddUnallocatedPod is a no-op

@@ -174,28 +174,35 @@ ScheduleResult HivedCore::schedule(const PodSpec& s, const std::string& podKey,
   bool havePlacement = false;
 
   auto it = groups_.find(s.groupName);
-  if (it != groups_.end()) {
+  bool groupExists = it != groups_.end();
+  // a group can come into being below only in the Preempting phase
+  // (createPreemptingGroup), so a Filtering miss needs no second lookup
+  bool mayHaveGroup = groupExists || phase == Phase::Preempting;
+  if (groupExists) {
     havePlacement = schedulePodFromExistingGroup(it->second.get(), s, suggestedNodes, phase,
                                                  podKey, &phys, &hasVirtual, &virt, &victims,
                                                  &podIndex);
+    // the group may have been a preempting group deleted just above
+    groupExists = groups_.find(s.groupName) != groups_.end();
   }
-  // the group may have been a preempting group deleted just above
-  if (groups_.find(s.groupName) == groups_.end()) {
+  if (!groupExists) {
     schedulePodFromNewGroup(s, suggestedNodes, phase, podKey, &phys, &hasVirtual, &virt, &victims,
                             &waitReason);
     havePlacement = !phys.empty();
   }
   (void)havePlacement;
   Group* g = nullptr;
-  if (auto git = groups_.find(s.groupName); git != groups_.end()) g = git->second.get();
-  return generateResult(phys, hasVirtual, virt, victims, waitReason, s.leafCellNumber, podIndex, g,
-                        s.groupName);
+  if (mayHaveGroup) {
+    if (auto git = groups_.find(s.groupName); git != groups_.end()) g = git->second.get();
+  }
+  return generateResult(phys, hasVirtual, virt, victims, std::move(waitReason), s.leafCellNumber,
+                        podIndex, g, s.groupName);
 }
 
 ScheduleResult HivedCore::generateResult(const Placement<PhysicalCell>& phys, bool hasVirtual,
                                          const Placement<VirtualCell>& virt,
                                          const std::map<std::string, std::set<std::string>>& victims,
-                                         const std::string& waitReason, int currentLeafNum,
+                                         std::string&& waitReason, int currentLeafNum,
                                          int podIndex, Group* group,
                                          const std::string& groupName) {
   ScheduleResult r;
@@ -204,7 +211,7 @@ ScheduleResult HivedCore::generateResult(const Placement<PhysicalCell>& phys, bo
     if (waitReason.empty()) {
       r.waitReason = "waiting for resources";
     } else {
-      r.waitReason = waitReason;
+      r.waitReason = std::move(waitReason);  // the caller's buffer, not a copy
     }
     return r;
   }
@@ -338,31 +345,28 @@ bool HivedCore::scheduleNewAffinityGroup(const PodSpec& s,
                                          const std::string& podKey, Placement<PhysicalCell>* phys,
                                          bool* hasVirtual, Placement<VirtualCell>* virt,
                                          std::string* failedReason) {
-  SchedulingRequest sr;
-  sr.vc = s.vc;
-  sr.pinnedCellId = s.pinnedCellId;
-  sr.priority = s.priority;
-  sr.groupName = s.groupName;
-  sr.podLeafCellNums = s.groupPodNums;
+  SchedulingRequest sr(s);  // refers to the spec's strings and map, copies none
   sr.suggestedNodes = &suggestedNodes;
   sr.ignoreSuggestedNodes = s.ignoreK8sSuggestedNodes;
   sr.hbmBytes = s.hbmBytesPerCell;
-  validateSchedulingRequest(sr, podKey);
+  validateSchedulingRequest(sr, podKey);  // also resolves sr.vcScheduler
   if (!sr.pinnedCellId.empty()) {
-    sr.chain = pinnedPhysical_[s.vc][s.pinnedCellId]->chain;
+    sr.chain = &pinnedPhysical_[s.vc][s.pinnedCellId]->chain;
+    auto it = sr.vcScheduler->pinnedSchedulers.find(sr.pinnedCellId);
+    sr.topo = it == sr.vcScheduler->pinnedSchedulers.end() ? nullptr : &it->second;
     return handleSchedulingRequest(sr, phys, hasVirtual, virt, failedReason);
   }
   if (!s.leafCellType.empty()) {
-    if (!cellChains_.count(s.leafCellType)) {
+    auto it = cellChains_.find(s.leafCellType);
+    if (it == cellChains_.end()) {
       throw HivedError::BadRequest("[" + podKey + "]: Pod requesting leaf cell type " +
                                    s.leafCellType + " which the whole cluster does not have");
     }
-    return scheduleForLeafCellType(sr, s.leafCellType, podKey, true, phys, hasVirtual, virt,
-                                   failedReason);
+    return scheduleForLeafCellType(sr, s.leafCellType, it->second, podKey, true, phys, hasVirtual,
+                                   virt, failedReason);
   }
   for (auto& [leafType, chains] : cellChains_) {
-    (void)chains;
-    if (scheduleForLeafCellType(sr, leafType, podKey, false, phys, hasVirtual, virt,
+    if (scheduleForLeafCellType(sr, leafType, chains, podKey, false, phys, hasVirtual, virt,
                                 failedReason)) {
       return true;
     }
@@ -371,17 +375,25 @@ bool HivedCore::scheduleNewAffinityGroup(const PodSpec& s,
 }
 
 bool HivedCore::scheduleForLeafCellType(SchedulingRequest& sr, const std::string& leafCellType,
+                                        const std::vector<std::string>& chains,
                                         const std::string& podKey, bool typeSpecified,
                                         Placement<PhysicalCell>* phys, bool* hasVirtual,
                                         Placement<VirtualCell>* virt, std::string* failedReason) {
   bool vcHasType = false;
-  for (const std::string& chain : cellChains_[leafCellType]) {
-    if (sr.priority < kMinGuaranteedPriority ||
-        vcSchedulers_[sr.vc].nonPinnedFull.count(chain)) {
-      vcHasType = true;
-      sr.chain = chain;
-      if (handleSchedulingRequest(sr, phys, hasVirtual, virt, failedReason)) return true;
+  for (const std::string& chain : chains) {
+    // one lookup per chain: the placement engine every attempt on it uses.
+    // A VC has an engine for exactly the chains it has cells of
+    // (nonPinnedSchedulers is built from nonPinnedFull, key for key).
+    if (sr.priority < kMinGuaranteedPriority) {
+      sr.topo = &opportunisticSchedulers_.at(chain);
+    } else {
+      auto it = sr.vcScheduler->nonPinnedSchedulers.find(chain);
+      if (it == sr.vcScheduler->nonPinnedSchedulers.end()) continue;
+      sr.topo = &it->second;
     }
+    vcHasType = true;
+    sr.chain = &chain;
+    if (handleSchedulingRequest(sr, phys, hasVirtual, virt, failedReason)) return true;
   }
   if (typeSpecified && sr.priority >= kMinGuaranteedPriority && !vcHasType) {
     throw HivedError::BadRequest("[" + podKey + "]: Pod requesting leaf cell type " + leafCellType +
@@ -390,15 +402,19 @@ bool HivedCore::scheduleForLeafCellType(SchedulingRequest& sr, const std::string
   return false;
 }
 
-void HivedCore::validateSchedulingRequest(const SchedulingRequest& sr, const std::string& podKey) {
+void HivedCore::validateSchedulingRequest(SchedulingRequest& sr, const std::string& podKey) {
   std::string message;
-  if (!vcSchedulers_.count(sr.vc)) {
+  auto vcIt = vcSchedulers_.find(sr.vc);
+  if (vcIt == vcSchedulers_.end()) {
     message = "VC " + sr.vc + " does not exist!";
-  } else if (!sr.pinnedCellId.empty()) {
-    if (!vcSchedulers_[sr.vc].pinned.count(sr.pinnedCellId)) {
-      message = "VC " + sr.vc + " does not have pinned cell " + sr.pinnedCellId;
-    } else if (sr.priority == kOpportunisticPriority) {
-      message = "opportunistic pod not supported to use pinned cell " + sr.pinnedCellId;
+  } else {
+    sr.vcScheduler = &vcIt->second;  // resolved here once for the whole request
+    if (!sr.pinnedCellId.empty()) {
+      if (!sr.vcScheduler->pinned.count(sr.pinnedCellId)) {
+        message = "VC " + sr.vc + " does not have pinned cell " + sr.pinnedCellId;
+      } else if (sr.priority == kOpportunisticPriority) {
+        message = "opportunistic pod not supported to use pinned cell " + sr.pinnedCellId;
+      }
     }
   }
   if (!message.empty()) throw HivedError::BadRequest("[" + podKey + "]: " + message);
@@ -431,13 +447,19 @@ bool HivedCore::scheduleGuaranteedGroup(SchedulingRequest& sr, Placement<Physica
     }
   } restoreSteering{sr, sr.honorLinksOnly, sr.cleanWorld};
 
+  // the chain's cells and whether any of its links is degraded, looked up
+  // once: nothing below changes a link (bad links change only through
+  // setXgmiLinkHealthy, a top-level operation of its own)
+  const ChainCellList& fullCells = fullCellList_[*sr.chain];
+  const bool badLinks = chainHasBadLinks(fullCells);
+
   // One full placement attempt: intra-VC schedule -> lazy preemption ->
   // binding-vertex construction -> virtual->physical mapping. honorOnly
   // restricts both the descent and the mapping to link-clean choices
   // within sr.cleanWorld; reverts lazy preemption on failure.
   auto attemptOnce = [&](bool honorOnly) -> bool {
     sr.honorLinksOnly = honorOnly;
-    if (!vcSchedulers_[sr.vc].schedule(sr, virt, failedReason)) return false;
+    if (!sr.vcScheduler->schedule(sr, virt, failedReason)) return false;
     if (mapDebugRelease()) {
       for (auto& [ln, pods] : *virt) {
         for (auto& pod : pods) {
@@ -508,16 +530,16 @@ bool HivedCore::scheduleGuaranteedGroup(SchedulingRequest& sr, Placement<Physica
     const std::unordered_map<VirtualCell*, PhysicalCell*> seedBindings = bindings;
     auto tryMap = [&](bool honorLinks) {
       bindings = seedBindings;  // drop partial picks from a failed attempt
-      std::map<int, int> freeCellNumCopy = allVCFreeCellNum_[sr.chain];
+      std::map<int, int> freeCellNumCopy = allVCFreeCellNum_[*sr.chain];
       return mapVirtualPlacementToPhysical(preassigned, nonPreassigned,
-                                           freeCellList_[sr.chain].shallowCopy(), freeCellNumCopy,
+                                           freeCellList_[*sr.chain].shallowCopy(), freeCellNumCopy,
                                            *sr.suggestedNodes, sr.ignoreSuggestedNodes, bindings,
                                            sr.hbmBytes, honorLinks, sr.cleanWorld);
     };
     bool mapped;
     if (honorOnly) {
       mapped = tryMap(true);
-    } else if (sr.cleanWorld != nullptr || chainHasBadLinks(sr.chain)) {
+    } else if (sr.cleanWorld != nullptr || badLinks) {
       mapped = tryMap(true) || tryMap(false);
     } else {
       mapped = tryMap(false);
@@ -549,7 +571,7 @@ bool HivedCore::scheduleGuaranteedGroup(SchedulingRequest& sr, Placement<Physica
   // should use — degraded endpoints).
   int gangLeaves = 0;
   for (auto& [ln, pn] : sr.podLeafCellNums) gangLeaves += ln * pn;
-  if (chainHasBadLinks(sr.chain) && gangLeaves >= 2) {
+  if (badLinks && gangLeaves >= 2) {
     const std::set<std::string>* filter =
         sr.ignoreSuggestedNodes ? nullptr : sr.suggestedNodes;
     // Link-clean placements take precedence over dirty ones even when
@@ -566,20 +588,20 @@ bool HivedCore::scheduleGuaranteedGroup(SchedulingRequest& sr, Placement<Physica
       std::vector<CleanShapeWorld> computed;
       const std::vector<CleanShapeWorld>* worldsPtr;
       if (filter == nullptr) {
-        WorldCacheEntry& entry = worldCache_[{sr.chain, tier}];
+        WorldCacheEntry& entry = worldCache_[{*sr.chain, tier}];
         if (entry.epoch != gWorldEpochCounter) {
-          entry.worlds = computeCleanShapeWorlds(fullCellList_[sr.chain], nullptr, 4, tier);
+          entry.worlds = computeCleanShapeWorlds(fullCells, nullptr, 4, tier);
           entry.epoch = gWorldEpochCounter;
         }
         worldsPtr = &entry.worlds;
       } else {
-        computed = computeCleanShapeWorlds(fullCellList_[sr.chain], filter, 4, tier);
+        computed = computeCleanShapeWorlds(fullCells, filter, 4, tier);
         worldsPtr = &computed;
       }
       for (const auto& w : *worldsPtr) {
         sr.cleanWorld = &w;
         if (mapDebugRelease()) {
-          fprintf(stderr, "[world] chain=%s tier=%d excl=%zu:", sr.chain.c_str(), tier,
+          fprintf(stderr, "[world] chain=%s tier=%d excl=%zu:", sr.chain->c_str(), tier,
                   w.excluded.size());
           for (auto& [l, v] : w.caps) fprintf(stderr, " L%d=%d", l, v);
           fprintf(stderr, "\n");
@@ -599,8 +621,7 @@ bool HivedCore::scheduleGuaranteedGroup(SchedulingRequest& sr, Placement<Physica
   return false;
 }
 
-bool HivedCore::chainHasBadLinks(const std::string& chain) {
-  auto& ccl = fullCellList_[chain];
+bool HivedCore::chainHasBadLinks(const ChainCellList& ccl) {
   for (Cell* c : ccl.at(ccl.top())) {
     if (static_cast<PhysicalCell*>(c)->badLinksUnder > 0) return true;
   }
@@ -630,9 +651,9 @@ bool HivedCore::scheduleOpportunisticGroup(const SchedulingRequest& sr,
                                            Placement<PhysicalCell>* phys,
                                            std::string* failedReason) {
   Placement<Cell> generic;
-  if (!opportunisticSchedulers_.at(sr.chain).Schedule(sr.podLeafCellNums, kOpportunisticPriority,
-                                                      *sr.suggestedNodes, sr.ignoreSuggestedNodes,
-                                                      &generic, failedReason, sr.hbmBytes)) {
+  // sr.topo: the chain's opportunistic engine (scheduleForLeafCellType)
+  if (!sr.topo->Schedule(sr.podLeafCellNums, kOpportunisticPriority, *sr.suggestedNodes,
+                         sr.ignoreSuggestedNodes, &generic, failedReason, sr.hbmBytes)) {
     failedReason->append(" when scheduling in physical cluster");
     return false;
   }

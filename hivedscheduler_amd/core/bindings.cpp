@@ -8,6 +8,7 @@
 #include <climits>
 #include <cstring>
 #include <functional>
+#include <mutex>
 
 #include "core.hpp"
 
@@ -144,6 +145,17 @@ struct Names {
   PyObject* victimNode;
   PyObject* victimPodKeys;
   PyObject* reason;
+  // schedule_pod: argument names in positional order, phase values
+  PyObject* pod_spec;
+  PyObject* spec;  // the facade's name for pod_spec
+  PyObject* pod_key;
+  PyObject* suggested_nodes;
+  PyObject* phase;
+  PyObject* commit;
+  PyObject* validate;
+  PyObject* Filtering;
+  PyObject* Preempting;
+  PyObject* code;
 };
 Names N{};
 
@@ -184,6 +196,16 @@ void initNames() {
   HIVED_NAME(victimNode);
   HIVED_NAME(victimPodKeys);
   HIVED_NAME(reason);
+  HIVED_NAME(pod_spec);
+  HIVED_NAME(spec);
+  HIVED_NAME(pod_key);
+  HIVED_NAME(suggested_nodes);
+  HIVED_NAME(phase);
+  HIVED_NAME(commit);
+  HIVED_NAME(validate);
+  HIVED_NAME(Filtering);
+  HIVED_NAME(Preempting);
+  HIVED_NAME(code);
 #undef HIVED_NAME
 }
 
@@ -195,6 +217,7 @@ struct ApiTypes {
   PyObject* PodBindInfo;
   PyObject* AffinityGroupMemberBindInfo;
   PyObject* PodPlacementInfo;
+  PyObject* WebServerError;
   PyObject* emptyTuple;
   PyObject* one;
 };
@@ -208,6 +231,7 @@ void initApiTypes() {
   HIVED_TYPE(PodBindInfo);
   HIVED_TYPE(AffinityGroupMemberBindInfo);
   HIVED_TYPE(PodPlacementInfo);
+  HIVED_TYPE(WebServerError);
 #undef HIVED_TYPE
   T.emptyTuple = PyTuple_New(0);
   T.one = PyLong_FromLong(1);
@@ -835,6 +859,23 @@ py::dict groupToDict(const Group* g) {
   return d;
 }
 
+// The stretch of a call that reads or writes core state. With a GIL that
+// stretch is whole already (see PyHivedCore::schedulePod) and this is nothing.
+// A free-threaded interpreter (Py_GIL_DISABLED) has no such guarantee, so there
+// the decision and the calls that change core state take a native mutex; the
+// code inside a section is C++ only and never calls into Python, so the mutex
+// cannot be held across a thread switch that needs it. (HIVED_CORE_MUTEX turns
+// the mutex on in a GIL build, to compile and test this path.)
+#if defined(Py_GIL_DISABLED) || defined(HIVED_CORE_MUTEX)
+using CoreMutex = std::mutex;
+using CoreSection = std::lock_guard<std::mutex>;
+#else
+struct CoreMutex {};
+struct CoreSection {
+  explicit CoreSection(CoreMutex&) {}
+};
+#endif
+
 class PyHivedCore {
  public:
   explicit PyHivedCore(const py::dict& spec) : core_(parseClusterSpec(spec)) {
@@ -844,11 +885,16 @@ class PyHivedCore {
     }
   }
 
-  void setNodeHealthy(const std::string& node, bool healthy) { core_.setNodeHealthy(node, healthy); }
+  void setNodeHealthy(const std::string& node, bool healthy) {
+    CoreSection section(coreMutex_);
+    core_.setNodeHealthy(node, healthy);
+  }
   void setLeafCellHealthy(const std::string& node, int leafIndex, bool healthy) {
+    CoreSection section(coreMutex_);
     core_.setLeafCellHealthy(node, leafIndex, healthy);
   }
   void setXgmiLinkHealthy(const std::string& node, int a, int b, bool healthy, double gbps) {
+    CoreSection section(coreMutex_);
     core_.setXgmiLinkHealthy(node, a, b, healthy, gbps);
   }
   py::list xgmiLinks(const std::string& node) const {
@@ -892,13 +938,17 @@ class PyHivedCore {
     // never converted.
     bool needSuggested = !s.ignoreK8sSuggestedNodes;
     if (!needSuggested) {
+      CoreSection section(coreMutex_);
       auto it = core_.groups().find(s.groupName);
       needSuggested = it != core_.groups().end() && !it->second->ignoreK8sSuggestedNodes;
     }
     std::set<std::string> suggested;
     if (needSuggested) suggested = toNodeNameSet(suggestedNodes);
     Phase ph = (phase == "Preempting") ? Phase::Preempting : Phase::Filtering;
-    ScheduleResult r = core_.schedule(s, podKey, suggested, ph);
+    ScheduleResult r = [&] {
+      CoreSection section(coreMutex_);
+      return core_.schedule(s, podKey, suggested, ph);
+    }();
     py::dict d;
     switch (r.kind) {
       case ScheduleResult::Kind::Bind:
@@ -921,10 +971,32 @@ class PyHivedCore {
   // One filter decision in one call: validate and default the request
   // (validate), decide, commit a bind decision (commit), and hand out the
   // native result. suggested_nodes=None stands for every node of the cluster.
+  //
+  // This call is not under HivedAlgorithm's lock (the facade binds the native
+  // method itself, see scheduleValidatedPodEntry). What keeps it whole is the
+  // GIL: no method of this class releases it, and between the first read of
+  // core state below (the group peek) and the last write (addAllocatedPod)
+  // this function runs no Python code, so no other thread can get in between.
+  // Everything that can run Python code sits outside that stretch: the spec is
+  // parsed before it ("nothing of the core is touched before the last check"),
+  // the result object is built after it, and the one conversion in between,
+  // toNodeNameSet, runs only when the peek said the names are needed; should
+  // another thread change the group meanwhile, the names are converted for
+  // nothing, and the decision itself is taken in one piece afterwards. Without
+  // a GIL (Py_GIL_DISABLED) a native mutex takes its place, see CoreSection.
   py::object schedulePod(py::handle spec, py::handle podKey, py::handle suggestedNodes,
                          py::handle phase, bool commit, bool validate) {
     if (!PyUnicode_Check(podKey.ptr())) throw py::type_error("pod_key must be a str");
-    if (!PyUnicode_Check(phase.ptr())) throw py::type_error("phase must be a str");
+    // phase: absent means Filtering; the two constants are interned strings,
+    // so they are told apart by identity before anything is compared
+    Phase ph = Phase::Filtering;
+    if (phase.ptr() != nullptr && phase.ptr() != N.Filtering) {
+      if (!PyUnicode_Check(phase.ptr())) throw py::type_error("phase must be a str");
+      if (phase.ptr() == N.Preempting ||
+          PyUnicode_CompareWithASCIIString(phase.ptr(), "Preempting") == 0) {
+        ph = Phase::Preempting;
+      }
+    }
     if (!suggestedNodes.is_none() && !isNodeNameCollection(suggestedNodes)) {
       throw py::type_error("suggested_nodes must be a sequence of node names, not " +
                            std::string(Py_TYPE(suggestedNodes.ptr())->tp_name));
@@ -935,6 +1007,7 @@ class PyHivedCore {
     // an existing group of that name, does not ignore suggested nodes
     bool needSuggested = !s.ignoreK8sSuggestedNodes;
     if (!needSuggested) {
+      CoreSection section(coreMutex_);
       auto it = core_.groups().find(s.groupName);
       needSuggested = it != core_.groups().end() && !it->second->ignoreK8sSuggestedNodes;
     }
@@ -947,23 +1020,33 @@ class PyHivedCore {
         given = toNodeNameSet(suggestedNodes);
       }
     }
-    Phase ph = PyUnicode_CompareWithASCIIString(phase.ptr(), "Preempting") == 0 ? Phase::Preempting
-                                                                               : Phase::Filtering;
-    hived::ScheduleResult r = core_.schedule(s, key, *suggested, ph);
-    if (commit && r.kind == hived::ScheduleResult::Kind::Bind) {
-      core_.addAllocatedPod(s, r.bindInfo, key);
-    }
+    hived::ScheduleResult r = [&] {
+      CoreSection section(coreMutex_);  // pure C++ in here: no Python call
+      hived::ScheduleResult decided = core_.schedule(s, key, *suggested, ph);
+      if (commit && decided.kind == hived::ScheduleResult::Kind::Bind) {
+        core_.addAllocatedPod(s, decided.bindInfo, key);
+      }
+      return decided;
+    }();
     return makeResult(std::move(r));
   }
 
   void deleteUnallocatedPod(py::handle spec, const std::string& podKey) {
-    core_.deleteUnallocatedPod(parsePodSpec(spec), podKey);
+    PodSpec s = parsePodSpec(spec);
+    CoreSection section(coreMutex_);
+    core_.deleteUnallocatedPod(s, podKey);
   }
   void addAllocatedPod(py::handle spec, py::handle bindInfo, const std::string& podKey) {
-    core_.addAllocatedPod(parsePodSpec(spec), parseBindInfo(bindInfo), podKey);
+    PodSpec s = parsePodSpec(spec);
+    BindInfo info = parseBindInfo(bindInfo);
+    CoreSection section(coreMutex_);
+    core_.addAllocatedPod(s, info, podKey);
   }
   void deleteAllocatedPod(py::handle spec, py::handle bindInfo, const std::string& podKey) {
-    core_.deleteAllocatedPod(parsePodSpec(spec), parseBindInfo(bindInfo), podKey);
+    PodSpec s = parsePodSpec(spec);
+    BindInfo info = parseBindInfo(bindInfo);
+    CoreSection section(coreMutex_);
+    core_.deleteAllocatedPod(s, info, podKey);
   }
 
   py::list getAllAffinityGroups() const {
@@ -1106,7 +1189,207 @@ class PyHivedCore {
   std::vector<py::object> nodeNames_;
   // every node name, for schedule_pod(suggested_nodes=None)
   std::set<std::string> allNodeSet_;
+  CoreMutex coreMutex_;
 };
+
+// ---------------------------------------------------------------------------
+// The direct entry of the fused decision. schedule_pod is called once per
+// decision, and pybind11's generic dispatcher (overload record, argument-loader
+// tuple, one caster per argument) costs more there than the arguments are
+// worth, so the method is a hand-written vectorcall function
+// (METH_FASTCALL | METH_KEYWORDS) set on the pybind11 class as a method
+// descriptor; the descriptor checks that self is a HivedCore. Everything else
+// of the class stays on pybind11.
+//
+//   schedule_pod(pod_spec, pod_key, suggested_nodes=None, phase="Filtering",
+//                commit=False, validate=True)              errors: CoreError
+//   schedule_validated_pod(spec, pod_key, suggested_nodes=None,
+//                phase="Filtering", commit=False)           errors: WebServerError
+//
+// The second is the first with validate=True and the facade's error protocol:
+// a core error leaves as WebServerError(code, text) with the CoreError as its
+// __cause__, which is what HivedAlgorithm._call makes of it. HivedAlgorithm
+// binds it as its schedule_pod, so no Python frame stands between a caller and
+// the core.
+// ---------------------------------------------------------------------------
+
+PyObject* gCoreError = nullptr;   // the CoreError class, set at module init
+PyTypeObject* gCoreType = nullptr;  // the HivedCore class
+
+// CoreError(text) with .code; a new reference, or nullptr with an error set
+PyObject* newCoreError(const HivedError& e) {
+  PyObject* text = PyUnicode_FromString(e.what());
+  if (text == nullptr) return nullptr;
+  PyObject* inst = PyObject_CallFunctionObjArgs(gCoreError, text, nullptr);
+  Py_DECREF(text);
+  if (inst == nullptr) return nullptr;
+  PyObject* code = PyLong_FromLong(e.code);
+  if (code == nullptr || PyObject_SetAttr(inst, N.code, code) != 0) {
+    Py_XDECREF(code);
+    Py_DECREF(inst);
+    return nullptr;
+  }
+  Py_DECREF(code);
+  return inst;
+}
+
+// Leaves the Python error for a HivedError: CoreError, or for the facade's
+// entry `raise WebServerError(e.code, str(e)) from e`.
+void setCoreError(const HivedError& e, bool asWebServerError) {
+  PyObject* inst = newCoreError(e);
+  if (inst == nullptr) return;
+  if (!asWebServerError) {
+    PyErr_SetObject(gCoreError, inst);
+    Py_DECREF(inst);
+    return;
+  }
+  PyObject* web = PyObject_CallFunction(T.WebServerError, "is", e.code, e.what());
+  if (web == nullptr) {
+    Py_DECREF(inst);
+    return;
+  }
+  Py_INCREF(inst);
+  PyException_SetCause(web, inst);    // steals; also sets __suppress_context__
+  PyException_SetContext(web, inst);  // steals
+  PyErr_SetObject(T.WebServerError, web);
+  Py_DECREF(web);
+}
+
+// A bool argument as pybind11's caster takes it: True / False, None as False,
+// or anything with __bool__.
+bool toFlag(PyObject* o, const char* name) {
+  if (o == Py_True) return true;
+  if (o == Py_False || o == Py_None) return false;
+  PyNumberMethods* num = Py_TYPE(o)->tp_as_number;
+  if (num != nullptr && num->nb_bool != nullptr) {
+    int r = num->nb_bool(o);
+    if (r < 0) throw py::error_already_set();
+    return r != 0;
+  }
+  throw py::type_error(std::string(name) + " must be a bool");
+}
+
+PyHivedCore* coreOf(PyObject* self) {
+  // instances of the class itself keep the C++ object at the head of
+  // pybind11's simple layout; subclasses go through the caster
+  if (Py_TYPE(self) == gCoreType) {
+    auto* inst = reinterpret_cast<py::detail::instance*>(self);
+    if (inst->simple_layout && inst->simple_value_holder[0] != nullptr) {
+      return static_cast<PyHivedCore*>(inst->simple_value_holder[0]);
+    }
+  }
+  return py::cast<PyHivedCore*>(py::handle(self));
+}
+
+constexpr int kSchedulePodArgs = 6;
+
+PyObject* schedulePodCall(PyObject* self, PyObject* const* args, Py_ssize_t nargs,
+                          PyObject* kwnames, bool facade) {
+  const char* fn = facade ? "schedule_validated_pod" : "schedule_pod";
+  const int maxArgs = facade ? kSchedulePodArgs - 1 : kSchedulePodArgs;
+  PyObject* const names[kSchedulePodArgs] = {facade ? N.spec : N.pod_spec, N.pod_key,
+                                             N.suggested_nodes,            N.phase,
+                                             N.commit,                     N.validate};
+  PyObject* a[kSchedulePodArgs] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  Py_ssize_t nkw = kwnames == nullptr ? 0 : PyTuple_GET_SIZE(kwnames);
+  if (nargs + nkw > maxArgs) {
+    PyErr_Format(PyExc_TypeError, "%s() takes at most %d arguments (%zd given)", fn, maxArgs,
+                 nargs + nkw);
+    return nullptr;
+  }
+  for (Py_ssize_t i = 0; i < nargs; i++) a[i] = args[i];
+  for (Py_ssize_t k = 0; k < nkw; k++) {
+    PyObject* name = PyTuple_GET_ITEM(kwnames, k);
+    int idx = -1;
+    for (int j = 0; j < maxArgs; j++) {  // keyword names are interned as a rule
+      if (name == names[j]) {
+        idx = j;
+        break;
+      }
+    }
+    for (int j = 0; idx < 0 && j < maxArgs; j++) {
+      int eq = PyObject_RichCompareBool(name, names[j], Py_EQ);
+      if (eq < 0) return nullptr;
+      if (eq) idx = j;
+    }
+    if (idx < 0) {
+      PyErr_Format(PyExc_TypeError, "%s() got an unexpected keyword argument '%U'", fn, name);
+      return nullptr;
+    }
+    if (a[idx] != nullptr) {
+      PyErr_Format(PyExc_TypeError, "%s() got multiple values for argument '%U'", fn, name);
+      return nullptr;
+    }
+    a[idx] = args[nargs + k];
+  }
+  for (int j = 0; j < 2; j++) {
+    if (a[j] == nullptr) {
+      PyErr_Format(PyExc_TypeError, "%s() missing required argument '%U' (pos %d)", fn, names[j],
+                   j + 1);
+      return nullptr;
+    }
+  }
+  try {
+    bool commit = a[4] != nullptr && toFlag(a[4], "commit");
+    bool validate = a[5] == nullptr || toFlag(a[5], "validate");
+    return coreOf(self)
+        ->schedulePod(a[0], a[1], a[2] != nullptr ? a[2] : Py_None, a[3], commit, validate)
+        .release()
+        .ptr();
+  } catch (py::error_already_set& e) {
+    e.restore();
+  } catch (const py::builtin_exception& e) {
+    e.set_error();
+  } catch (const HivedError& e) {
+    setCoreError(e, facade);
+  } catch (const std::bad_alloc&) {
+    PyErr_NoMemory();
+  } catch (const std::out_of_range& e) {
+    PyErr_SetString(PyExc_IndexError, e.what());
+  } catch (const std::exception& e) {
+    PyErr_SetString(PyExc_RuntimeError, e.what());
+  }
+  return nullptr;
+}
+
+PyObject* schedulePodEntry(PyObject* self, PyObject* const* args, Py_ssize_t nargs,
+                           PyObject* kwnames) {
+  return schedulePodCall(self, args, nargs, kwnames, false);
+}
+PyObject* scheduleValidatedPodEntry(PyObject* self, PyObject* const* args, Py_ssize_t nargs,
+                                    PyObject* kwnames) {
+  return schedulePodCall(self, args, nargs, kwnames, true);
+}
+
+using FastCallWithKeywords = PyObject* (*)(PyObject*, PyObject* const*, Py_ssize_t, PyObject*);
+PyCFunction asCFunction(FastCallWithKeywords f) {
+  return reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(f));
+}
+
+PyMethodDef directMethods[] = {
+    {"schedule_pod", asCFunction(schedulePodEntry), METH_FASTCALL | METH_KEYWORDS,
+     "schedule_pod($self, /, pod_spec, pod_key, suggested_nodes=None, phase='Filtering', "
+     "commit=False, validate=True)\n--\n\n"
+     "One filter decision in one call: validate and default the request, decide,\n"
+     "commit a bind decision, return the native ScheduleResult. Raises CoreError."},
+    {"schedule_validated_pod", asCFunction(scheduleValidatedPodEntry),
+     METH_FASTCALL | METH_KEYWORDS,
+     "schedule_validated_pod($self, /, spec, pod_key, suggested_nodes=None, "
+     "phase='Filtering', commit=False)\n--\n\n"
+     "schedule_pod with validate=True whose core errors leave as\n"
+     "WebServerError(code, text) with the CoreError as __cause__."},
+};
+
+void addDirectMethods(py::handle cls) {
+  gCoreType = reinterpret_cast<PyTypeObject*>(cls.ptr());
+  for (PyMethodDef& def : directMethods) {
+    PyObject* descr = PyDescr_NewMethod(gCoreType, &def);
+    if (descr == nullptr) throw py::error_already_set();
+    int rc = PyObject_SetAttrString(cls.ptr(), def.ml_name, descr);
+    Py_DECREF(descr);
+    if (rc != 0) throw py::error_already_set();
+  }
+}
 
 }  // namespace
 
@@ -1117,6 +1400,7 @@ PYBIND11_MODULE(hivedcore, m) {
   initResultType(m);
 
   static py::exception<HivedError> exc(m, "CoreError");
+  gCoreError = exc.ptr();
   py::register_exception_translator([](std::exception_ptr p) {
     try {
       if (p) std::rethrow_exception(p);
@@ -1128,7 +1412,8 @@ PYBIND11_MODULE(hivedcore, m) {
     }
   });
 
-  py::class_<PyHivedCore>(m, "HivedCore")
+  py::class_<PyHivedCore> coreClass(m, "HivedCore");
+  coreClass
       .def(py::init<const py::dict&>(), py::arg("spec"))
       .def("set_node_healthy", &PyHivedCore::setNodeHealthy, py::arg("node"), py::arg("healthy"))
       .def("set_xgmi_link_healthy", &PyHivedCore::setXgmiLinkHealthy, py::arg("node"),
@@ -1140,9 +1425,6 @@ PYBIND11_MODULE(hivedcore, m) {
       .def("bad_nodes", &PyHivedCore::badNodes)
       .def("schedule", &PyHivedCore::schedule, py::arg("pod_spec"), py::arg("pod_key"),
            py::arg("suggested_nodes"), py::arg("phase"))
-      .def("schedule_pod", &PyHivedCore::schedulePod, py::arg("pod_spec"), py::arg("pod_key"),
-           py::arg("suggested_nodes") = py::none(), py::arg("phase") = "Filtering",
-           py::arg("commit") = false, py::arg("validate") = true)
       .def("delete_unallocated_pod", &PyHivedCore::deleteUnallocatedPod, py::arg("pod_spec"),
            py::arg("pod_key"))
       .def("add_allocated_pod", &PyHivedCore::addAllocatedPod, py::arg("pod_spec"),
@@ -1158,4 +1440,6 @@ PYBIND11_MODULE(hivedcore, m) {
       .def("schedule_count", &PyHivedCore::scheduleCount)
       .def("check_invariants", &PyHivedCore::checkInvariants)
       .def("debug_counters", &PyHivedCore::debugCounters);
+  // schedule_pod and schedule_validated_pod: hand-written vectorcall methods
+  addDirectMethods(coreClass);
 }

@@ -291,12 +291,30 @@ struct CleanShapeWorld {
   std::map<int, std::vector<PhysicalCell*>> physByLevel;
 };
 
+class TopoScheduler;
+struct IntraVCScheduler;
+
+// One request on its way through the core. The strings and the pod-number map
+// are the PodSpec's own (the request lives inside one HivedCore::schedule call,
+// the spec outlives it), so building a request copies nothing.
 struct SchedulingRequest {
-  std::string vc;
-  std::string pinnedCellId;
-  std::string chain;
-  std::string groupName;
-  std::map<int, int> podLeafCellNums;
+  explicit SchedulingRequest(const PodSpec& s)
+      : vc(s.vc),
+        pinnedCellId(s.pinnedCellId),
+        groupName(s.groupName),
+        podLeafCellNums(s.groupPodNums),
+        priority(s.priority) {}
+  const std::string& vc;
+  const std::string& pinnedCellId;
+  const std::string& groupName;
+  const std::map<int, int>& podLeafCellNums;
+  // the chain being tried (a key of cellChains_' lists or a cell's own chain)
+  const std::string* chain = nullptr;
+  // the VC's scheduler, resolved once per request, and the placement engine
+  // of the chain (or pinned cell) being tried, resolved once per chain: the
+  // attempts themselves look nothing up by name
+  IntraVCScheduler* vcScheduler = nullptr;
+  const TopoScheduler* topo = nullptr;
   int priority = 0;
   const std::set<std::string>* suggestedNodes = nullptr;
   bool ignoreSuggestedNodes = true;
@@ -354,6 +372,14 @@ class TopoScheduler {
   std::vector<Cell*> viewCells_;
   std::map<int, int> levelLeafNum_;
   bool crossPriorityPack_ = false;
+  // Reused by every Schedule call so that a failing decision allocates
+  // nothing here (see the note on re-entrance in Schedule).
+  struct Scratch {
+    std::vector<NodeView> view;
+    std::vector<int> sortedLeafNums;
+    std::vector<int> pickedNodeIndices;
+  };
+  mutable Scratch scratch_;
 };
 
 // ---------------------------------------------------------------------------
@@ -466,7 +492,7 @@ class HivedCore {
   ScheduleResult generateResult(const Placement<PhysicalCell>& phys, bool hasVirtual,
                                 const Placement<VirtualCell>& virt,
                                 const std::map<std::string, std::set<std::string>>& victims,
-                                const std::string& waitReason, int currentLeafNum, int podIndex,
+                                std::string&& waitReason, int currentLeafNum, int podIndex,
                                 Group* group, const std::string& groupName);
   bool schedulePodFromExistingGroup(Group* g, const PodSpec& s,
                                     const std::set<std::string>& suggestedNodes, Phase phase,
@@ -485,6 +511,7 @@ class HivedCore {
                                 bool* hasVirtual, Placement<VirtualCell>* virt,
                                 std::string* failedReason);
   bool scheduleForLeafCellType(SchedulingRequest& sr, const std::string& leafCellType,
+                               const std::vector<std::string>& chains,
                                const std::string& podKey, bool typeSpecified,
                                Placement<PhysicalCell>* phys, bool* hasVirtual,
                                Placement<VirtualCell>* virt, std::string* failedReason);
@@ -493,10 +520,10 @@ class HivedCore {
                                std::string* failedReason);
   bool scheduleGuaranteedGroup(SchedulingRequest& sr, Placement<PhysicalCell>* phys,
                                Placement<VirtualCell>* virt, std::string* failedReason);
-  bool chainHasBadLinks(const std::string& chain);
+  static bool chainHasBadLinks(const ChainCellList& fullCells);
   bool scheduleOpportunisticGroup(const SchedulingRequest& sr, Placement<PhysicalCell>* phys,
                                   std::string* failedReason);
-  void validateSchedulingRequest(const SchedulingRequest& sr, const std::string& podKey);
+  void validateSchedulingRequest(SchedulingRequest& sr, const std::string& podKey);
 
   std::map<std::string, Placement<VirtualCell>> tryLazyPreempt(const Placement<VirtualCell>& p,
                                                                const std::string& groupName);

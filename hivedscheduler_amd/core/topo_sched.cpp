@@ -751,11 +751,17 @@ bool TopoScheduler::tryScheduleAtPriority(const std::vector<int>& sortedLeafNums
                                           std::string* failedReason) const {
   // Build and sort the cluster view: healthy > suggested > same-priority used
   // (desc, packing) > higher-priority used (asc, stay away).
-  std::vector<NodeView> cv;
+  std::vector<NodeView>& cv = scratch_.view;
+  cv.clear();
   cv.reserve(viewCells_.size());
   PickSession probe;  // empty: availability before any placement
   probe.minHbm = minHbmBytes;
   if (honorLinks) probe.world = cleanWorld;
+  int totalLeafNum = 0;
+  for (int q : sortedLeafNums) totalLeafNum += q;
+  long long freeSum = 0;
+  int freeMax = 0;
+  bool allSuggested = true;
   for (Cell* c : viewCells_) {
     NodeView n;
     n.c = c;
@@ -782,14 +788,39 @@ bool TopoScheduler::tryScheduleAtPriority(const std::vector<int>& sortedLeafNums
     auto [healthy, suggested] = healthyAndSuggested(c, suggestedNodes, ignoreSuggestedNodes);
     n.healthy = healthy;
     n.suggested = suggested;
+    freeSum += n.freeAtPriority;
+    freeMax = std::max(freeMax, n.freeAtPriority);
+    allSuggested = allSuggested && suggested;
     cv.push_back(n);
   }
-  std::stable_sort(cv.begin(), cv.end(), [](const NodeView& a, const NodeView& b) {
+  // Failure decided before the sort, where the node order can change neither
+  // the verdict nor the reason. With every node suggested (or suggestions
+  // ignored) the only reason the loops below can give is "insufficient
+  // capacity", and they must give it when no node can host a single-pod gang
+  // or when the gang asks for more than all nodes together offer. With a
+  // non-suggested node in the view the reason may name the first such node
+  // with room, which depends on the order: no early exit then.
+  if (allSuggested && (totalLeafNum > freeSum ||
+                       (sortedLeafNums.size() == 1 && sortedLeafNums[0] > freeMax))) {
+    *failedReason = "insufficient capacity";
+    return false;
+  }
+  // Stable insertion sort (equal keys keep their view order, as with
+  // std::stable_sort, which would heap-allocate its merge buffer): the view
+  // holds a handful of nodes.
+  auto before = [](const NodeView& a, const NodeView& b) {
     if (a.healthy != b.healthy) return a.healthy;
     if (a.suggested != b.suggested) return a.suggested;
     if (a.usedSamePriority != b.usedSamePriority) return a.usedSamePriority > b.usedSamePriority;
     return a.usedHigherPriority < b.usedHigherPriority;
-  });
+  };
+  for (size_t i = 1; i < cv.size(); i++) {
+    if (!before(cv[i], cv[i - 1])) continue;
+    NodeView moving = cv[i];
+    size_t j = i;
+    for (; j > 0 && before(moving, cv[j - 1]); j--) cv[j] = cv[j - 1];
+    cv[j] = moving;
+  }
 
   // Single-node preference: when ONE node can host the whole gang, use it
   // (most-packed first via the sort above). The reference's greedy fit
@@ -798,11 +829,10 @@ bool TopoScheduler::tryScheduleAtPriority(const std::vector<int>& sortedLeafNums
   // split gang communicates over the NETWORK while a same-node gang rides
   // 7x ~153 GB/s xGMI links, so locality outranks strict packing here.
   // (Property-tested: tests/test_placement_optimality.py.)
-  std::vector<int> pickedNodeIndices(sortedLeafNums.size(), -1);
+  std::vector<int>& pickedNodeIndices = scratch_.pickedNodeIndices;
+  pickedNodeIndices.assign(sortedLeafNums.size(), -1);
   size_t podIndex = 0;
   int pickedLeafCellNum = 0;
-  int totalLeafNum = 0;
-  for (int q : sortedLeafNums) totalLeafNum += q;
   for (size_t nodeIndex = 0; nodeIndex < cv.size(); nodeIndex++) {
     const NodeView& n = cv[nodeIndex];
     if (n.freeAtPriority >= totalLeafNum) {
@@ -895,7 +925,15 @@ bool TopoScheduler::Schedule(const std::map<int, int>& podLeafCellNums, int prio
                              bool ignoreSuggestedNodes, Placement<Cell>* out,
                              std::string* failedReason, long long minHbmBytes,
                              const CleanShapeWorld* cleanWorld, bool honorOnly) const {
-  std::vector<int> sortedLeafNums;
+  // The scratch is this scheduler's own and Schedule never re-enters itself:
+  // tryScheduleAtPriority and the pick* / avail* helpers it calls call no
+  // scheduler, every caller (IntraVCScheduler::schedule, the opportunistic
+  // path, the clean-shape-world loop of scheduleGuaranteedGroup) runs its
+  // Schedule calls one after the other, and the core is single-threaded per
+  // operation. Each attempt rebuilds the view and the picked indices from
+  // scratch, so nothing carries over from one call to the next.
+  std::vector<int>& sortedLeafNums = scratch_.sortedLeafNums;
+  sortedLeafNums.clear();
   for (auto& [leafNum, podNum] : podLeafCellNums) {
     for (int i = 0; i < podNum; i++) sortedLeafNums.push_back(leafNum);
   }
@@ -936,14 +974,8 @@ bool TopoScheduler::Schedule(const std::map<int, int>& podLeafCellNums, int prio
 
 bool IntraVCScheduler::schedule(const SchedulingRequest& sr, Placement<VirtualCell>* out,
                                 std::string* failedReason) const {
-  const TopoScheduler* scheduler = nullptr;
-  if (!sr.pinnedCellId.empty()) {
-    auto it = pinnedSchedulers.find(sr.pinnedCellId);
-    if (it != pinnedSchedulers.end()) scheduler = &it->second;
-  } else {
-    auto it = nonPinnedSchedulers.find(sr.chain);
-    if (it != nonPinnedSchedulers.end()) scheduler = &it->second;
-  }
+  // resolved once per chain by the caller (pinned: per request)
+  const TopoScheduler* scheduler = sr.topo;
   Placement<Cell> generic;
   if (scheduler == nullptr ||
       !scheduler->Schedule(sr.podLeafCellNums, sr.priority, *sr.suggestedNodes,
