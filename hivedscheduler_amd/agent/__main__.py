@@ -21,6 +21,13 @@ def main() -> None:
                     help="full 28-pair p2p link-matrix sweep every N deep sweeps")
     ap.add_argument("--p2p-matrix", action="store_true",
                     help="with --local: also measure the full p2p link matrix")
+    ap.add_argument("--burn-every", type=int, default=0,
+                    help="sustained MFMA burn-in every N sweeps (on deep sweeps); 0 = never")
+    ap.add_argument("--min-mfma-tflops", type=float, default=None,
+                    help="mark a GPU bad when its burn-in bf16 TFLOP/s is below this "
+                         "(no default: measure your fleet, see docs/user-manual.md)")
+    ap.add_argument("--burn", action="store_true",
+                    help="with --local: also run the MFMA burn-in")
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
@@ -31,7 +38,8 @@ def main() -> None:
         import json
 
         report = collect_node_health(deep=True, sweep=True,
-                                     probe_pairs=args.probe_pairs)
+                                     probe_pairs=args.probe_pairs, burn=args.burn,
+                                     min_mfma_tflops=args.min_mfma_tflops)
         if args.p2p_matrix:
             try:
                 m = p2p_link_matrix()
@@ -47,7 +55,9 @@ def main() -> None:
     agent = NodeHealthAgent(args.scheduler, node_name=args.node_name,
                             interval_s=args.interval, deep_every=args.deep_every,
                             probe_pairs=args.probe_pairs,
-                            p2p_matrix_every=args.p2p_matrix_every)
+                            p2p_matrix_every=args.p2p_matrix_every,
+                            burn_every=args.burn_every,
+                            min_mfma_tflops=args.min_mfma_tflops)
     if args.once:
         import json
 

@@ -48,11 +48,19 @@ def collect_node_health(
     min_pair_busbw_gbps: float = 50.0,
     probe_pairs: bool = False,
     sweep: bool = False,
+    burn: bool = False,
+    min_mfma_tflops: Optional[float] = None,
 ) -> dict:
     """One health sweep over all visible GPUs. deep=True also runs the HIP
     kernels (HBM + MFMA); sweep=True adds the 16 GiB HBM stuck-bit pattern
     sweep (any error => leaf bad); probe_pairs=True RCCL-probes each xGMI
     pair.
+
+    burn=True (with deep) adds the sustained MFMA burn-in: per GPU it records
+    `mfma_tflops` ({fmt: TFLOP/s}), `mfma_burn_ok` and `bad_cus` (the CUs of
+    any wave whose result was wrong), and a failed burn marks the leaf bad.
+    min_mfma_tflops is a floor on the bf16 figure; there is no default
+    because the right value is site-measured (docs/user-manual.md).
 
     The stuck-bit scan transiently holds up to 16 GiB of HBM; on a GPU
     running tenant jobs this can make the tenant's own allocations fail.
@@ -78,7 +86,8 @@ def collect_node_health(
             try:
                 # best-of-3 bandwidth: a tenant job on the GPU can halve a
                 # single triad sample (see profiles/interference_r01.md)
-                rep = gpu_health_report(i, quick=True, deep=sweep, bw_samples=3)
+                kwargs = {"burn": True} if burn else {}
+                rep = gpu_health_report(i, quick=True, deep=sweep, bw_samples=3, **kwargs)
                 report["gpus"][str(i)].update(
                     hbm_gbps=round(rep["hbm_gbps"], 1),
                     mfma_ok=rep["mfma_ok"],
@@ -89,6 +98,18 @@ def collect_node_health(
                     report["gpus"][str(i)]["hbm_sweep_errors"] = rep["hbm_sweep"]["errors"]
                 if not rep["healthy"] or rep["hbm_gbps"] < min_hbm_gbps:
                     report["gpus"][str(i)]["healthy"] = False
+                if burn:
+                    b = rep["mfma_burn"]
+                    tflops = {f: round(s["tflops"], 1) for f, s in b["formats"].items()}
+                    report["gpus"][str(i)].update(
+                        mfma_tflops=tflops,
+                        mfma_burn_ok=bool(b["ok"]),
+                        bad_cus=b["bad_cus"],
+                    )
+                    bf16 = b["formats"].get("bf16", {}).get("tflops", 0.0)
+                    slow = min_mfma_tflops is not None and bf16 < min_mfma_tflops
+                    if not b["ok"] or b["bad_cus"] or slow:
+                        report["gpus"][str(i)]["healthy"] = False
             except Exception as e:
                 report["gpus"][str(i)].update(healthy=False, error=str(e)[:200])
     if probe_pairs and n >= 2:
@@ -160,7 +181,8 @@ class NodeHealthAgent:
     def __init__(self, scheduler_url: str, node_name: Optional[str] = None,
                  interval_s: float = 60.0, deep_every: int = 10,
                  sweep_every: int = 60, probe_pairs: bool = True,
-                 p2p_matrix_every: int = 30):
+                 p2p_matrix_every: int = 30, burn_every: int = 0,
+                 min_mfma_tflops: Optional[float] = None):
         self.scheduler_url = scheduler_url.rstrip("/")
         self.node_name = node_name or socket.gethostname()
         self.interval_s = interval_s
@@ -172,6 +194,11 @@ class NodeHealthAgent:
         # full p2p matrix cadence (28 pairs x 2 directions, ~1 min on 8 GPUs):
         # localizes a degraded link to one pair when collective probes read low
         self.p2p_matrix_every = p2p_matrix_every
+        # sustained MFMA burn-in cadence, same pattern as sweep_every; 0 = never
+        # (four formats x tens of ms per GPU, and it saturates the matrix
+        # cores of a GPU a tenant may be using)
+        self.burn_every = burn_every
+        self.min_mfma_tflops = min_mfma_tflops
         self._rounds = 0
 
     def post_report(self, report: dict) -> bool:
@@ -219,9 +246,13 @@ class NodeHealthAgent:
         deep = (self._rounds % self.deep_every) == 0
         sweep = (self._rounds % self.sweep_every) == 0
         matrix = (self._rounds % self.p2p_matrix_every) == 0
+        burn = self.burn_every > 0 and (self._rounds % self.burn_every) == 0
         self._rounds += 1
+        kwargs = {}
+        if burn and deep:
+            kwargs = {"burn": True, "min_mfma_tflops": self.min_mfma_tflops}
         report = collect_node_health(deep=deep, probe_pairs=self.probe_pairs and deep,
-                                     sweep=sweep and deep)
+                                     sweep=sweep and deep, **kwargs)
         report["node"] = self.node_name
         if matrix and deep:
             try:

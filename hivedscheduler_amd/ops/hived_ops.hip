@@ -7,6 +7,8 @@
 //                stack shows up as a large deficit)
 //  - mfma_check: bf16 MFMA tile GEMM on every CU, output verified bitwise by
 //                the host against a reference — catches broken matrix cores
+//  - mfma_burn:  sustained, timed MFMA issue per datapath, verified bitwise in
+//                the kernel; TFLOP/s plus the CU of any wave that was wrong
 //  - p2p copy:   xGMI link bandwidth between two GPUs (expected ~153 GB/s per
 //                link per direction); a degraded link marks the PAIR cell bad
 //
@@ -16,6 +18,8 @@
 #include <ATen/cuda/CUDAContext.h>
 #include <hip/hip_runtime.h>
 
+#include <string>
+#include <tuple>
 #include <vector>
 
 #define HIP_CHECK(cmd)                                                                     \
@@ -342,6 +346,278 @@ torch::Tensor cu_coverage(long blocks) {
 }
 
 // ---------------------------------------------------------------------------
+// MFMA burn-in: a bounded, timed, exactly verifiable run of sustained MFMA
+// issue on every CU. The single-tile checks above issue one instruction per
+// wave; a matrix pipe that corrupts data only under sustained issue, or a
+// GPU that cannot hold its clock, passes them. Here each wave keeps NACC=4
+// independent accumulators (A tile i of A[4*16,K] against a shared B[K,16]),
+// loads every operand and the expected result into registers once, and then
+// for each round zeroes the accumulators, issues `chain` dependent MFMAs per
+// accumulator, and compares all four bitwise against `expected`. The hot
+// loop has no memory traffic.
+//
+// Exactness by construction: operands are integers in {-2..2} (exact in
+// bf16, e4m3 and e2m1), so every partial sum is an integer of magnitude
+// <= 4*K*chain, exact in fp32 while 4*K*chain <= 2^24, and the expected tile
+// is chain * (A_i @ B) whatever order the hardware accumulates in.
+//
+// Lane 0 of each wave writes one int4 record:
+//   { (XCC_ID<<16)|HW_ID   (the cu_coverage_kernel encoding),
+//     mismatched elements over all rounds,
+//     first bad round (-1 if none),
+//     xor of all accumulator bits over all lanes and rounds }
+// so the host can join a wrong result to the CU that produced it.
+//
+// inject_wave/inject_round (default -1 = off): in that wave, at that round,
+// lane 0 flips the lowest mantissa bit of acc[0][0] before the compare.
+// Register arithmetic only; it exists to test detection and attribution on
+// healthy hardware.
+//
+// Fragment layouts are those of the checks above (bf16/fp8: 8 K-elements
+// per lane; MX: 32 K-elements per lane, fp4 codes one per byte in memory and
+// packed low nibble first in registers).
+// ---------------------------------------------------------------------------
+enum { BURN_BF16 = 0, BURN_FP8 = 1, BURN_MX8 = 2, BURN_MX4 = 3 };
+constexpr int BURN_NACC = 4;
+
+template <int FMT> struct BurnMma;
+
+template <> struct BurnMma<BURN_BF16> {
+  static constexpr int K = 32;
+  typedef frag8 frag;
+  static __device__ __forceinline__ frag load_a(const void* A, int row, int lane) {
+    const short* p = static_cast<const short*>(A);
+    int kbase = (lane >> 4) * 8;
+    frag f;
+    for (int j = 0; j < 8; j++) f[j] = p[row * 32 + kbase + j];
+    return f;
+  }
+  static __device__ __forceinline__ frag load_b(const void* B, int lane) {
+    const short* p = static_cast<const short*>(B);
+    int kbase = (lane >> 4) * 8, n = lane & 15;
+    frag f;
+    for (int j = 0; j < 8; j++) f[j] = p[(kbase + j) * 16 + n];
+    return f;
+  }
+  static __device__ __forceinline__ f32x4 mma(frag a, frag b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+  }
+};
+
+template <> struct BurnMma<BURN_FP8> {
+  static constexpr int K = 32;
+  typedef long frag;
+  static __device__ __forceinline__ frag load_a(const void* A, int row, int lane) {
+    const unsigned char* p = static_cast<const unsigned char*>(A);
+    int kbase = (lane >> 4) * 8;
+    long f = 0;
+    for (int j = 0; j < 8; j++) f |= (long)p[row * 32 + kbase + j] << (8 * j);
+    return f;
+  }
+  static __device__ __forceinline__ frag load_b(const void* B, int lane) {
+    const unsigned char* p = static_cast<const unsigned char*>(B);
+    int kbase = (lane >> 4) * 8, n = lane & 15;
+    long f = 0;
+    for (int j = 0; j < 8; j++) f |= (long)p[(kbase + j) * 16 + n] << (8 * j);
+    return f;
+  }
+  static __device__ __forceinline__ f32x4 mma(frag a, frag b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a, b, c, 0, 0, 0);
+  }
+};
+
+template <int MXFMT> struct BurnMmaMx {  // MXFMT: 0 = fp8 e4m3, 4 = fp4 e2m1
+  static constexpr int K = 128;
+  typedef i32x8 frag;
+  // element k of this lane's fragment is p[base + k*kstride]: A walks k along
+  // a row (kstride 1), B walks k down a column (kstride 16)
+  static __device__ __forceinline__ frag load(const unsigned char* p, int lane, int base,
+                                              int kstride) {
+    int kbase = (lane >> 4) * 32;
+    union { i32x8 v; unsigned char b[32]; } f;
+    f.v = (i32x8){0, 0, 0, 0, 0, 0, 0, 0};
+    if constexpr (MXFMT == 0) {
+      for (int j = 0; j < 32; j++) f.b[j] = p[base + (kbase + j) * kstride];
+    } else {
+      for (int j = 0; j < 32; j += 2) {
+        unsigned lo = p[base + (kbase + j) * kstride] & 0xF;
+        unsigned hi = p[base + (kbase + j + 1) * kstride] & 0xF;
+        f.b[j / 2] = lo | (hi << 4);
+      }
+    }
+    return f.v;
+  }
+  static __device__ __forceinline__ frag load_a(const void* A, int row, int lane) {
+    return load(static_cast<const unsigned char*>(A), lane, row * 128, 1);
+  }
+  static __device__ __forceinline__ frag load_b(const void* B, int lane) {
+    return load(static_cast<const unsigned char*>(B), lane, lane & 15, 16);
+  }
+  static __device__ __forceinline__ f32x4 mma(frag a, frag b, f32x4 c) {
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, MXFMT, MXFMT, 0, 0x7F7F7F7F,
+                                                            0, 0x7F7F7F7F);
+  }
+};
+template <> struct BurnMma<BURN_MX8> : BurnMmaMx<0> {};
+template <> struct BurnMma<BURN_MX4> : BurnMmaMx<4> {};
+
+template <int FMT>
+__global__ void __launch_bounds__(256)
+mfma_burn_kernel(const void* __restrict__ A, const void* __restrict__ B,
+                 const float* __restrict__ expected, int4* __restrict__ records, int chain,
+                 int rounds, int inject_wave, int inject_round) {
+  typedef BurnMma<FMT> M;
+  int lane = threadIdx.x & 63;
+  int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  int m = lane & 15;
+  unsigned hwid, xcc;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+
+  typename M::frag a[BURN_NACC];
+  for (int i = 0; i < BURN_NACC; i++) a[i] = M::load_a(A, i * 16 + m, lane);
+  typename M::frag b = M::load_b(B, lane);
+  unsigned want[BURN_NACC][4];
+  for (int i = 0; i < BURN_NACC; i++)
+    for (int r = 0; r < 4; r++)
+      want[i][r] = __float_as_uint(expected[i * 256 + ((lane >> 4) * 4 + r) * 16 + m]);
+
+  bool inject_here = (wave == inject_wave) && (lane == 0);
+  int mismatched = 0, first_bad = -1;
+  unsigned checksum = 0;
+  for (int round = 0; round < rounds; round++) {
+    f32x4 acc[BURN_NACC];
+#pragma unroll
+    for (int i = 0; i < BURN_NACC; i++) {
+      acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      // opaque to the optimiser: every round really recomputes its chain
+      asm volatile("" : "+v"(acc[i]));
+    }
+    for (int c = 0; c < chain; c++) {
+#pragma unroll
+      for (int i = 0; i < BURN_NACC; i++) acc[i] = M::mma(a[i], b, acc[i]);
+    }
+    if (inject_here && round == inject_round)
+      acc[0][0] = __uint_as_float(__float_as_uint(acc[0][0]) ^ 1u);
+    int bad = 0;
+#pragma unroll
+    for (int i = 0; i < BURN_NACC; i++) {
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        unsigned bits = __float_as_uint(acc[i][r]);
+        bad += (bits != want[i][r]);
+        checksum ^= bits;
+      }
+    }
+    for (int off = 32; off > 0; off >>= 1) bad += __shfl_xor(bad, off);
+    mismatched += bad;
+    if (bad && first_bad < 0) first_bad = round;
+  }
+  for (int off = 32; off > 0; off >>= 1) checksum ^= (unsigned)__shfl_xor((int)checksum, off);
+  if (lane == 0)
+    records[wave] = make_int4((int)((xcc << 16) | (hwid & 0xffff)), mismatched, first_bad,
+                              (int)checksum);
+}
+
+template <int FMT>
+static void launch_mfma_burn(long blocks, hipStream_t stream, const void* A, const void* B,
+                             const float* expected, int4* records, long chain, long rounds,
+                             long inject_wave, long inject_round) {
+  hipLaunchKernelGGL((mfma_burn_kernel<FMT>), dim3(blocks), dim3(256), 0, stream, A, B, expected,
+                     records, (int)chain, (int)rounds, (int)inject_wave, (int)inject_round);
+}
+
+// A: [64,K], B: [K,16], expected: [4,16,16] fp32 (= chain * A_i @ B).
+// fmt "bf16": bf16 tensors, K=32. "fp8": uint8 raw e4m3 bytes, K=32.
+// "mx8": uint8 raw e4m3 bytes, K=128. "mx4": uint8 e2m1 codes one per byte,
+// K=128. One untimed warm-up launch, then one launch timed with HIP events.
+// Returns (records [waves,4] int32, elapsed_ms of the timed launch).
+std::tuple<torch::Tensor, double> mfma_burn(torch::Tensor A, torch::Tensor B,
+                                            torch::Tensor expected, const std::string& fmt,
+                                            long blocks, long chain, long rounds,
+                                            long inject_wave, long inject_round) {
+  int f = fmt == "bf16" ? BURN_BF16 : fmt == "fp8" ? BURN_FP8 : fmt == "mx8" ? BURN_MX8
+          : fmt == "mx4" ? BURN_MX4 : -1;
+  TORCH_CHECK(f >= 0, "fmt must be one of bf16, fp8, mx8, mx4; got ", fmt);
+  const long K = (f == BURN_BF16 || f == BURN_FP8) ? 32 : 128;
+  TORCH_CHECK(A.is_cuda() && B.is_cuda() && expected.is_cuda(), "A/B/expected must be on GPU");
+  TORCH_CHECK(A.device() == B.device() && A.device() == expected.device(),
+              "A/B/expected must be on the same device");
+  if (f == BURN_BF16) {
+    TORCH_CHECK(A.dtype() == torch::kBFloat16 && B.dtype() == torch::kBFloat16,
+                "bf16 burn: A/B must be bfloat16");
+  } else {
+    TORCH_CHECK(A.dtype() == torch::kUInt8 && B.dtype() == torch::kUInt8,
+                "fp8/mx8/mx4 burn: A/B must be uint8 (raw e4m3 bytes or e2m1 codes)");
+  }
+  TORCH_CHECK(expected.dtype() == torch::kFloat32, "expected must be float32");
+  TORCH_CHECK(A.sizes() == torch::IntArrayRef({BURN_NACC * 16, K}) &&
+                  B.sizes() == torch::IntArrayRef({K, 16}) &&
+                  expected.sizes() == torch::IntArrayRef({BURN_NACC, 16, 16}),
+              "shapes must be A [64,K], B [K,16], expected [4,16,16] with K=", K);
+  TORCH_CHECK(blocks >= 1 && blocks <= (1L << 20), "blocks must be in [1, 2^20]");
+  TORCH_CHECK(chain >= 1 && rounds >= 1, "chain and rounds must be >= 1");
+  // |operand| <= 2, so every partial sum is an integer <= 4*K*chain: exact
+  // in fp32 only up to 2^24
+  TORCH_CHECK(4 * K * chain <= (1L << 24), "chain ", chain, " breaks fp32 exactness for K=", K,
+              " (need 4*K*chain <= 2^24)");
+  // bounded run: at most 2^22 MFMAs per accumulator per wave (~2 s at the
+  // default grid on the slowest format)
+  TORCH_CHECK(rounds <= (1L << 22) && chain * rounds <= (1L << 22),
+              "chain*rounds must be <= 2^22");
+  TORCH_CHECK(inject_wave >= -1 && inject_wave < blocks * 4 && inject_round >= -1 &&
+                  inject_round < rounds,
+              "inject_wave/inject_round out of range");
+  A = A.contiguous();
+  B = B.contiguous();
+  expected = expected.contiguous();
+  long waves = blocks * 4;
+  auto records = torch::zeros({waves, 4},
+                              torch::TensorOptions().dtype(torch::kInt32).device(A.device()));
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  auto launch = [&]() {
+    const void* a = A.data_ptr();
+    const void* b = B.data_ptr();
+    const float* e = expected.data_ptr<float>();
+    int4* rec = reinterpret_cast<int4*>(records.data_ptr<int>());
+    switch (f) {
+      case BURN_BF16:
+        launch_mfma_burn<BURN_BF16>(blocks, stream, a, b, e, rec, chain, rounds, inject_wave,
+                                    inject_round);
+        break;
+      case BURN_FP8:
+        launch_mfma_burn<BURN_FP8>(blocks, stream, a, b, e, rec, chain, rounds, inject_wave,
+                                   inject_round);
+        break;
+      case BURN_MX8:
+        launch_mfma_burn<BURN_MX8>(blocks, stream, a, b, e, rec, chain, rounds, inject_wave,
+                                   inject_round);
+        break;
+      default:
+        launch_mfma_burn<BURN_MX4>(blocks, stream, a, b, e, rec, chain, rounds, inject_wave,
+                                   inject_round);
+    }
+  };
+  launch();  // warm-up: code-object load and clock ramp stay out of the timing
+  HIP_CHECK(hipGetLastError());
+  hipEvent_t start, stop;
+  HIP_CHECK(hipEventCreate(&start));
+  HIP_CHECK(hipEventCreate(&stop));
+  HIP_CHECK(hipEventRecord(start, stream));
+  launch();
+  HIP_CHECK(hipEventRecord(stop, stream));
+  HIP_CHECK(hipGetLastError());
+  // the torch stream is non-blocking (see lds_check): wait on the stop event
+  // before anything reads the records or the timing
+  HIP_CHECK(hipEventSynchronize(stop));
+  float ms = 0;
+  HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
+  HIP_CHECK(hipEventDestroy(start));
+  HIP_CHECK(hipEventDestroy(stop));
+  return std::make_tuple(records, (double)ms);
+}
+
+// ---------------------------------------------------------------------------
 // xGMI p2p bandwidth between two devices (one direction).
 // ---------------------------------------------------------------------------
 double p2p_gbps(int src_dev, int dst_dev, long size_mb, long iters) {
@@ -519,6 +795,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma_check_mx", &mfma_check_mx, py::arg("A"), py::arg("B"), py::arg("blocks") = 2048,
         py::arg("fmt") = 0,
         "Per-wave MX block-scaled MFMA (16x16x128 f8f6f4) tile; fmt 0=fp8, 4=fp4");
+  m.def("mfma_burn", &mfma_burn, py::arg("A"), py::arg("B"), py::arg("expected"), py::arg("fmt"),
+        py::arg("blocks") = 2048, py::arg("chain") = 1024, py::arg("rounds") = 64,
+        py::arg("inject_wave") = -1, py::arg("inject_round") = -1,
+        "Sustained MFMA burn-in (fmt bf16|fp8|mx8|mx4): rounds x chain dependent MFMAs on 4 "
+        "accumulators per wave, verified bitwise; returns (per-wave records [waves,4], ms)");
   m.def("p2p_gbps", &p2p_gbps, py::arg("src_dev"), py::arg("dst_dev"), py::arg("size_mb") = 256,
         py::arg("iters") = 10, "xGMI peer-to-peer copy bandwidth in GB/s");
   m.def("hbm_sweep", &hbm_sweep, py::arg("max_gib") = 16, py::arg("chunk_gib") = 4,
