@@ -28,6 +28,11 @@ def main() -> None:
                          "(no default: measure your fleet, see docs/user-manual.md)")
     ap.add_argument("--burn", action="store_true",
                     help="with --local: also run the MFMA burn-in")
+    ap.add_argument("--lds-march-every", type=int, default=0,
+                    help="full-LDS march (160 KiB per CU, both polarities) every N sweeps "
+                         "(on deep sweeps); 0 = never")
+    ap.add_argument("--lds-march", action="store_true",
+                    help="with --local: also run the full-LDS march")
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
@@ -39,7 +44,8 @@ def main() -> None:
 
         report = collect_node_health(deep=True, sweep=True,
                                      probe_pairs=args.probe_pairs, burn=args.burn,
-                                     min_mfma_tflops=args.min_mfma_tflops)
+                                     min_mfma_tflops=args.min_mfma_tflops,
+                                     lds_march=args.lds_march)
         if args.p2p_matrix:
             try:
                 m = p2p_link_matrix()
@@ -57,7 +63,8 @@ def main() -> None:
                             probe_pairs=args.probe_pairs,
                             p2p_matrix_every=args.p2p_matrix_every,
                             burn_every=args.burn_every,
-                            min_mfma_tflops=args.min_mfma_tflops)
+                            min_mfma_tflops=args.min_mfma_tflops,
+                            lds_march_every=args.lds_march_every)
     if args.once:
         import json
 

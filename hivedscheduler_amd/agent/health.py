@@ -50,6 +50,7 @@ def collect_node_health(
     sweep: bool = False,
     burn: bool = False,
     min_mfma_tflops: Optional[float] = None,
+    lds_march: bool = False,
 ) -> dict:
     """One health sweep over all visible GPUs. deep=True also runs the HIP
     kernels (HBM + MFMA); sweep=True adds the 16 GiB HBM stuck-bit pattern
@@ -61,6 +62,12 @@ def collect_node_health(
     any wave whose result was wrong), and a failed burn marks the leaf bad.
     min_mfma_tflops is a floor on the bf16 figure; there is no default
     because the right value is site-measured (docs/user-manual.md).
+
+    lds_march=True (with deep) adds the full-LDS march: per GPU it records
+    `lds_march_ok`, `lds_gbps` (reported, not judged: there is no floor) and
+    `lds_bad_cus` (the CUs whose LDS read back wrong; a key of its own, so
+    `bad_cus` keeps meaning the burn-in's), and a failed march marks the leaf
+    bad.
 
     The stuck-bit scan transiently holds up to 16 GiB of HBM; on a GPU
     running tenant jobs this can make the tenant's own allocations fail.
@@ -87,6 +94,8 @@ def collect_node_health(
                 # best-of-3 bandwidth: a tenant job on the GPU can halve a
                 # single triad sample (see profiles/interference_r01.md)
                 kwargs = {"burn": True} if burn else {}
+                if lds_march:
+                    kwargs["lds_march"] = True
                 rep = gpu_health_report(i, quick=True, deep=sweep, bw_samples=3, **kwargs)
                 report["gpus"][str(i)].update(
                     hbm_gbps=round(rep["hbm_gbps"], 1),
@@ -109,6 +118,16 @@ def collect_node_health(
                     bf16 = b["formats"].get("bf16", {}).get("tflops", 0.0)
                     slow = min_mfma_tflops is not None and bf16 < min_mfma_tflops
                     if not b["ok"] or b["bad_cus"] or slow:
+                        report["gpus"][str(i)]["healthy"] = False
+                if lds_march:
+                    m = rep["lds_march"]
+                    report["gpus"][str(i)].update(
+                        lds_march_ok=bool(m["ok"]),
+                        lds_gbps=round(m["gbps"], 1),
+                        lds_bad_cus=[{k: c[k] for k in ("xcc", "se", "sh", "cu")}
+                                     for c in m["bad_cus"]],
+                    )
+                    if not m["ok"] or m["bad_cus"]:
                         report["gpus"][str(i)]["healthy"] = False
             except Exception as e:
                 report["gpus"][str(i)].update(healthy=False, error=str(e)[:200])
@@ -182,7 +201,7 @@ class NodeHealthAgent:
                  interval_s: float = 60.0, deep_every: int = 10,
                  sweep_every: int = 60, probe_pairs: bool = True,
                  p2p_matrix_every: int = 30, burn_every: int = 0,
-                 min_mfma_tflops: Optional[float] = None):
+                 min_mfma_tflops: Optional[float] = None, lds_march_every: int = 0):
         self.scheduler_url = scheduler_url.rstrip("/")
         self.node_name = node_name or socket.gethostname()
         self.interval_s = interval_s
@@ -199,6 +218,9 @@ class NodeHealthAgent:
         # cores of a GPU a tenant may be using)
         self.burn_every = burn_every
         self.min_mfma_tflops = min_mfma_tflops
+        # full-LDS march cadence, same pattern; 0 = never (about a millisecond
+        # per GPU, but it takes every CU's whole LDS while it runs)
+        self.lds_march_every = lds_march_every
         self._rounds = 0
 
     def post_report(self, report: dict) -> bool:
@@ -247,10 +269,13 @@ class NodeHealthAgent:
         sweep = (self._rounds % self.sweep_every) == 0
         matrix = (self._rounds % self.p2p_matrix_every) == 0
         burn = self.burn_every > 0 and (self._rounds % self.burn_every) == 0
+        march = self.lds_march_every > 0 and (self._rounds % self.lds_march_every) == 0
         self._rounds += 1
         kwargs = {}
         if burn and deep:
             kwargs = {"burn": True, "min_mfma_tflops": self.min_mfma_tflops}
+        if march and deep:
+            kwargs["lds_march"] = True
         report = collect_node_health(deep=deep, probe_pairs=self.probe_pairs and deep,
                                      sweep=sweep and deep, **kwargs)
         report["node"] = self.node_name

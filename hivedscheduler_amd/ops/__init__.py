@@ -22,7 +22,7 @@ def get_ops():
 
 
 def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
-                      bw_samples: int = 1, burn: bool = False) -> dict:
+                      bw_samples: int = 1, burn: bool = False, lds_march: bool = False) -> dict:
     """Run the health-probe kernels on one GPU and return measured facts.
 
     Feeds leaf-cell healthiness: HBM bandwidth deficit, MFMA mismatch, or
@@ -39,6 +39,11 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     burn=True adds the sustained MFMA burn-in (`mfma_burn_report`, tens of
     milliseconds per format) as report["mfma_burn"] and ANDs its verdict
     into `healthy`. Off by default: the report is then unchanged.
+
+    lds_march=True adds the full-LDS march (`lds_march_report`, about a
+    millisecond) as report["lds_march"] and ANDs its verdict into `healthy`.
+    Off by default, and the report is then unchanged; `lds_errors` stays the
+    64 KiB single-pass check either way.
     """
     import torch
 
@@ -97,6 +102,9 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     if burn:
         report["mfma_burn"] = mfma_burn_report(device)
         report["healthy"] = bool(report["healthy"] and report["mfma_burn"]["ok"])
+    if lds_march:
+        report["lds_march"] = lds_march_report(device)
+        report["healthy"] = bool(report["healthy"] and report["lds_march"]["ok"])
     return report
 
 
@@ -290,4 +298,141 @@ def mfma_burn_report(device: int = 0, fmts=BURN_FORMATS, blocks: int = 2048,
         bad.update((c["xcc"], c["se"], c["sh"], c["cu"]) for c in s["bad_cus"])
     out["ok"] = all(s["ok"] for s in out["formats"].values())
     out["bad_cus"] = [dict(xcc=x, se=se, sh=sh, cu=cu) for x, se, sh, cu in sorted(bad)]
+    return out
+
+
+# ---------------------------------------------------------------------------
+# Full-LDS march (ops.lds_march): all 160 KiB of a CU, both bit polarities,
+# ds_read_b32 and ds_read_b128 read-back, timed, attributed per CU. See the
+# kernel comment in hived_ops.hip.
+# ---------------------------------------------------------------------------
+LDS_MARCH_WORDS = 40960  # 163840 B, the whole LDS of a CU
+_LDS_MARCH_BYTES = 4 * LDS_MARCH_WORDS
+# default rounds per workgroup, and workgroups per CU of the default grid
+# (BENCHMARKS.md "LDS march")
+_LDS_MARCH_DEFAULT_ROUNDS = 8
+_LDS_MARCH_BLOCKS_PER_CU = 2
+
+
+def _fmix32(h):
+    """murmur3 32-bit finaliser on a numpy uint32 array."""
+    import numpy as np
+
+    h = h ^ (h >> np.uint32(16))
+    h = h * np.uint32(0x85EBCA6B)
+    h = h ^ (h >> np.uint32(13))
+    h = h * np.uint32(0xC2B2AE35)
+    return h ^ (h >> np.uint32(16))
+
+
+def lds_march_pattern(seed: int, round: int):
+    """The np.uint32[40960] pattern p(round, i) the kernel writes in the true
+    polarity: fmix32((seed + round*0x9E3779B9) ^ (i*0x85EBCA6B)). Every step
+    is a bijection on 32 bits, so the 40960 values of a round are distinct.
+    The complement passes write ~p."""
+    import numpy as np
+
+    rs = np.uint32((int(seed) + int(round) * 0x9E3779B9) & 0xFFFFFFFF)
+    i = np.arange(LDS_MARCH_WORDS, dtype=np.uint32)
+    return _fmix32(rs ^ (i * np.uint32(0x85EBCA6B)))
+
+
+def lds_march_block_checksum(seed: int, rounds: int) -> int:
+    """Expected sum of record field [6] over the four waves of a block: every
+    word of p is read once in phase 0 and once in phase 2 of each round, so
+    2 * sum_round sum_i p(round, i) mod 2^32."""
+    import numpy as np
+
+    total = sum(int(lds_march_pattern(seed, r).sum(dtype=np.uint64)) for r in range(rounds))
+    return (2 * total) & 0xFFFFFFFF
+
+
+def summarize_lds_march(records, elapsed_ms: float, rounds: int, seed: int,
+                        expected_cus: int) -> dict:
+    """Turn the per-wave records of one ops.lds_march launch into a verdict.
+
+    records: [blocks*4, 8] int32 rows {hw word, mismatched dwords, first bad
+    global pass (-1), lowest bad word in that pass (-1), dropped mask (bits
+    that should be 1 and read 0), raised mask (should be 0, read 1), sum of
+    the dwords read in phases 0 and 2, reserved}. The four waves of a block
+    (wave // 4) are combined; a block is attributed to the CU of its first
+    wave, and a block whose waves name different CUs is counted in
+    `split_blocks` (one workgroup runs on one CU, so that is a fault in
+    itself). Pure numpy; needs no GPU.
+    """
+    import numpy as np
+
+    rec = np.asarray(records).reshape(-1, 4, 8).astype(np.int64)
+    blocks = int(rec.shape[0])
+    nbytes = float(blocks) * rounds * 4 * 2 * _LDS_MARCH_BYTES
+    gbps = nbytes / (elapsed_ms * 1e-3) / 1e9 if elapsed_ms > 0 else 0.0
+    want_sum = lds_march_block_checksum(seed, rounds)
+    cus_seen = len({decode_hw_word(w) for w in np.unique(rec[:, :, 0])})
+    mismatched_blocks = split_blocks = 0
+    checksum_ok = True
+    bad: dict = {}
+    for blk in rec:
+        cus = [decode_hw_word(w) for w in blk[:, 0]]
+        if len(set(cus)) != 1:
+            split_blocks += 1
+        if (int(blk[:, 6].sum()) & 0xFFFFFFFF) != want_sum:
+            checksum_ok = False
+        mism = int(blk[:, 1].sum())
+        if mism == 0:
+            continue
+        mismatched_blocks += 1
+        first = min((int(w[2]), int(w[3])) for w in blk if w[1] != 0)
+        dropped = int(np.bitwise_or.reduce(blk[:, 4])) & 0xFFFFFFFF
+        raised = int(np.bitwise_or.reduce(blk[:, 5])) & 0xFFFFFFFF
+        e = bad.setdefault(cus[0], {"blocks": 0, "mismatched_dwords": 0, "first": first,
+                                    "dropped_mask": 0, "raised_mask": 0})
+        e["blocks"] += 1
+        e["mismatched_dwords"] += mism
+        e["first"] = min(e["first"], first)
+        e["dropped_mask"] |= dropped
+        e["raised_mask"] |= raised
+    bad_cus = []
+    for key in sorted(bad):
+        e = bad[key]
+        bad_cus.append(dict(xcc=key[0], se=key[1], sh=key[2], cu=key[3], blocks=e["blocks"],
+                            mismatched_dwords=e["mismatched_dwords"],
+                            first_bad_pass=e["first"][0], first_bad_word=e["first"][1],
+                            dropped_mask=e["dropped_mask"], raised_mask=e["raised_mask"]))
+    return {
+        "gbps": gbps,
+        "elapsed_ms": float(elapsed_ms),
+        "blocks": blocks,
+        "cus_seen": cus_seen,
+        "mismatched_blocks": mismatched_blocks,
+        "checksum_ok": checksum_ok,
+        "split_blocks": split_blocks,
+        "bad_cus": bad_cus,
+        "ok": bool(mismatched_blocks == 0 and checksum_ok and split_blocks == 0
+                   and cus_seen >= expected_cus),
+    }
+
+
+def lds_march_report(device: int = 0, blocks: int = None, rounds: int = None, seed: int = 1,
+                     inject=None) -> dict:
+    """Run the full-LDS march on one GPU and summarise it.
+
+    The kernel takes all 160 KiB of LDS, so one workgroup is resident per CU;
+    the default grid is two workgroups per CU (every CU is then covered on an
+    idle GPU) and the default rounds keep the launch at about a millisecond.
+    `inject=(block, word, pass, bit)` flips that bit of that LDS word in that
+    block after the write of that global pass (round*4 + phase): a harmless
+    store into the workgroup's own LDS that exercises detection and
+    attribution on healthy hardware.
+    """
+    import torch
+
+    ops = get_ops()
+    torch.cuda.set_device(device)
+    expected_cus = ops.device_info(device)["multiProcessorCount"]
+    blocks = _LDS_MARCH_BLOCKS_PER_CU * expected_cus if blocks is None else int(blocks)
+    rounds = _LDS_MARCH_DEFAULT_ROUNDS if rounds is None else int(rounds)
+    inject_args = (-1, -1, -1, 0) if inject is None else tuple(int(v) for v in inject)
+    records, ms = ops.lds_march(blocks, rounds, seed, *inject_args)
+    out = summarize_lds_march(records.cpu().numpy(), ms, rounds, seed, expected_cus)
+    out["rounds"] = rounds
     return out

@@ -9,6 +9,8 @@
 //                the host against a reference — catches broken matrix cores
 //  - mfma_burn:  sustained, timed MFMA issue per datapath, verified bitwise in
 //                the kernel; TFLOP/s plus the CU of any wave that was wrong
+//  - lds_march:  all 160 KiB of every CU's LDS, both bit polarities, narrow
+//                and wide reads, timed; the CU, word and bits of any mismatch
 //  - p2p copy:   xGMI link bandwidth between two GPUs (expected ~153 GB/s per
 //                link per direction); a degraded link marks the PAIR cell bad
 //
@@ -618,6 +620,252 @@ std::tuple<torch::Tensor, double> mfma_burn(torch::Tensor A, torch::Tensor B,
 }
 
 // ---------------------------------------------------------------------------
+// LDS march: a timed write/read-verify of the WHOLE 160 KiB LDS of a CU, in
+// both bit polarities and through both the narrow and the wide read path,
+// with the location and direction of any mismatch recorded per wave.
+// lds_check above touches a 64 KiB slab once with one value per word; this
+// kernel declares all 163840 B statically, so at most one workgroup is
+// resident per CU and that workgroup owns every byte of the CU's LDS.
+//
+// Pattern: p(round, i) = fmix32((seed + round*0x9E3779B9) ^ (i*0x85EBCA6B)),
+// fmix32 the murmur3 finaliser. The multiply by an odd constant, the xor and
+// fmix32 are bijections on 32 bits, so within a pass all 40960 words hold
+// distinct values and an address-decoder alias (two indices reaching one
+// cell) reads back as a data mismatch.
+//
+// Each round runs four passes (global pass index = round*4 + phase); word i
+// is always written by thread i mod 256 with ds_write_b32:
+//   phase 0: write  p, read b32, thread t reads words j = t+65 (mod 256)
+//   phase 1: write ~p, read b32, same mapping
+//   phase 2: write  p, read b128 (uint4), thread t reads quads q = t (mod 256)
+//   phase 3: write ~p, read b128
+// 40960 = 160*256, so in the b32 passes every word is read by lane+1 of
+// another wave than the one that wrote it. A barrier separates each write
+// from its read and each read from the next write. After the four passes
+// every bit of every word has been verified holding 0 and holding 1 through
+// ds_read_b32 and through ds_read_b128 (checked in the gfx950 disassembly:
+// the phase 2/3 loop issues ds_read_b128, the phase 0/1 loop ds_read_b32 and
+// the writes ds_write_b32).
+//
+// No LDS is left for a reduction: each wave reduces with shuffles and lane 0
+// writes its own record of eight int32 (two int4 vector stores):
+//   [0] (XCC_ID<<16)|HW_ID      (the cu_coverage_kernel encoding)
+//   [1] mismatched dwords over all passes
+//   [2] first bad global pass index (-1 if none)
+//   [3] lowest mismatching word index within that pass (-1 if none)
+//   [4] dropped mask: OR of (want & ~got), bits that should be 1 and read 0
+//   [5] raised mask:  OR of (got & ~want), bits that should be 0 and read 1
+//   [6] sum mod 2^32 of every dword this wave read in phases 0 and 2
+//   [7] 0 (reserved)
+// The host combines the four waves of a block.
+//
+// inject_* (default -1 = off): in block inject_block, at global pass
+// inject_pass, after that pass's write and barrier, thread 0 flips bit
+// inject_bit of lds[inject_word]; an extra barrier follows and the read
+// proceeds. A plain store into the workgroup's own LDS: it sends a known
+// one-bit fault through the real read-and-compare path on healthy hardware.
+// ---------------------------------------------------------------------------
+constexpr int LDS_MARCH_WORDS = 40960;  // 163840 B: the whole LDS of a CU
+constexpr int LDS_MARCH_THREADS = 256;  // four waves, one per SIMD
+// accesses per thread and batch; 160 words and 40 quads per thread and pass
+constexpr int LDS_MARCH_BATCH = 8;
+constexpr int LDS_MARCH_WIDE_BATCH = 4;
+static_assert(LDS_MARCH_WORDS % (LDS_MARCH_BATCH * LDS_MARCH_THREADS) == 0 &&
+                  (LDS_MARCH_WORDS / 4) % (LDS_MARCH_WIDE_BATCH * LDS_MARCH_THREADS) == 0,
+              "batches must tile the LDS exactly");
+
+__device__ __forceinline__ unsigned fmix32(unsigned h) {
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  return h;
+}
+
+// p(round, i) with rs = seed + round*0x9E3779B9
+__device__ __forceinline__ unsigned lds_march_pattern(unsigned rs, int i) {
+  return fmix32(rs ^ ((unsigned)i * 0x85EBCA6Bu));
+}
+
+struct LdsMarchState {
+  int mismatched, first_pass, first_word;
+  unsigned dropped, raised;
+};
+
+// a thread visits its words in ascending order within a pass, so the first
+// mismatch it sees in its first bad pass is its lowest
+__device__ __forceinline__ void lds_march_compare(LdsMarchState& s, unsigned got, unsigned want,
+                                                  int pass, int word) {
+  // branch-free, so the unrolled read loops keep their LDS reads in flight
+  const unsigned diff = got ^ want;
+  const bool bad = diff != 0;
+  const bool first = bad && s.first_pass < 0;
+  s.mismatched += bad;
+  s.dropped |= want & diff;
+  s.raised |= got & diff;
+  s.first_pass = first ? pass : s.first_pass;
+  s.first_word = first ? word : s.first_word;
+}
+
+__global__ void __launch_bounds__(LDS_MARCH_THREADS)
+lds_march_kernel(int4* __restrict__ records, int rounds, unsigned seed, int inject_block,
+                 int inject_word, int inject_pass, int inject_bit) {
+  __shared__ __attribute__((aligned(16))) unsigned lds[LDS_MARCH_WORDS];
+  const int t = threadIdx.x;
+  const int lane = t & 63;
+  const int wave = blockIdx.x * (LDS_MARCH_THREADS >> 6) + (t >> 6);
+  unsigned hwid, xcc;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+
+  const bool inject_block_here = (int)blockIdx.x == inject_block &&
+                                 (unsigned)inject_word < (unsigned)LDS_MARCH_WORDS;
+  const int tr = (t + 65) & (LDS_MARCH_THREADS - 1);  // b32 read mapping
+  LdsMarchState s = {0, -1, -1, 0u, 0u};
+  unsigned checksum = 0;
+  for (int round = 0; round < rounds; round++) {
+    const unsigned rs = seed + (unsigned)round * 0x9E3779B9u;
+    for (int phase = 0; phase < 4; phase++) {
+      const int pass = round * 4 + phase;
+      const unsigned inv = (phase & 1) ? 0xFFFFFFFFu : 0u;
+      const unsigned sum_mask = (phase & 1) ? 0u : 0xFFFFFFFFu;
+      // Batches of LDS_MARCH_BATCH accesses per thread: the values of a batch
+      // are hashed (or compared) in registers around one run of LDS
+      // instructions, so several are in flight per wave. The empty asm
+      // between two accesses keeps each one a single ds_write_b32 /
+      // ds_read_b32: the compiler otherwise pairs the strided accesses into
+      // ds_write2st64_b32 / ds_read2st64_b32.
+      for (int base = t; base < LDS_MARCH_WORDS; base += LDS_MARCH_BATCH * LDS_MARCH_THREADS) {
+        unsigned val[LDS_MARCH_BATCH];
+#pragma unroll
+        for (int k = 0; k < LDS_MARCH_BATCH; k++)
+          val[k] = lds_march_pattern(rs, base + k * LDS_MARCH_THREADS) ^ inv;
+#pragma unroll
+        for (int k = 0; k < LDS_MARCH_BATCH; k++) {
+          lds[base + k * LDS_MARCH_THREADS] = val[k];
+          asm volatile("" ::: "memory");
+        }
+      }
+      __syncthreads();
+      if (inject_block_here && pass == inject_pass) {  // block-uniform
+        if (t == 0) lds[inject_word] ^= 1u << inject_bit;
+        __syncthreads();
+      }
+      if (phase < 2) {
+        for (int base = tr; base < LDS_MARCH_WORDS; base += LDS_MARCH_BATCH * LDS_MARCH_THREADS) {
+          unsigned got[LDS_MARCH_BATCH];
+#pragma unroll
+          for (int k = 0; k < LDS_MARCH_BATCH; k++) {
+            got[k] = lds[base + k * LDS_MARCH_THREADS];
+            asm volatile("" ::: "memory");
+          }
+#pragma unroll
+          for (int k = 0; k < LDS_MARCH_BATCH; k++) {
+            int j = base + k * LDS_MARCH_THREADS;
+            checksum += got[k] & sum_mask;
+            lds_march_compare(s, got[k], lds_march_pattern(rs, j) ^ inv, pass, j);
+          }
+        }
+      } else {
+        const uint4* quads = reinterpret_cast<const uint4*>(lds);
+        for (int base = t; base < LDS_MARCH_WORDS / 4;
+             base += LDS_MARCH_WIDE_BATCH * LDS_MARCH_THREADS) {
+          uint4 got[LDS_MARCH_WIDE_BATCH];
+#pragma unroll
+          for (int k = 0; k < LDS_MARCH_WIDE_BATCH; k++)
+            got[k] = quads[base + k * LDS_MARCH_THREADS];
+#pragma unroll
+          for (int k = 0; k < LDS_MARCH_WIDE_BATCH; k++) {
+            int j = 4 * (base + k * LDS_MARCH_THREADS);
+            checksum += (got[k].x + got[k].y + got[k].z + got[k].w) & sum_mask;
+            lds_march_compare(s, got[k].x, lds_march_pattern(rs, j) ^ inv, pass, j);
+            lds_march_compare(s, got[k].y, lds_march_pattern(rs, j + 1) ^ inv, pass, j + 1);
+            lds_march_compare(s, got[k].z, lds_march_pattern(rs, j + 2) ^ inv, pass, j + 2);
+            lds_march_compare(s, got[k].w, lds_march_pattern(rs, j + 3) ^ inv, pass, j + 3);
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  // wave reduction with shuffles; -1 as unsigned is the largest value, so an
+  // unsigned min picks the earliest pass, then the lowest word among the
+  // lanes that failed in that pass
+  unsigned first_pass = (unsigned)s.first_pass;
+  for (int off = 32; off > 0; off >>= 1) {
+    s.mismatched += __shfl_xor(s.mismatched, off);
+    s.dropped |= (unsigned)__shfl_xor((int)s.dropped, off);
+    s.raised |= (unsigned)__shfl_xor((int)s.raised, off);
+    checksum += (unsigned)__shfl_xor((int)checksum, off);
+    first_pass = min(first_pass, (unsigned)__shfl_xor((int)first_pass, off));
+  }
+  unsigned first_word = (unsigned)s.first_pass == first_pass ? (unsigned)s.first_word : 0xFFFFFFFFu;
+  for (int off = 32; off > 0; off >>= 1)
+    first_word = min(first_word, (unsigned)__shfl_xor((int)first_word, off));
+  if (lane == 0) {
+    records[2 * wave] = make_int4((int)((xcc << 16) | (hwid & 0xffff)), s.mismatched,
+                                  (int)first_pass, (int)first_word);
+    records[2 * wave + 1] = make_int4((int)s.dropped, (int)s.raised, (int)checksum, 0);
+  }
+}
+
+// One untimed warm-up launch, then one launch timed with HIP events.
+// Returns (records [blocks*4, 8] int32, elapsed_ms of the timed launch).
+std::tuple<torch::Tensor, double> lds_march(long blocks, long rounds, long seed,
+                                            long inject_block, long inject_word,
+                                            long inject_pass, long inject_bit) {
+  TORCH_CHECK(blocks >= 1 && blocks <= (1L << 16), "blocks must be in [1, 2^16]");
+  TORCH_CHECK(rounds >= 1, "rounds must be >= 1");
+  // bounded run: a round of one workgroup measures ~51 us on an MI355X
+  // (BENCHMARKS.md "LDS march"). The LDS instructions alone would need ~14 k
+  // clocks, ~6 us (163840 B x 4 written at 64 B/clk, x 2 read at 128 and x 2
+  // at 256 B/clk); the rest is the hash arithmetic of the pattern, with one
+  // wave per SIMD to hide it. One workgroup per CU on 256 CUs then puts 2^20
+  // block-rounds at ~0.2 s
+  TORCH_CHECK(rounds <= (1L << 20) && blocks * rounds <= (1L << 20),
+              "blocks*rounds must be <= 2^20");
+  TORCH_CHECK(inject_block >= -1 && inject_block < blocks, "inject_block out of range");
+  TORCH_CHECK(inject_word >= -1 && inject_word < LDS_MARCH_WORDS, "inject_word out of range");
+  TORCH_CHECK(inject_pass >= -1 && inject_pass < rounds * 4, "inject_pass out of range");
+  TORCH_CHECK(inject_bit >= 0 && inject_bit < 32, "inject_bit out of range");
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  hipDeviceProp_t prop;
+  HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+  const size_t need = LDS_MARCH_WORDS * sizeof(unsigned);
+  TORCH_CHECK(prop.sharedMemPerBlock >= need, "lds_march needs ", need,
+              " B of LDS per workgroup; this device offers ", prop.sharedMemPerBlock);
+  long waves = blocks * (LDS_MARCH_THREADS / 64);
+  auto records = torch::zeros({waves, 8},
+                              torch::TensorOptions().dtype(torch::kInt32).device(torch::kCUDA));
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  auto launch = [&]() {
+    hipLaunchKernelGGL(lds_march_kernel, dim3(blocks), dim3(LDS_MARCH_THREADS), 0, stream,
+                       reinterpret_cast<int4*>(records.data_ptr<int>()), (int)rounds,
+                       (unsigned)seed, (int)inject_block, (int)inject_word, (int)inject_pass,
+                       (int)inject_bit);
+  };
+  launch();  // warm-up: code-object load and clock ramp stay out of the timing
+  HIP_CHECK(hipGetLastError());
+  hipEvent_t start, stop;
+  HIP_CHECK(hipEventCreate(&start));
+  HIP_CHECK(hipEventCreate(&stop));
+  HIP_CHECK(hipEventRecord(start, stream));
+  launch();
+  HIP_CHECK(hipEventRecord(stop, stream));
+  HIP_CHECK(hipGetLastError());
+  // the torch stream is non-blocking (see lds_check): wait on the stop event
+  // before anything reads the records or the timing
+  HIP_CHECK(hipEventSynchronize(stop));
+  float ms = 0;
+  HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
+  HIP_CHECK(hipEventDestroy(start));
+  HIP_CHECK(hipEventDestroy(stop));
+  return std::make_tuple(records, (double)ms);
+}
+
+// ---------------------------------------------------------------------------
 // xGMI p2p bandwidth between two devices (one direction).
 // ---------------------------------------------------------------------------
 double p2p_gbps(int src_dev, int dst_dev, long size_mb, long iters) {
@@ -807,6 +1055,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Stuck-bit pattern sweep over up to max_gib GiB of HBM; returns error count");
   m.def("lds_check", &lds_check, py::arg("blocks") = 2048, py::arg("seed") = 1,
         "LDS slab write/read-verify across the chip; returns error count");
+  m.def("lds_march", &lds_march, py::arg("blocks"), py::arg("rounds"), py::arg("seed"),
+        py::arg("inject_block") = -1, py::arg("inject_word") = -1, py::arg("inject_pass") = -1,
+        py::arg("inject_bit") = 0,
+        "Full-LDS (160 KiB per CU) march: both polarities, b32 and b128 read-back, timed; "
+        "returns (per-wave records [blocks*4,8], ms)");
   m.def("cu_coverage", &cu_coverage, py::arg("blocks") = 4096,
         "Per-wave (XCC_ID<<16 | HW_ID) placement words for CU-coverage checks");
   m.def("device_info", &device_info, py::arg("dev") = 0);
