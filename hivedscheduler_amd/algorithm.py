@@ -59,13 +59,15 @@ class HivedAlgorithm:
     """Thread-safe wrapper: a single lock serializes all calls, matching the
     reference's algorithmLock (hived_algorithm.go:104).
 
-    The one call per decision, `schedule_pod`, is the exception: it is the
-    core's own native method, bound in __init__, with no Python frame, lock or
-    `try` around it. The core holds the GIL from its first read of core state
-    to its last write and runs no Python code in between (see
-    PyHivedCore::schedulePod in core/bindings.cpp), so the lock would serialise
-    nothing there that the GIL does not, and the native method itself turns a
-    core error into the WebServerError that `_call` raises.
+    The one call per decision, `schedule_pod`, and the release of a pod by its
+    key, `delete_allocated_pod_by_key`, are the exceptions: they are the core's
+    own native methods, bound in __init__, with no Python frame, lock or `try`
+    around them. The core holds the GIL from its first read of core state to
+    its last write and runs no Python code in between (see
+    PyHivedCore::schedulePod and ::deleteAllocatedPodByKey in
+    core/bindings.cpp), so the lock would serialise nothing there that the GIL
+    does not, and the native methods themselves turn a core error into the
+    WebServerError that `_call` raises.
     """
 
     def __init__(self, config: Config):
@@ -82,6 +84,13 @@ class HivedAlgorithm:
         # commit=True add the pod as allocated on a bind decision.
         # suggested_nodes=None stands for every node of the cluster.
         self.schedule_pod = self._core.schedule_validated_pod
+        # delete_allocated_pod_by_key(pod_key) -> bool
+        # Releases the allocated pod the core holds under pod_key, exactly as
+        # delete_allocated_pod(spec, info, pod_key) does for the spec and bind
+        # info the pod was added with. False, with nothing changed, if the core
+        # holds no such pod (never added, released already, or added before a
+        # restart and not replayed yet): fall back to the spec / info form then.
+        self.delete_allocated_pod_by_key = self._core.delete_validated_pod_by_key
 
     def _call(self, fn, *args):
         with self._lock:

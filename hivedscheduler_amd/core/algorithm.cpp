@@ -4,7 +4,6 @@
 // Semantics parity: pkg/algorithm/hived_algorithm.go:180-1352 and
 // pkg/algorithm/utils.go:38-310; state machines per doc/design/state-machine.md.
 #include <cstdio>
-#include <functional>
 #include <cstdlib>
 
 #include "core.hpp"
@@ -136,6 +135,14 @@ bool allPodsReleased(const std::map<int, std::vector<AllocatedPod>>& allocatedPo
   return true;
 }
 
+bool anyBoundUnder(PhysicalCell* c) {
+  if (c->virt != nullptr) return true;
+  for (Cell* ch : c->children) {
+    if (anyBoundUnder(static_cast<PhysicalCell*>(ch))) return true;
+  }
+  return false;
+}
+
 std::unique_ptr<Group> newGroup(const PodSpec& s, GState state) {
   auto g = std::make_unique<Group>();
   g->name = s.groupName;
@@ -148,8 +155,13 @@ std::unique_ptr<Group> newGroup(const PodSpec& s, GState state) {
   g->totalPodNums = s.groupPodNums;
   for (auto& [leafNum, podNum] : s.groupPodNums) {
     g->allocatedPods[leafNum].resize(podNum);
-    g->physPlacement[leafNum].assign(podNum, std::vector<PhysicalCell*>(leafNum, nullptr));
-    g->virtPlacement[leafNum].assign(podNum, std::vector<VirtualCell*>(leafNum, nullptr));
+    // filled in place: no prototype vector to copy from and throw away
+    auto& phys = g->physPlacement[leafNum];
+    phys.resize(podNum);
+    for (auto& pod : phys) pod.assign(leafNum, nullptr);
+    auto& virt = g->virtPlacement[leafNum];
+    virt.resize(podNum);
+    for (auto& pod : virt) pod.assign(leafNum, nullptr);
   }
   return g;
 }
@@ -311,7 +323,7 @@ bool HivedCore::schedulePodFromExistingGroup(
   *hasVirtual = g->hasVirtualPlacement;
   *virt = g->virtPlacement;
   Victims v = collectPreemptionVictims(g->physPlacement);
-  *victims = v.byNode;
+  *victims = std::move(v.byNode);
   g->preemptingPods.insert(podKey);
   return true;
 }
@@ -327,13 +339,13 @@ void HivedCore::schedulePodFromNewGroup(const PodSpec& s,
     return;
   }
   Victims v = collectPreemptionVictims(*phys);
-  *victims = v.byNode;
+  *victims = std::move(v.byNode);  // v.byNode is not read below
   if (phase == Phase::Preempting) {
     // cancel lower-priority preemptors whose reservations overlap ours
     for (Group* preemptor : v.overlappingPreemptors) {
       deletePreemptingGroup(preemptor, podKey);
     }
-    if (!v.byNode.empty()) {
+    if (!victims->empty()) {
       // reserve cells immediately so equal-priority groups cannot contend
       createPreemptingGroup(s, *phys, *virt, podKey);
     }
@@ -470,14 +482,16 @@ bool HivedCore::scheduleGuaranteedGroup(SchedulingRequest& sr, Placement<Physica
       }
     }
 
-    std::unordered_map<VirtualCell*, PhysicalCell*> bindings;
+    CellBindings bindings;
     auto lazyPreempted = tryLazyPreempt(*virt, sr.groupName);
 
-    // build binding paths: trees of unbound virtual cells to bind
-    std::vector<std::unique_ptr<BindingVertex>> roots;
-    std::vector<BindingVertex*> preassigned;
-    std::vector<std::vector<BindingVertex*>> nonPreassigned;
-    std::unordered_map<VirtualCell*, BindingVertex*> vertexMap;
+    // build binding paths: trees of unbound virtual cells to bind. The
+    // vertices and the lists come from the core's scratch (see MapScratch).
+    MapScratch& ms = mapScratch_;
+    ms.reset();
+    std::vector<BindingVertex*>& preassigned = ms.preassigned;
+    SmallPtrMap<VirtualCell, BindingVertex*, 32> vertexMap;
+    std::vector<VirtualCell*>& path = ms.path;
     for (auto& [leafNum, pods] : *virt) {
       (void)leafNum;
       for (auto& pod : pods) {
@@ -486,7 +500,7 @@ bool HivedCore::scheduleGuaranteedGroup(SchedulingRequest& sr, Placement<Physica
             bindings[leaf] = leaf->phys;
             continue;
           }
-          std::vector<VirtualCell*> path;
+          path.clear();
           for (Cell* c = leaf; c != nullptr; c = c->parent) {
             auto* vc = static_cast<VirtualCell*>(c);
             if (vc->phys != nullptr || vertexMap.count(vc)) break;
@@ -494,47 +508,49 @@ bool HivedCore::scheduleGuaranteedGroup(SchedulingRequest& sr, Placement<Physica
           }
           if (path.empty()) continue;
           VirtualCell* pathRoot = path.back();
-          auto rootVertex = std::make_unique<BindingVertex>();
-          rootVertex->cell = pathRoot;
-          BindingVertex* rootPtr = rootVertex.get();
+          BindingVertex* rootPtr = ms.newVertex(pathRoot);
           vertexMap[pathRoot] = rootPtr;
           if (pathRoot->parent == nullptr) {
             preassigned.push_back(rootPtr);
-            roots.push_back(std::move(rootVertex));
           } else if (static_cast<VirtualCell*>(pathRoot->parent)->phys != nullptr) {
             bool buddyExists = false;
-            for (auto& grp : nonPreassigned) {
+            for (size_t gi = 0; gi < ms.nonPreassignedUsed; gi++) {
+              auto& grp = ms.nonPreassigned[gi];
               if (grp[0]->cell->parent == pathRoot->parent) {
                 grp.push_back(rootPtr);
                 buddyExists = true;
                 break;
               }
             }
-            if (!buddyExists) nonPreassigned.push_back({rootPtr});
-            roots.push_back(std::move(rootVertex));
+            if (!buddyExists) ms.newNonPreassignedGroup().push_back(rootPtr);
           } else {
-            BindingVertex* parentVertex = vertexMap.at(static_cast<VirtualCell*>(pathRoot->parent));
-            parentVertex->children.push_back(std::move(rootVertex));
+            vertexMap.at(static_cast<VirtualCell*>(pathRoot->parent))->children.push_back(rootPtr);
           }
           for (int i = static_cast<int>(path.size()) - 2; i >= 0; i--) {
-            auto childVertex = std::make_unique<BindingVertex>();
-            childVertex->cell = path[i];
-            vertexMap[path[i]] = childVertex.get();
-            vertexMap.at(static_cast<VirtualCell*>(path[i]->parent))
-                ->children.push_back(std::move(childVertex));
+            BindingVertex* childVertex = ms.newVertex(path[i]);
+            vertexMap[path[i]] = childVertex;
+            vertexMap.at(static_cast<VirtualCell*>(path[i]->parent))->children.push_back(childVertex);
           }
         }
       }
     }
 
-    const std::unordered_map<VirtualCell*, PhysicalCell*> seedBindings = bindings;
+    // a second mapping try starts from the bound leaves alone; the copy is
+    // taken only where a second try can follow
+    const bool mayRetry = !honorOnly && (sr.cleanWorld != nullptr || badLinks);
+    CellBindings seedBindings;
+    if (mayRetry) seedBindings = bindings;
+    bool firstTry = true;
     auto tryMap = [&](bool honorLinks) {
-      bindings = seedBindings;  // drop partial picks from a failed attempt
-      std::map<int, int> freeCellNumCopy = allVCFreeCellNum_[*sr.chain];
-      return mapVirtualPlacementToPhysical(preassigned, nonPreassigned,
-                                           freeCellList_[*sr.chain].shallowCopy(), freeCellNumCopy,
-                                           *sr.suggestedNodes, sr.ignoreSuggestedNodes, bindings,
-                                           sr.hbmBytes, honorLinks, sr.cleanWorld);
+      if (!firstTry) bindings = seedBindings;  // drop partial picks from a failed attempt
+      firstTry = false;
+      // working copies, assigned into the scratch's own storage
+      ms.freeList = freeCellList_[*sr.chain];
+      ms.freeCellNum = allVCFreeCellNum_[*sr.chain];
+      return mapVirtualPlacementToPhysical(preassigned, ms.nonPreassigned, ms.nonPreassignedUsed,
+                                           ms.freeList, ms.freeCellNum, *sr.suggestedNodes,
+                                           sr.ignoreSuggestedNodes, bindings, sr.hbmBytes,
+                                           honorLinks, sr.cleanWorld);
     };
     bool mapped;
     if (honorOnly) {
@@ -687,21 +703,23 @@ void HivedCore::deleteUnallocatedPod(const PodSpec& s, const std::string& podKey
 void HivedCore::addAllocatedPod(const PodSpec& s, const BindInfo& info, const std::string& podKey) {
   OpGuard opGuard(this);
   int podIndex = 0;
+  bool releasable = true;
+  Group* g = nullptr;
   auto it = groups_.find(s.groupName);
   if (it != groups_.end()) {
-    Group* g = it->second.get();
+    g = it->second.get();
     if (g->state == GState::Preempting) allocatePreemptingGroup(g, podKey);
     podIndex = getAllocatedPodIndex(info, s.leafCellNumber);
     if (podIndex == -1) return;  // placement not found in group; ignore
   } else {
-    createAllocatedGroup(s, info, podKey);
+    g = createAllocatedGroup(s, info, podKey);
     podIndex = getAllocatedPodIndex(info, s.leafCellNumber);
-    if (podIndex == -1) podIndex = 0;
+    if (podIndex == -1) {
+      podIndex = 0;
+      releasable = false;  // deleteAllocatedPod will not find this pod either
+    }
   }
-  Group* g = groups_.at(s.groupName).get();
-  auto& slots = g->allocatedPods[s.leafCellNumber];
-  if (podIndex >= static_cast<int>(slots.size())) slots.resize(podIndex + 1);
-  slots[podIndex] = AllocatedPod{true, podKey, info.node, info};
+  setPodSlot(g, s.leafCellNumber, podIndex, releasable, podKey, info);
 }
 
 void HivedCore::deleteAllocatedPod(const PodSpec& s, const BindInfo& info,
@@ -712,19 +730,71 @@ void HivedCore::deleteAllocatedPod(const PodSpec& s, const BindInfo& info,
   Group* g = it->second.get();
   int podIndex = getAllocatedPodIndex(info, s.leafCellNumber);
   if (podIndex == -1) return;
-  auto& slots = g->allocatedPods[s.leafCellNumber];
-  if (podIndex < static_cast<int>(slots.size())) slots[podIndex] = AllocatedPod{};
+  clearPodSlot(g, s.leafCellNumber, podIndex);
   if (allPodsReleased(g->allocatedPods)) {
     deleteAllocatedGroup(g, podKey);
   }
+}
+
+bool HivedCore::deleteAllocatedPodByKey(const std::string& podKey) {
+  auto it = podIndex_.find(podKey);
+  if (it == podIndex_.end()) return false;
+  const PodSlotRef ref = it->second;
+  OpGuard opGuard(this);
+  if (!ref.releasable) return true;  // as deleteAllocatedPod: podIndex == -1
+  // the entry found above is the slot's own (setPodSlot wrote both), so it
+  // goes here and clearPodSlot has no second lookup to make
+  podIndex_.erase(it);
+  ref.group->allocatedPods[ref.leafCellNum][ref.podIndex] = AllocatedPod{};
+  if (allPodsReleased(ref.group->allocatedPods)) {
+    deleteAllocatedGroup(ref.group, podKey);
+  }
+  return true;
+}
+
+// The three writers of an allocatedPods slot; they keep podIndex_ in step.
+void HivedCore::setPodSlot(Group* g, int leafCellNum, int podIndex, bool releasable,
+                           const std::string& podKey, const BindInfo& info) {
+  auto& slots = g->allocatedPods[leafCellNum];
+  if (podIndex >= static_cast<int>(slots.size())) slots.resize(podIndex + 1);
+  AllocatedPod& slot = slots[podIndex];
+  if (slot.present && slot.key != podKey) clearPodSlot(g, leafCellNum, podIndex);
+  slot.present = true;
+  slot.key = podKey;
+  slot.node = info.node;
+  slot.bindInfo = info;
+  podIndex_[podKey] = PodSlotRef{g, leafCellNum, podIndex, releasable};
+}
+
+void HivedCore::clearPodSlot(Group* g, int leafCellNum, int podIndex) {
+  auto& slots = g->allocatedPods[leafCellNum];
+  if (podIndex >= static_cast<int>(slots.size())) return;
+  AllocatedPod& slot = slots[podIndex];
+  if (slot.present) {
+    auto it = podIndex_.find(slot.key);
+    if (it != podIndex_.end() && it->second.group == g &&
+        it->second.leafCellNum == leafCellNum && it->second.podIndex == podIndex) {
+      podIndex_.erase(it);
+    }
+  }
+  slot = AllocatedPod{};
+}
+
+void HivedCore::eraseGroup(Group* g) {
+  for (auto& [leafNum, pods] : g->allocatedPods) {
+    for (size_t i = 0; i < pods.size(); i++) {
+      if (pods[i].present) clearPodSlot(g, leafNum, static_cast<int>(i));
+    }
+  }
+  groups_.erase(g->name);
 }
 
 // ---------------------------------------------------------------------------
 // Group lifecycle
 // ---------------------------------------------------------------------------
 
-void HivedCore::createAllocatedGroup(const PodSpec& s, const BindInfo& info,
-                                     const std::string& podKey) {
+Group* HivedCore::createAllocatedGroup(const PodSpec& s, const BindInfo& info,
+                                       const std::string& podKey) {
   auto group = newGroup(s, GState::Allocated);
   Group* g = group.get();
   groups_[s.groupName] = std::move(group);
@@ -787,6 +857,7 @@ void HivedCore::createAllocatedGroup(const PodSpec& s, const BindInfo& info,
   if (shouldLazyPreempt) {
     lazyPreemptGroup(g, g->name);
   }
+  return g;
 }
 
 void HivedCore::deleteAllocatedGroup(Group* g, const std::string& podKey) {
@@ -807,7 +878,7 @@ void HivedCore::deleteAllocatedGroup(Group* g, const std::string& podKey) {
       }
     }
   }
-  groups_.erase(g->name);
+  eraseGroup(g);
 }
 
 void HivedCore::createPreemptingGroup(const PodSpec& s, const Placement<PhysicalCell>& phys,
@@ -884,7 +955,7 @@ void HivedCore::deletePreemptingGroup(Group* g, const std::string& podKey) {
       if (!stillPreempted) other->state = GState::Allocated;
     }
   }
-  groups_.erase(g->name);
+  eraseGroup(g);
 }
 
 void HivedCore::allocatePreemptingGroup(Group* g, const std::string& podKey) {
@@ -965,7 +1036,22 @@ std::pair<PhysicalCell*, VirtualCell*> HivedCore::findAllocatedLeafCell(
   *lazyPreempt = false;
   *isOpportunistic = false;
   int leafIndex = placement.leafIndices[index];
-  PhysicalCell* p = findPhysicalLeafCell(fullCellList_, chain, placement.node, leafIndex);
+  // The node's own leaves settle it whenever at most one of them carries the
+  // index: that leaf is what the search by chain finds, in the named chain or,
+  // failing that, in another. Two leaves of one node name with one index (the
+  // name used in two chains) leave the choice to that search.
+  PhysicalCell* p = nullptr;
+  int matches = 0;
+  if (auto nodeIt = nodeLeafCellsStorage_.find(placement.node);
+      nodeIt != nodeLeafCellsStorage_.end()) {
+    for (PhysicalCell* leaf : nodeIt->second) {
+      if (leaf->leafIndices[0] == leafIndex) {
+        p = leaf;
+        matches++;
+      }
+    }
+  }
+  if (matches > 1) p = findPhysicalLeafCell(fullCellList_, chain, placement.node, leafIndex);
   if (p == nullptr) return {nullptr, nullptr};
   if (placement.preassignedTypes.empty()) {
     *lazyPreempt = true;
@@ -1013,15 +1099,8 @@ std::pair<PhysicalCell*, VirtualCell*> HivedCore::findAllocatedLeafCell(
     // freshly binding `pre` on top would nest ownerships (fuzz-found:
     // left the sibling quad in the free list while bound)
     if (pre->virt == nullptr) {
-      std::function<bool(PhysicalCell*)> anyBound = [&](PhysicalCell* c) -> bool {
-        if (c->virt != nullptr) return true;
-        for (Cell* ch : c->children) {
-          if (anyBound(static_cast<PhysicalCell*>(ch))) return true;
-        }
-        return false;
-      };
       for (Cell* ch : pre->children) {
-        if (anyBound(static_cast<PhysicalCell*>(ch))) {
+        if (anyBoundUnder(static_cast<PhysicalCell*>(ch))) {
           *lazyPreempt = true;
           return {p, nullptr};
         }

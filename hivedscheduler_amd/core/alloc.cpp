@@ -27,7 +27,7 @@ namespace {
 // property oracle, seed 1999-class: the 4-leaf vertex retried on another
 // quad still saw its abandoned quad's claims).
 struct ClaimSet {
-  std::unordered_map<PhysicalCell*, int> refs;
+  SmallPtrMap<PhysicalCell, int, 32> refs;
   std::vector<PhysicalCell*> log;  // claimed leaves, in order
 
   bool count(PhysicalCell* c) const { return refs.count(c) > 0; }
@@ -43,8 +43,8 @@ struct ClaimSet {
       PhysicalCell* leaf = log.back();
       log.pop_back();
       for (PhysicalCell* a = leaf; a != nullptr; a = static_cast<PhysicalCell*>(a->parent)) {
-        auto it = refs.find(a);
-        if (--it->second == 0) refs.erase(it);
+        int* r = refs.find(a);
+        if (--*r == 0) refs.erase(a);
       }
     }
   }
@@ -53,7 +53,7 @@ struct ClaimSet {
 struct AllocCtx {
   const std::set<std::string>& suggested;
   bool ignoreSuggested;
-  std::unordered_map<VirtualCell*, PhysicalCell*>& bindings;
+  CellBindings& bindings;
   // exact claim tracking (see ClaimSet): drives the packing sort keys AND
   // the honorLinks pick-time link constraint
   ClaimSet& claimed;
@@ -77,7 +77,7 @@ struct AllocCtx {
 int vertexLeafDemand(const BindingVertex* v) {
   if (v->children.empty()) return v->cell->totalLeaf;
   int n = 0;
-  for (auto& ch : v->children) n += vertexLeafDemand(ch.get());
+  for (BindingVertex* ch : v->children) n += vertexLeafDemand(ch);
   return n;
 }
 
@@ -97,10 +97,12 @@ bool leafLinkConflict(const AllocCtx& ctx, PhysicalCell* leaf) {
 // Usable = unbound, not a known-bad single-node cell, and (unless ignoring
 // suggestions) at least one node within the suggested set. Sorted by
 // opportunistic usage ascending to minimize preemption of opportunistic pods.
-std::vector<PhysicalCell*> getUsablePhysicalCells(const std::vector<Cell*>& candidates,
-                                                  int numNeeded, const AllocCtx& ctx,
-                                                  int demandLeaves = 0) {
-  std::vector<PhysicalCell*> usable;
+// Fills `usable` (emptied first); leaves it empty when fewer than numNeeded
+// cells are usable.
+void getUsablePhysicalCells(const std::vector<Cell*>& candidates, int numNeeded,
+                            const AllocCtx& ctx, int demandLeaves,
+                            std::vector<PhysicalCell*>& usable) {
+  usable.clear();
   for (Cell* cc : candidates) {
     auto* c = static_cast<PhysicalCell*>(cc);
     if (c->virt != nullptr) continue;
@@ -125,7 +127,10 @@ std::vector<PhysicalCell*> getUsablePhysicalCells(const std::vector<Cell*>& cand
     }
     usable.push_back(c);
   }
-  if (static_cast<int>(usable.size()) < numNeeded) return {};
+  if (static_cast<int>(usable.size()) < numNeeded) {
+    usable.clear();
+    return;
+  }
   // Buddy packing first: prefer candidates in already-fragmented regions
   // (fewer untouched free buddies), so intact higher-level free cells — other
   // VCs' guarantees — survive. Fuzz-found: picking a pair under the last
@@ -162,7 +167,7 @@ std::vector<PhysicalCell*> getUsablePhysicalCells(const std::vector<Cell*>& cand
   auto linkKey = [demandLeaves](PhysicalCell* c) {
     return demandLeaves >= 2 ? c->badLinksUnder : -c->badLinksUnder;
   };
-  std::stable_sort(usable.begin(), usable.end(), [&](PhysicalCell* a, PhysicalCell* b) {
+  stableSortSmall(usable.begin(), usable.end(), [&](PhysicalCell* a, PhysicalCell* b) {
     bool pa = parentClaimed(a), pb = parentClaimed(b);
     if (pa != pb) return pa;
     int fa = freeBuddies(a), fb = freeBuddies(b);
@@ -178,37 +183,35 @@ std::vector<PhysicalCell*> getUsablePhysicalCells(const std::vector<Cell*>& cand
               u->usedAt(kOpportunisticPriority));
     fprintf(stderr, "\n");
   }
-  return usable;
 }
 
 // Backtracking bipartite match of virtual cells onto candidate physical cells,
 // recursing into children to preserve the intra-cell topology.
-bool mapVirtualCellsToPhysical(const std::vector<BindingVertex*>& cellsIn,
+bool mapVirtualCellsToPhysical(BindingVertex* const* cellsIn, size_t numCells,
                                const std::vector<Cell*>& candidatesIn, const AllocCtx& ctx,
                                bool returnPicked, std::vector<PhysicalCell*>* picked) {
   // Multi-leaf vertices map first (demand descending) so they get the
   // link-clean candidates and single-leaf vertices take the leftovers
   // (incl. degraded pairs, which suit them fine).
-  std::vector<BindingVertex*> cells = cellsIn;
+  SmallBuf<BindingVertex*> cells(numCells);
   int maxDemand = 0;
-  {
-    std::vector<int> demand(cells.size());
-    for (size_t i = 0; i < cells.size(); i++) {
-      demand[i] = vertexLeafDemand(cells[i]);
-      maxDemand = std::max(maxDemand, demand[i]);
-    }
-    std::stable_sort(cells.begin(), cells.end(), [&](BindingVertex* a, BindingVertex* b) {
+  for (size_t i = 0; i < numCells; i++) {
+    cells[i] = cellsIn[i];
+    maxDemand = std::max(maxDemand, vertexLeafDemand(cells[i]));
+  }
+  if (numCells > 1) {
+    stableSortSmall(cells.begin(), cells.end(), [&](BindingVertex* a, BindingVertex* b) {
       return vertexLeafDemand(a) > vertexLeafDemand(b);
     });
   }
-  std::vector<PhysicalCell*> candidates =
-      getUsablePhysicalCells(candidatesIn, static_cast<int>(cells.size()), ctx, maxDemand);
-  if (candidates.empty() && !cells.empty()) return false;
+  std::vector<PhysicalCell*> candidates;
+  getUsablePhysicalCells(candidatesIn, static_cast<int>(cells.size()), ctx, maxDemand, candidates);
+  if (candidates.empty() && numCells != 0) return false;
   int n = static_cast<int>(cells.size());
   int m = static_cast<int>(candidates.size());
-  std::vector<int> pickedIdx(n, 0);
-  std::vector<size_t> claimCp(n, 0);  // claims checkpoint before each vertex's pick
-  std::vector<bool> used(m, false);
+  SmallBuf<int> pickedIdx(n, 0);
+  SmallBuf<size_t> claimCp(n, 0);  // claims checkpoint before each vertex's pick
+  SmallBuf<char> used(m, 0);
   int cellIndex = 0;
   while (cellIndex >= 0) {
     int candidateIndex;
@@ -223,10 +226,9 @@ bool mapVirtualCellsToPhysical(const std::vector<BindingVertex*>& cellsIn,
         ctx.bindings[cells[cellIndex]->cell] = candidate;
         markClaimed(ctx, candidate);
       } else {
-        std::vector<BindingVertex*> childVerts;
-        childVerts.reserve(cells[cellIndex]->children.size());
-        for (auto& ch : cells[cellIndex]->children) childVerts.push_back(ch.get());
-        ok = mapVirtualCellsToPhysical(childVerts, candidate->children, ctx, false, nullptr);
+        const std::vector<BindingVertex*>& childVerts = cells[cellIndex]->children;
+        ok = mapVirtualCellsToPhysical(childVerts.data(), childVerts.size(), candidate->children,
+                                       ctx, false, nullptr);
         // abandoned branch: unwind its claims exactly, or the honorLinks
         // link constraint would see ghosts on the next branch
         if (!ok) ctx.claimed.unwindTo(attemptCp);
@@ -234,7 +236,7 @@ bool mapVirtualCellsToPhysical(const std::vector<BindingVertex*>& cellsIn,
       if (ok) {
         pickedIdx[cellIndex] = candidateIndex;
         claimCp[cellIndex] = attemptCp;
-        used[candidateIndex] = true;
+        used[candidateIndex] = 1;
         if (cellIndex == n - 1) {
           if (returnPicked) {
             picked->clear();
@@ -248,7 +250,7 @@ bool mapVirtualCellsToPhysical(const std::vector<BindingVertex*>& cellsIn,
     if (candidateIndex == m) {
       cellIndex--;
       if (cellIndex >= 0) {
-        used[pickedIdx[cellIndex]] = false;
+        used[pickedIdx[cellIndex]] = 0;
         ctx.claimed.unwindTo(claimCp[cellIndex]);
         pickedIdx[cellIndex]++;
       }
@@ -273,7 +275,7 @@ bool buddyAlloc(BindingVertex* cell, ChainCellList& freeList, int currentLevel,
   }
   if (currentLevel == cell->cell->level) {
     std::vector<PhysicalCell*> picked;
-    if (mapVirtualCellsToPhysical({cell}, freeList.at(currentLevel), ctx, true, &picked)) {
+    if (mapVirtualCellsToPhysical(&cell, 1, freeList.at(currentLevel), ctx, true, &picked)) {
       for (PhysicalCell* c : picked) freeList.remove(c, currentLevel);
       if (mapDebug())
         fprintf(stderr, "[map]  -> picked %s\n", picked.empty() ? "?" : picked[0]->address.c_str());
@@ -282,17 +284,20 @@ bool buddyAlloc(BindingVertex* cell, ChainCellList& freeList, int currentLevel,
     if (mapDebug()) fprintf(stderr, "[map]  -> no usable candidate at own level\n");
     return false;
   }
-  std::vector<PhysicalCell*> freeCells =
-      getUsablePhysicalCells(freeList.at(currentLevel), 1, ctx, vertexLeafDemand(cell));
+  std::vector<PhysicalCell*> freeCells;
+  getUsablePhysicalCells(freeList.at(currentLevel), 1, ctx, vertexLeafDemand(cell), freeCells);
   if (freeCells.empty()) return false;
   for (PhysicalCell* c : freeCells) {
-    auto saved = freeList.at(currentLevel - 1);
+    // A failing descent leaves the lower level as it found it (it removes
+    // cells only on success and undoes its own splits the same way), so the
+    // children appended here are still its tail: cutting them off restores it.
+    const size_t savedSize = freeList.at(currentLevel - 1).size();
     for (Cell* child : c->children) freeList.add(child, currentLevel - 1);
     if (buddyAlloc(cell, freeList, currentLevel - 1, ctx)) {
       freeList.remove(c, currentLevel);
       return true;
     }
-    freeList.at(currentLevel - 1) = saved;
+    freeList.at(currentLevel - 1).resize(savedSize);
   }
   return false;
 }
@@ -345,7 +350,7 @@ bool safeRelaxedBuddyAlloc(BindingVertex* cell, ChainCellList& freeList,
     auto& cur = freeList.at(currentLevel);
     cur.insert(cur.begin(), splitList.begin(), splitList.end());
     std::vector<PhysicalCell*> picked;
-    if (mapVirtualCellsToPhysical({cell}, cur, ctx, true, &picked)) {
+    if (mapVirtualCellsToPhysical(&cell, 1, cur, ctx, true, &picked)) {
       for (PhysicalCell* c : picked) freeList.remove(c, currentLevel);
       if (mapDebug())
         fprintf(stderr, "[map] safeRelaxed picked %s\n",
@@ -366,11 +371,11 @@ int getLowestFreeCellLevel(const ChainCellList& freeList, int l) {
 }  // namespace
 
 bool HivedCore::mapVirtualPlacementToPhysical(
-    std::vector<BindingVertex*>& preassigned, std::vector<std::vector<BindingVertex*>>& nonPreassigned,
-    ChainCellList freeList, std::map<int, int> freeCellNum,
-    const std::set<std::string>& suggestedNodes, bool ignoreSuggestedNodes,
-    std::unordered_map<VirtualCell*, PhysicalCell*>& bindings, long long minHbmBytes,
-    bool honorLinks, const CleanShapeWorld* world) {
+    const std::vector<BindingVertex*>& preassigned,
+    const std::vector<std::vector<BindingVertex*>>& nonPreassigned, size_t nonPreassignedCount,
+    ChainCellList& freeList, std::map<int, int>& freeCellNum,
+    const std::set<std::string>& suggestedNodes, bool ignoreSuggestedNodes, CellBindings& bindings,
+    long long minHbmBytes, bool honorLinks, const CleanShapeWorld* world) {
   ClaimSet claimed;
   AllocCtx ctx{suggestedNodes, ignoreSuggestedNodes, bindings, claimed,
                minHbmBytes, honorLinks, honorLinks ? world : nullptr};
@@ -378,10 +383,9 @@ bool HivedCore::mapVirtualPlacementToPhysical(
   // seeds `bindings` with bound virtual leaves, which skip the vertex trees)
   // so the link constraint sees the whole gang, not just the new picks
   if (honorLinks) {
-    for (auto& [v, p] : bindings) {
-      (void)v;
+    bindings.forEach([&](VirtualCell*, PhysicalCell* p) {
       if (p != nullptr) markClaimed(ctx, p);
-    }
+    });
   }
   for (BindingVertex* c : preassigned) {
     if (!buddyAlloc(c, freeList, getLowestFreeCellLevel(freeList, c->cell->level), ctx)) {
@@ -392,10 +396,12 @@ bool HivedCore::mapVirtualPlacementToPhysical(
       freeCellNum[c->cell->level]--;
     }
   }
-  for (auto& cells : nonPreassigned) {
+  for (size_t gi = 0; gi < nonPreassignedCount; gi++) {
+    const std::vector<BindingVertex*>& cells = nonPreassigned[gi];
     auto* parentVirtual = static_cast<VirtualCell*>(cells[0]->cell->parent);
     if (parentVirtual == nullptr || parentVirtual->phys == nullptr) return false;
-    if (!mapVirtualCellsToPhysical(cells, parentVirtual->phys->children, ctx, false, nullptr)) {
+    if (!mapVirtualCellsToPhysical(cells.data(), cells.size(), parentVirtual->phys->children, ctx,
+                                   false, nullptr)) {
       return false;
     }
   }
@@ -412,8 +418,6 @@ bool HivedCore::mapVirtualPlacementToPhysical(
     const std::string& chain = preassigned[0]->cell->chain;
     auto avfIt = allVCFreeCellNum_.find(chain);
     if (avfIt != allVCFreeCellNum_.end()) {
-      std::map<int, int> newPre;
-      for (BindingVertex* c : preassigned) newPre[c->cell->level]++;
       int top = freeList.top();
       int producible = 0;
       for (int l = top; l >= kLowestLevel; l--) {
@@ -423,7 +427,9 @@ bool HivedCore::mapVirtualPlacementToPhysical(
         producible += static_cast<int>(freeList.at(l).size());
         auto needIt = avfIt->second.find(l);
         int need = needIt == avfIt->second.end() ? 0 : needIt->second;
-        need -= newPre.count(l) ? newPre[l] : 0;
+        for (BindingVertex* c : preassigned) {
+          if (c->cell->level == l) need--;  // this placement's new preassigned bindings
+        }
         if (producible < need) return false;
       }
     }

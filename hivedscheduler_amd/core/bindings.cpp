@@ -212,6 +212,7 @@ void initNames() {
 // API classes (hivedscheduler_amd.api.types) and constants, looked up once at
 // module initialisation and never released, like the names above.
 struct ApiTypes {
+  PyObject* PodSchedulingSpec;
   PyObject* AffinityGroupSpec;
   PyObject* AffinityGroupMemberSpec;
   PyObject* PodBindInfo;
@@ -226,6 +227,7 @@ ApiTypes T{};
 void initApiTypes() {
   py::module_ types = py::module_::import("hivedscheduler_amd.api.types");
 #define HIVED_TYPE(x) T.x = py::object(types.attr(#x)).release().ptr()
+  HIVED_TYPE(PodSchedulingSpec);
   HIVED_TYPE(AffinityGroupSpec);
   HIVED_TYPE(AffinityGroupMemberSpec);
   HIVED_TYPE(PodBindInfo);
@@ -237,6 +239,43 @@ void initApiTypes() {
   T.one = PyLong_FromLong(1);
   if (T.emptyTuple == nullptr || T.one == nullptr) throw py::error_already_set();
 }
+
+// A request record about to be read field by field: the wire-format dict, or an
+// API object. An object whose type is exactly PodSchedulingSpec,
+// AffinityGroupSpec or AffinityGroupMemberSpec is a plain dataclass instance:
+// its fields sit in its __dict__, and the class holds nothing that outranks
+// them (no property, no __getattribute__), so a field found there is what
+// getattr would give. Its __dict__ is fetched once and the fields are looked up
+// in it by their interned names. A field not found there (deleted from the
+// instance, so that the class default applies) and every other type (a
+// subclass, which may carry properties; any other object) go through getattr.
+class Record {
+ public:
+  explicit Record(py::handle rec) : rec_(rec.ptr()) {
+    if (PyDict_Check(rec_)) {
+      dict_ = rec_;
+      wire_ = true;
+      return;
+    }
+    PyObject* tp = reinterpret_cast<PyObject*>(Py_TYPE(rec_));
+    if (tp == T.PodSchedulingSpec || tp == T.AffinityGroupMemberSpec ||
+        tp == T.AffinityGroupSpec) {
+      dict_ = ownedDict_ = PyObject_GenericGetDict(rec_, nullptr);
+      if (dict_ == nullptr) PyErr_Clear();  // no __dict__ after all: getattr it is
+    }
+  }
+  Record(const Record&) = delete;
+  Record& operator=(const Record&) = delete;
+  ~Record() { Py_XDECREF(ownedDict_); }
+  py::handle object() const { return rec_; }
+
+ private:
+  friend class Field;
+  PyObject* rec_;
+  PyObject* dict_ = nullptr;       // the wire dict or the instance's __dict__
+  PyObject* ownedDict_ = nullptr;  // the reference PyObject_GenericGetDict gave
+  bool wire_ = false;
+};
 
 // One field of a record. A record is either the wire-format dict, read by key
 // (borrowed reference), or an API object (PodSchedulingSpec, PodBindInfo and
@@ -254,6 +293,23 @@ class Field {
       if (p_ == nullptr) throw py::error_already_set();
       owned_ = true;
     }
+  }
+  Field(const Record& rec, PyObject* name) {
+    if (rec.dict_ != nullptr) {
+      p_ = PyDict_GetItemWithError(rec.dict_, name);
+      if (p_ == nullptr && PyErr_Occurred()) throw py::error_already_set();
+      if (rec.wire_) return;
+      if (p_ != nullptr) {
+        // owned, like an attribute: converting a value can run Python code
+        // (__str__, __index__), which may drop the instance's own reference
+        Py_INCREF(p_);
+        owned_ = true;
+        return;
+      }
+    }
+    p_ = PyObject_GetAttr(rec.rec_, name);
+    if (p_ == nullptr) throw py::error_already_set();
+    owned_ = true;
   }
   Field(const Field&) = delete;
   Field& operator=(const Field&) = delete;
@@ -305,15 +361,18 @@ bool toBool(py::handle v) {
   return py::cast<bool>(v);
 }
 
-std::string fstr(py::handle rec, PyObject* name) {
+template <class Rec>
+std::string fstr(const Rec& rec, PyObject* name) {
   Field f(rec, name);
   return f ? toStdString(f.get()) : std::string();
 }
-long long fint(py::handle rec, PyObject* name) {
+template <class Rec>
+long long fint(const Rec& rec, PyObject* name) {
   Field f(rec, name);
   return f ? toLongLong(f.get()) : 0;
 }
-bool fbool(py::handle rec, PyObject* name, bool def) {
+template <class Rec>
+bool fbool(const Rec& rec, PyObject* name, bool def) {
   Field f(rec, name);
   return f ? toBool(f.get()) : def;
 }
@@ -334,7 +393,8 @@ class Items {
   PyObject* seq_;
 };
 
-PodSpec parsePodSpec(py::handle d) {
+PodSpec parsePodSpec(py::handle spec) {
+  Record d(spec);
   PodSpec s;
   s.vc = fstr(d, N.virtualCluster);
   s.priority = static_cast<int>(fint(d, N.priority));
@@ -349,12 +409,14 @@ PodSpec parsePodSpec(py::handle d) {
     throw HivedError::BadRequest("hbmBytesPerCell must be non-negative");
   }
   if (Field ag{d, N.affinityGroup}) {
-    s.groupName = fstr(ag.get(), N.name);
-    if (Field members{ag.get(), N.members}) {
+    Record group(ag.get());
+    s.groupName = fstr(group, N.name);
+    if (Field members{group, N.members}) {
       Items ms(members.get());
       for (Py_ssize_t i = 0; i < ms.size(); i++) {
-        s.groupPodNums[static_cast<int>(fint(ms[i], N.leafCellNumber))] +=
-            static_cast<int>(fint(ms[i], N.podNumber));
+        Record member(ms[i]);
+        s.groupPodNums[static_cast<int>(fint(member, N.leafCellNumber))] +=
+            static_cast<int>(fint(member, N.podNumber));
       }
     }
   }
@@ -518,17 +580,18 @@ py::object defaultAffinityGroup(py::handle podKey, py::handle leafCellNumber) {
 // pass over the PodSchedulingSpec object: the singleton-group default is set
 // on the spec first, then the same checks run in the same order with the same
 // message texts. Nothing of the core is touched before the last check.
-PodSpec parseValidatedPodSpec(py::handle d, py::handle podKey, const std::string& key) {
-  if (PyDict_Check(d.ptr())) {
+PodSpec parseValidatedPodSpec(py::handle spec, py::handle podKey, const std::string& key) {
+  if (PyDict_Check(spec.ptr())) {
     throw py::type_error("schedule_pod validates a PodSchedulingSpec object, not a dict");
   }
+  Record d(spec);
   PodSpec s;
   Field leaf(d, N.leafCellNumber);
   bool defaulted = false;
   {
     Field ag(d, N.affinityGroup);
     if (!ag) {
-      setAttr(d, N.affinityGroup, defaultAffinityGroup(podKey, leaf.get()));
+      setAttr(spec, N.affinityGroup, defaultAffinityGroup(podKey, leaf.get()));
       defaulted = true;
     }
   }
@@ -551,17 +614,19 @@ PodSpec parseValidatedPodSpec(py::handle d, py::handle podKey, const std::string
     s.groupPodNums[s.leafCellNumber] = 1;
   } else {
     Field ag(d, N.affinityGroup);
-    s.groupName = fstr(ag.get(), N.name);
+    Record group(ag.get());
+    s.groupName = fstr(group, N.name);
     if (s.groupName.empty()) throw HivedError::BadRequest("AffinityGroup.Name is empty");
     bool podInGroup = false;
-    if (Field members{ag.get(), N.members}) {
+    if (Field members{group, N.members}) {
       Items ms(members.get());
       for (Py_ssize_t i = 0; i < ms.size(); i++) {
-        long long podNumber = fint(ms[i], N.podNumber);
+        Record member(ms[i]);
+        long long podNumber = fint(member, N.podNumber);
         if (podNumber <= 0) {
           throw HivedError::BadRequest("AffinityGroup.Members has non-positive PodNumber");
         }
-        long long memberLeafNum = fint(ms[i], N.leafCellNumber);
+        long long memberLeafNum = fint(member, N.leafCellNumber);
         if (memberLeafNum <= 0) {
           throw HivedError::BadRequest("AffinityGroup.Members has non-positive LeafCellNumber");
         }
@@ -1049,6 +1114,23 @@ class PyHivedCore {
     core_.deleteAllocatedPod(s, info, podKey);
   }
 
+  // The release of a pod the core itself knows by key; false for a key it does
+  // not know. Like schedulePod this is not under HivedAlgorithm's lock, and the
+  // same argument holds: with a GIL no other thread runs between the lookup
+  // and the last write, because nothing in here runs Python code (reading a
+  // str's UTF-8 does not); without one the CoreSection's mutex covers the same
+  // stretch. The key is copied inside the section, into a buffer that is
+  // reused from call to call.
+  bool deleteAllocatedPodByKey(py::handle podKey) {
+    if (!PyUnicode_Check(podKey.ptr())) throw py::type_error("pod_key must be a str");
+    Py_ssize_t n = 0;
+    const char* utf8 = PyUnicode_AsUTF8AndSize(podKey.ptr(), &n);
+    if (utf8 == nullptr) throw py::error_already_set();
+    CoreSection section(coreMutex_);  // pure C++ in here: no Python call
+    releaseKey_.assign(utf8, static_cast<size_t>(n));
+    return core_.deleteAllocatedPodByKey(releaseKey_);
+  }
+
   py::list getAllAffinityGroups() const {
     py::list out;
     for (auto& [name, g] : core_.groups()) {
@@ -1190,6 +1272,7 @@ class PyHivedCore {
   // every node name, for schedule_pod(suggested_nodes=None)
   std::set<std::string> allNodeSet_;
   CoreMutex coreMutex_;
+  std::string releaseKey_;  // deleteAllocatedPodByKey's key, written under the section
 };
 
 // ---------------------------------------------------------------------------
@@ -1205,6 +1288,8 @@ class PyHivedCore {
 //                commit=False, validate=True)              errors: CoreError
 //   schedule_validated_pod(spec, pod_key, suggested_nodes=None,
 //                phase="Filtering", commit=False)           errors: WebServerError
+//   delete_allocated_pod_by_key(pod_key) -> bool            errors: CoreError
+//   delete_validated_pod_by_key(pod_key) -> bool            errors: WebServerError
 //
 // The second is the first with validate=True and the facade's error protocol:
 // a core error leaves as WebServerError(code, text) with the CoreError as its
@@ -1281,6 +1366,25 @@ PyHivedCore* coreOf(PyObject* self) {
   return py::cast<PyHivedCore*>(py::handle(self));
 }
 
+// The Python error for the C++ exception in flight (call from a catch block).
+void setErrorFromCurrentException(bool facade) {
+  try {
+    throw;
+  } catch (py::error_already_set& e) {
+    e.restore();
+  } catch (const py::builtin_exception& e) {
+    e.set_error();
+  } catch (const HivedError& e) {
+    setCoreError(e, facade);
+  } catch (const std::bad_alloc&) {
+    PyErr_NoMemory();
+  } catch (const std::out_of_range& e) {
+    PyErr_SetString(PyExc_IndexError, e.what());
+  } catch (const std::exception& e) {
+    PyErr_SetString(PyExc_RuntimeError, e.what());
+  }
+}
+
 constexpr int kSchedulePodArgs = 6;
 
 PyObject* schedulePodCall(PyObject* self, PyObject* const* args, Py_ssize_t nargs,
@@ -1336,18 +1440,37 @@ PyObject* schedulePodCall(PyObject* self, PyObject* const* args, Py_ssize_t narg
         ->schedulePod(a[0], a[1], a[2] != nullptr ? a[2] : Py_None, a[3], commit, validate)
         .release()
         .ptr();
-  } catch (py::error_already_set& e) {
-    e.restore();
-  } catch (const py::builtin_exception& e) {
-    e.set_error();
-  } catch (const HivedError& e) {
-    setCoreError(e, facade);
-  } catch (const std::bad_alloc&) {
-    PyErr_NoMemory();
-  } catch (const std::out_of_range& e) {
-    PyErr_SetString(PyExc_IndexError, e.what());
-  } catch (const std::exception& e) {
-    PyErr_SetString(PyExc_RuntimeError, e.what());
+  } catch (...) {
+    setErrorFromCurrentException(facade);
+  }
+  return nullptr;
+}
+
+// delete_allocated_pod_by_key(pod_key) -> bool. One argument, by position or
+// by name; the error protocol is schedule_pod's.
+PyObject* deleteByKeyCall(PyObject* self, PyObject* const* args, Py_ssize_t nargs,
+                          PyObject* kwnames, bool facade) {
+  const char* fn = facade ? "delete_validated_pod_by_key" : "delete_allocated_pod_by_key";
+  Py_ssize_t nkw = kwnames == nullptr ? 0 : PyTuple_GET_SIZE(kwnames);
+  if (nargs + nkw != 1) {
+    PyErr_Format(PyExc_TypeError, "%s() takes exactly one argument 'pod_key' (%zd given)", fn,
+                 nargs + nkw);
+    return nullptr;
+  }
+  if (nkw == 1) {
+    PyObject* name = PyTuple_GET_ITEM(kwnames, 0);
+    int eq = name == N.pod_key ? 1 : PyObject_RichCompareBool(name, N.pod_key, Py_EQ);
+    if (eq < 0) return nullptr;
+    if (eq == 0) {
+      PyErr_Format(PyExc_TypeError, "%s() got an unexpected keyword argument '%U'", fn, name);
+      return nullptr;
+    }
+  }
+  try {
+    if (coreOf(self)->deleteAllocatedPodByKey(args[0])) Py_RETURN_TRUE;
+    Py_RETURN_FALSE;
+  } catch (...) {
+    setErrorFromCurrentException(facade);
   }
   return nullptr;
 }
@@ -1359,6 +1482,15 @@ PyObject* schedulePodEntry(PyObject* self, PyObject* const* args, Py_ssize_t nar
 PyObject* scheduleValidatedPodEntry(PyObject* self, PyObject* const* args, Py_ssize_t nargs,
                                     PyObject* kwnames) {
   return schedulePodCall(self, args, nargs, kwnames, true);
+}
+
+PyObject* deleteByKeyEntry(PyObject* self, PyObject* const* args, Py_ssize_t nargs,
+                           PyObject* kwnames) {
+  return deleteByKeyCall(self, args, nargs, kwnames, false);
+}
+PyObject* deleteValidatedByKeyEntry(PyObject* self, PyObject* const* args, Py_ssize_t nargs,
+                                    PyObject* kwnames) {
+  return deleteByKeyCall(self, args, nargs, kwnames, true);
 }
 
 using FastCallWithKeywords = PyObject* (*)(PyObject*, PyObject* const*, Py_ssize_t, PyObject*);
@@ -1377,6 +1509,16 @@ PyMethodDef directMethods[] = {
      "schedule_validated_pod($self, /, spec, pod_key, suggested_nodes=None, "
      "phase='Filtering', commit=False)\n--\n\n"
      "schedule_pod with validate=True whose core errors leave as\n"
+     "WebServerError(code, text) with the CoreError as __cause__."},
+    {"delete_allocated_pod_by_key", asCFunction(deleteByKeyEntry), METH_FASTCALL | METH_KEYWORDS,
+     "delete_allocated_pod_by_key($self, /, pod_key)\n--\n\n"
+     "Release the allocated pod the core holds under pod_key, as\n"
+     "delete_allocated_pod does for the spec and bind info it was added with.\n"
+     "False, and nothing changed, if the core holds no such pod. Raises CoreError."},
+    {"delete_validated_pod_by_key", asCFunction(deleteValidatedByKeyEntry),
+     METH_FASTCALL | METH_KEYWORDS,
+     "delete_validated_pod_by_key($self, /, pod_key)\n--\n\n"
+     "delete_allocated_pod_by_key whose core errors leave as\n"
      "WebServerError(code, text) with the CoreError as __cause__."},
 };
 
@@ -1440,6 +1582,7 @@ PYBIND11_MODULE(hivedcore, m) {
       .def("schedule_count", &PyHivedCore::scheduleCount)
       .def("check_invariants", &PyHivedCore::checkInvariants)
       .def("debug_counters", &PyHivedCore::debugCounters);
-  // schedule_pod and schedule_validated_pod: hand-written vectorcall methods
+  // schedule_pod, schedule_validated_pod and the two releases by key:
+  // hand-written vectorcall methods
   addDirectMethods(coreClass);
 }

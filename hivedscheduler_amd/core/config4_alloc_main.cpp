@@ -1,7 +1,10 @@
 // Heap allocations of one HivedCore::schedule call, per kind of decision, on
-// the flagship benchmark's stream (config 4, see config4_bench_main.cpp). The
-// global operator new is replaced by a counting one; the count is taken around
-// the schedule call alone, after warm-up, so reusable scratch has its size.
+// the flagship benchmark's stream (config 4, see config4_bench_main.cpp), and
+// of what follows a bind: the commit (addAllocatedPod) and the release, by spec
+// and bind info in even steps and by pod key in odd ones. The global operator
+// new is replaced by a counting one; each count is taken around the one core
+// call, after warm-up, so reusable scratch has its size.
+// -DCONFIG4_NO_RELEASE_BY_KEY drives a core from before the release by key.
 //
 // The aim for a decision that waits because placement failed (reason ending in
 // "when scheduling in physical cluster", or a guaranteed request whose intra-VC
@@ -100,7 +103,15 @@ int main(int argc, char** argv) {
       switch (r.kind) {
         case ScheduleResult::Kind::Bind:
           what = "bind";
-          core.addAllocatedPod(specs[i], r.bindInfo, keys[i]);
+          {
+            long beforeAdd = gAllocations;
+            core.addAllocatedPod(specs[i], r.bindInfo, keys[i]);
+            long add = gAllocations - beforeAdd;
+            if (step >= warmup) {
+              tallies["commit (addAllocatedPod)"].add(add);
+              tallies["bind + commit"].add(during + add);
+            }
+          }
           bound.emplace_back(i, std::move(r.bindInfo));
           break;
         case ScheduleResult::Kind::Preempt:
@@ -115,11 +126,41 @@ int main(int argc, char** argv) {
       }
       if (step >= warmup) tallies[what].add(during);
     }
-    for (auto& [i, info] : bound) core.deleteAllocatedPod(specs[i], info, keys[i]);
+#ifdef CONFIG4_NO_RELEASE_BY_KEY
+    const bool byKey = false;
+#else
+    const bool byKey = step % 2 == 1;
+#endif
+    for (auto& [i, info] : bound) {
+      long before = gAllocations;
+#ifndef CONFIG4_NO_RELEASE_BY_KEY
+      if (byKey) {
+        if (!core.deleteAllocatedPodByKey(keys[i])) {
+          fprintf(stderr, "unknown key %s\n", keys[i].c_str());
+          return 1;
+        }
+      } else
+#endif
+        core.deleteAllocatedPod(specs[i], info, keys[i]);
+      if (step >= warmup) {
+        tallies[byKey ? "release (deleteAllocatedPodByKey)" : "release (deleteAllocatedPod)"].add(
+            gAllocations - before);
+      }
+    }
+#ifndef CONFIG4_NO_RELEASE_BY_KEY
+    // a released key is unknown, and asking again changes nothing
+    for (auto& [i, info] : bound) {
+      (void)info;
+      if (core.deleteAllocatedPodByKey(keys[i])) {
+        fprintf(stderr, "key %s known after its release\n", keys[i].c_str());
+        return 1;
+      }
+    }
+#endif
   }
   checkInvariants(core);
 
-  printf("config4 heap allocations inside HivedCore::schedule: steps=%d warmup=%d\n", steps, warmup);
+  printf("config4 heap allocations per core call: steps=%d warmup=%d\n", steps, warmup);
   for (auto& [what, t] : tallies) {
     printf("  n=%-5ld min=%-3ld max=%-3ld mean=%6.2f  %s\n", t.n, t.lo, t.hi,
            static_cast<double>(t.total) / static_cast<double>(t.n), what.c_str());

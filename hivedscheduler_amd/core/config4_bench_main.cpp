@@ -2,8 +2,11 @@
 // 64 mixed 1/2/4-GPU requests on a 4-node x 8-MI355X cluster with the VC
 // quotas of bench.py. One step = schedule all 64 requests (a bind is committed
 // at once with addAllocatedPod, as the simulation harness does), then delete
-// every bound pod. Reports the p50 of HivedCore::schedule per decision kind and
-// of addAllocatedPod / deleteAllocatedPod.
+// every bound pod: by spec and bind info (deleteAllocatedPod) in even steps, by
+// pod key (deleteAllocatedPodByKey) in odd ones, so both see the same stream.
+// Reports the p50 of HivedCore::schedule per decision kind, of addAllocatedPod
+// and of the two releases. -DCONFIG4_NO_RELEASE_BY_KEY drives a core from
+// before the release by key (every step releases by spec and bind info).
 //
 // This is the "core time" of a decision. bench.py measures the same stream
 // through the pybind11 boundary and the Python facade, so the difference
@@ -69,7 +72,7 @@ int main(int argc, char** argv) {
   }
   const std::set<std::string> suggested;  // ignoreK8sSuggestedNodes = true
 
-  Samples all, waitS, preemptS, bindS, addS, delS;
+  Samples all, waitS, preemptS, bindS, addS, delS, delKeyS;
   std::vector<double> stepMs;
   long binds = 0, waits = 0, preempts = 0;
   for (int step = 0; step < warmup + steps; step++) {
@@ -105,11 +108,24 @@ int main(int argc, char** argv) {
           break;
       }
     }
+#ifdef CONFIG4_NO_RELEASE_BY_KEY
+    const bool byKey = false;
+#else
+    const bool byKey = step % 2 == 1;
+#endif
     for (auto& [i, info] : bound) {
       auto t0 = Clock::now();
-      core.deleteAllocatedPod(specs[i], info, keys[i]);
+#ifndef CONFIG4_NO_RELEASE_BY_KEY
+      if (byKey) {
+        if (!core.deleteAllocatedPodByKey(keys[i])) {
+          fprintf(stderr, "unknown key %s\n", keys[i].c_str());
+          return 1;
+        }
+      } else
+#endif
+        core.deleteAllocatedPod(specs[i], info, keys[i]);
       double us = usSince(t0);
-      if (timed) delS.us.push_back(us);
+      if (timed) (byKey ? delKeyS : delS).us.push_back(us);
     }
     if (timed) stepMs.push_back(usSince(ts) / 1e3);
   }
@@ -124,6 +140,7 @@ int main(int argc, char** argv) {
   bindS.report("schedule -> bind");
   addS.report("addAllocatedPod");
   delS.report("deleteAllocatedPod");
+  delKeyS.report("deleteAllocatedPodByKey");
   std::sort(stepMs.begin(), stepMs.end());
   if (!stepMs.empty()) printf("  ms_per_step p50=%.4f\n", stepMs[stepMs.size() / 2]);
   return 0;

@@ -19,6 +19,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cstddef>
 #include <map>
 #include <memory>
 #include <optional>
@@ -56,6 +57,158 @@ struct HivedError : std::runtime_error {
   static HivedError NotFound(const std::string& msg) { return HivedError(404, msg); }
   static HivedError Internal(const std::string& msg) { return HivedError(500, msg); }
 };
+
+// ---------------------------------------------------------------------------
+// Small containers for the handful of cells one decision touches. The first N
+// entries live inside the object (on the caller's stack or in reused scratch,
+// no heap); a decision that needs more spills into the std container, so large
+// gangs keep their O(1) lookups. Neither promises an iteration order; no
+// caller depends on one.
+// ---------------------------------------------------------------------------
+template <class K, size_t N = 16>
+class SmallPtrSet {
+ public:
+  bool empty() const { return n_ == 0 && big_.empty(); }
+  size_t count(K* k) const {
+    if (!big_.empty()) return big_.count(k);
+    for (size_t i = 0; i < n_; i++) {
+      if (inl_[i] == k) return 1;
+    }
+    return 0;
+  }
+  void insert(K* k) {
+    if (count(k)) return;
+    if (big_.empty() && n_ < N) {
+      inl_[n_++] = k;
+      return;
+    }
+    for (size_t i = 0; i < n_; i++) big_.insert(inl_[i]);
+    n_ = 0;
+    big_.insert(k);
+  }
+  void erase(K* k) {
+    if (!big_.empty()) {
+      big_.erase(k);
+      return;
+    }
+    for (size_t i = 0; i < n_; i++) {
+      if (inl_[i] == k) {
+        inl_[i] = inl_[--n_];
+        return;
+      }
+    }
+  }
+
+ private:
+  K* inl_[N];
+  size_t n_ = 0;
+  std::unordered_set<K*> big_;
+};
+
+template <class K, class V, size_t N = 32>
+class SmallPtrMap {
+ public:
+  bool empty() const { return n_ == 0 && big_.empty(); }
+  // the value of k, or nullptr
+  V* find(K* k) {
+    if (!big_.empty()) {
+      auto it = big_.find(k);
+      return it == big_.end() ? nullptr : &it->second;
+    }
+    for (size_t i = 0; i < n_; i++) {
+      if (inl_[i].first == k) return &inl_[i].second;
+    }
+    return nullptr;
+  }
+  const V* find(K* k) const { return const_cast<SmallPtrMap*>(this)->find(k); }
+  size_t count(K* k) const { return find(k) != nullptr ? 1 : 0; }
+  V& at(K* k) {
+    V* v = find(k);
+    if (v == nullptr) throw std::out_of_range("SmallPtrMap::at");
+    return *v;
+  }
+  V& operator[](K* k) {
+    if (V* v = find(k)) return *v;
+    if (big_.empty() && n_ < N) {
+      inl_[n_] = {k, V{}};
+      return inl_[n_++].second;
+    }
+    for (size_t i = 0; i < n_; i++) big_.emplace(inl_[i].first, inl_[i].second);
+    n_ = 0;
+    return big_[k];
+  }
+  void erase(K* k) {
+    if (!big_.empty()) {
+      big_.erase(k);
+      return;
+    }
+    for (size_t i = 0; i < n_; i++) {
+      if (inl_[i].first == k) {
+        inl_[i] = inl_[--n_];
+        return;
+      }
+    }
+  }
+  void clear() {
+    n_ = 0;
+    big_.clear();
+  }
+  template <class F>
+  void forEach(F f) const {
+    for (size_t i = 0; i < n_; i++) f(inl_[i].first, inl_[i].second);
+    for (auto& [k, v] : big_) f(k, v);
+  }
+
+ private:
+  std::pair<K*, V> inl_[N];
+  size_t n_ = 0;
+  std::unordered_map<K*, V> big_;
+};
+
+// n values of a trivially copyable T, inline up to N, on the heap beyond.
+template <class T, size_t N = 16>
+class SmallBuf {
+ public:
+  explicit SmallBuf(size_t n, const T& init = T{}) : n_(n) {
+    if (n > N) {
+      heap_.assign(n, init);
+      p_ = heap_.data();
+    } else {
+      p_ = inl_;
+      for (size_t i = 0; i < n; i++) inl_[i] = init;
+    }
+  }
+  SmallBuf(const SmallBuf&) = delete;
+  SmallBuf& operator=(const SmallBuf&) = delete;
+  T& operator[](size_t i) { return p_[i]; }
+  const T& operator[](size_t i) const { return p_[i]; }
+  T* begin() { return p_; }
+  T* end() { return p_ + n_; }
+  size_t size() const { return n_; }
+
+ private:
+  T inl_[N];
+  std::vector<T> heap_;
+  T* p_;
+  size_t n_;
+};
+
+// Stable sort without std::stable_sort's heap-allocated merge buffer while
+// the range is short (an insertion sort, which is stable too, so both give
+// the same order).
+template <class It, class Less>
+void stableSortSmall(It first, It last, Less less) {
+  if (last - first > 16) {
+    std::stable_sort(first, last, less);
+    return;
+  }
+  for (It i = first == last ? last : first + 1; i != last; ++i) {
+    auto moving = *i;
+    It j = i;
+    for (; j != first && less(moving, *(j - 1)); --j) *j = *(j - 1);
+    *j = moving;
+  }
+}
 
 // ---------------------------------------------------------------------------
 // Cell model
@@ -397,10 +550,14 @@ struct IntraVCScheduler {
 
 // A vertex in a cell-binding path: a tree of unbound virtual cells that need
 // physical bindings, preserving intra-cell topology.
+// The vertices of one mapping attempt belong to HivedCore::MapScratch.
 struct BindingVertex {
   VirtualCell* cell = nullptr;
-  std::vector<std::unique_ptr<BindingVertex>> children;
+  std::vector<BindingVertex*> children;
 };
+
+// virtual cell -> the physical cell one mapping attempt gives it
+using CellBindings = SmallPtrMap<VirtualCell, PhysicalCell*, 32>;
 
 // ---------------------------------------------------------------------------
 // The algorithm facade
@@ -431,6 +588,11 @@ class HivedCore {
   void deleteUnallocatedPod(const PodSpec& s, const std::string& podKey);
   void addAllocatedPod(const PodSpec& s, const BindInfo& info, const std::string& podKey);
   void deleteAllocatedPod(const PodSpec& s, const BindInfo& info, const std::string& podKey);
+  // deleteAllocatedPod for the spec and bind info the pod was added with, found
+  // through podIndex_ instead of being handed back. Answers false, and changes
+  // nothing, for a key the index does not hold (never added, already released,
+  // or added to a core that has since been rebuilt and not yet replayed).
+  bool deleteAllocatedPodByKey(const std::string& podKey);
 
   // -- inspect --
   const std::map<std::string, std::unique_ptr<Group>>& groups() const { return groups_; }
@@ -528,8 +690,14 @@ class HivedCore {
   std::map<std::string, Placement<VirtualCell>> tryLazyPreempt(const Placement<VirtualCell>& p,
                                                                const std::string& groupName);
 
+  // --- allocated-pod slots and their key index ---
+  void setPodSlot(Group* g, int leafCellNum, int podIndex, bool releasable,
+                  const std::string& podKey, const BindInfo& info);
+  void clearPodSlot(Group* g, int leafCellNum, int podIndex);
+  void eraseGroup(Group* g);
+
   // --- group lifecycle ---
-  void createAllocatedGroup(const PodSpec& s, const BindInfo& info, const std::string& podKey);
+  Group* createAllocatedGroup(const PodSpec& s, const BindInfo& info, const std::string& podKey);
   void deleteAllocatedGroup(Group* g, const std::string& podKey);
   void createPreemptingGroup(const PodSpec& s, const Placement<PhysicalCell>& phys,
                              const Placement<VirtualCell>& virt, const std::string& podKey);
@@ -555,14 +723,51 @@ class HivedCore {
   int addCellToFreeList(PhysicalCell* c);
 
   // --- mapping virtual -> physical (buddy allocation) ---
-  bool mapVirtualPlacementToPhysical(std::vector<BindingVertex*>& preassigned,
-                                     std::vector<std::vector<BindingVertex*>>& nonPreassigned,
-                                     ChainCellList freeList, std::map<int, int> freeCellNum,
+  // freeList / freeCellNum: the caller's working copies of the chain's free
+  // list and allVCFreeCellNum_ entry; both are consumed. Of nonPreassigned the
+  // first nonPreassignedCount groups count.
+  bool mapVirtualPlacementToPhysical(const std::vector<BindingVertex*>& preassigned,
+                                     const std::vector<std::vector<BindingVertex*>>& nonPreassigned,
+                                     size_t nonPreassignedCount, ChainCellList& freeList,
+                                     std::map<int, int>& freeCellNum,
                                      const std::set<std::string>& suggestedNodes,
-                                     bool ignoreSuggestedNodes,
-                                     std::unordered_map<VirtualCell*, PhysicalCell*>& bindings,
+                                     bool ignoreSuggestedNodes, CellBindings& bindings,
                                      long long minHbmBytes = 0, bool honorLinks = false,
                                      const CleanShapeWorld* world = nullptr);
+
+  // What one mapping attempt of scheduleGuaranteedGroup builds and throws
+  // away, kept between attempts so that its vectors and vertices are reused:
+  // an attempt starts with reset(), attempts never nest (nothing an attempt
+  // calls schedules), and nothing in here is read after the attempt ends.
+  struct MapScratch {
+    std::vector<std::unique_ptr<BindingVertex>> vertexPool;
+    size_t verticesUsed = 0;
+    std::vector<BindingVertex*> preassigned;
+    std::vector<std::vector<BindingVertex*>> nonPreassigned;  // first ...Used count
+    size_t nonPreassignedUsed = 0;
+    std::vector<VirtualCell*> path;
+    ChainCellList freeList;
+    std::map<int, int> freeCellNum;
+    void reset() {
+      verticesUsed = 0;
+      preassigned.clear();
+      nonPreassignedUsed = 0;
+    }
+    BindingVertex* newVertex(VirtualCell* cell) {
+      if (verticesUsed == vertexPool.size()) vertexPool.push_back(std::make_unique<BindingVertex>());
+      BindingVertex* v = vertexPool[verticesUsed++].get();
+      v->cell = cell;
+      v->children.clear();
+      return v;
+    }
+    std::vector<BindingVertex*>& newNonPreassignedGroup() {
+      if (nonPreassignedUsed == nonPreassigned.size()) nonPreassigned.emplace_back();
+      std::vector<BindingVertex*>& g = nonPreassigned[nonPreassignedUsed++];
+      g.clear();
+      return g;
+    }
+  };
+  MapScratch mapScratch_;
 
  public:
   // state (public for inspect/bindings simplicity; external mutation forbidden)
@@ -573,6 +778,19 @@ class HivedCore {
   std::map<std::string, IntraVCScheduler> vcSchedulers_;
   std::map<std::string, TopoScheduler> opportunisticSchedulers_;
   std::map<std::string, std::unique_ptr<Group>> groups_;
+  // pod key -> the allocatedPods slot that holds it. Kept by setPodSlot /
+  // clearPodSlot / eraseGroup, the only writers of a slot's `present`, so it
+  // holds exactly the present slots (one entry per key: a key added again
+  // points at the slot of its latest add). `releasable` is false for a pod
+  // whose own bind info does not name its placement; deleteAllocatedPod leaves
+  // such a pod alone, and so does the release by key.
+  struct PodSlotRef {
+    Group* group = nullptr;
+    int leafCellNum = 0;
+    int podIndex = 0;
+    bool releasable = true;
+  };
+  std::unordered_map<std::string, PodSlotRef> podIndex_;
 
   // vc -> chain -> level -> free preassigned cell count
   std::map<std::string, std::map<std::string, std::map<int, int>>> vcFreeCellNum_;

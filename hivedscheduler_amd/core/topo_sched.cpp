@@ -60,7 +60,8 @@ int badLinksUnderOf(Cell* c) {
 }
 
 struct PickSession {
-  std::unordered_set<Cell*> taken;
+  // leaves picked so far in this session (inline for the usual few)
+  SmallPtrSet<Cell> taken;
   // leaves excluded for THIS request because their bad-link peer may be
   // co-placed (gang-wide: one session spans all pods of the gang)
   std::unordered_set<Cell*> excluded;
@@ -416,7 +417,7 @@ void pickLeaves(Cell* cell, int q, int p, PickSession& s, std::vector<Cell*>& ou
     return;
   }
   int n = static_cast<int>(cell->children.size());
-  std::vector<std::pair<int, int>> av(n);
+  SmallBuf<std::pair<int, int>, 8> av(n);
   for (int i = 0; i < n; i++) av[i] = availLeaves(cell->children[i], p, s);
 
   // A single child can hold the whole request: descend into the one that
@@ -459,10 +460,10 @@ void pickLeaves(Cell* cell, int q, int p, PickSession& s, std::vector<Cell*>& ou
   }
   // This cell is the LCA: drain children largest-available first so the fewest
   // subtrees are touched (keeps fragmentation low for later requests).
-  std::vector<int> order(n);
+  SmallBuf<int, 8> order(n);
   for (int i = 0; i < n; i++) order[i] = i;
-  std::stable_sort(order.begin(), order.end(),
-                   [&](int a, int b) { return av[a].first > av[b].first; });
+  stableSortSmall(order.begin(), order.end(),
+                  [&](int a, int b) { return av[a].first > av[b].first; });
   int remaining = q;
   for (int idx : order) {
     if (remaining == 0) break;
@@ -882,11 +883,14 @@ bool TopoScheduler::tryScheduleAtPriority(const std::vector<int>& sortedLeafNums
     // With a precomputed clean-shape world the exclusions are already
     // global (world.excluded), so the per-node analysis is skipped.
     if (cleanWorld == nullptr) {
-      std::map<int, int> nodeDemand;  // nodeIndex -> total gang leaves
-      for (size_t i = 0; i < sortedLeafNums.size(); i++) {
-        nodeDemand[pickedNodeIndices[i]] += sortedLeafNums[i];
-      }
-      for (auto& [nodeIndex, demand] : nodeDemand) {
+      // total gang leaves per picked node. Both loops above hand out node
+      // indices in non-decreasing pod order, so the pods of one node are a run.
+      for (size_t i = 0; i < sortedLeafNums.size();) {
+        const int nodeIndex = pickedNodeIndices[i];
+        int demand = 0;
+        for (; i < sortedLeafNums.size() && pickedNodeIndices[i] == nodeIndex; i++) {
+          demand += sortedLeafNums[i];
+        }
         if (demand >= 2) applyLinkExclusions(cv[nodeIndex].c, demand, priority, session);
       }
     }

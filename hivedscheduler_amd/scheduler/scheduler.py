@@ -118,12 +118,16 @@ class HivedScheduler:
             st = self.pod_statuses.pop(uid, None)
             if podutil.is_bound(pod) or (st is not None and st.state in (POD_BINDING, POD_BOUND)):
                 try:
-                    spec = podutil.extract_pod_scheduling_spec(pod)
-                    if st is not None and st.pod_bind_info is not None:
-                        info = st.pod_bind_info
-                    else:
-                        info = podutil.extract_pod_bind_info(pod)
-                    self.algorithm.delete_allocated_pod(spec, info, key)
+                    # by key where the core knows the pod; from the pod's own
+                    # annotations where it does not (e.g. deleted before the
+                    # replay after a restart reached it)
+                    if not self.algorithm.delete_allocated_pod_by_key(key):
+                        spec = podutil.extract_pod_scheduling_spec(pod)
+                        if st is not None and st.pod_bind_info is not None:
+                            info = st.pod_bind_info
+                        else:
+                            info = podutil.extract_pod_bind_info(pod)
+                        self.algorithm.delete_allocated_pod(spec, info, key)
                 except WebServerError as e:
                     log.warning("[%s]: delete allocated pod failed: %s", key, e)
             else:

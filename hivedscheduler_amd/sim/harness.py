@@ -125,7 +125,10 @@ class SimScheduler:
 
     def delete_pod(self, key: str) -> None:
         spec, info = self.pods.pop(key)
-        self.alg.delete_allocated_pod(spec, info, key)
+        # the core knows its allocated pods by key; the spec / info form is
+        # for a pod it does not know (one it never saw committed)
+        if not self.alg.delete_allocated_pod_by_key(key):
+            self.alg.delete_allocated_pod(spec, info, key)
 
     def delete_unallocated(self, key: str, spec: PodSchedulingSpec) -> None:
         validate_pod_scheduling_spec(spec, key)
