@@ -33,6 +33,15 @@ def main() -> None:
                          "(on deep sweeps); 0 = never")
     ap.add_argument("--lds-march", action="store_true",
                     help="with --local: also run the full-LDS march")
+    ap.add_argument("--hbm-march-every", type=int, default=0,
+                    help="HBM march (both polarities, fault location, per-XCD bandwidth; "
+                         "holds up to 16 GiB) every N sweeps (on deep sweeps); 0 = never")
+    ap.add_argument("--hbm-march", action="store_true",
+                    help="with --local: also run the HBM march")
+    ap.add_argument("--min-xcd-ratio", type=float, default=None,
+                    help="mark a GPU bad when one XCD's march read rate is below this "
+                         "fraction of the median XCD (no default: measure your fleet, see "
+                         "docs/user-manual.md)")
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
@@ -45,7 +54,8 @@ def main() -> None:
         report = collect_node_health(deep=True, sweep=True,
                                      probe_pairs=args.probe_pairs, burn=args.burn,
                                      min_mfma_tflops=args.min_mfma_tflops,
-                                     lds_march=args.lds_march)
+                                     lds_march=args.lds_march, hbm_march=args.hbm_march,
+                                     min_xcd_ratio=args.min_xcd_ratio)
         if args.p2p_matrix:
             try:
                 m = p2p_link_matrix()
@@ -64,7 +74,9 @@ def main() -> None:
                             p2p_matrix_every=args.p2p_matrix_every,
                             burn_every=args.burn_every,
                             min_mfma_tflops=args.min_mfma_tflops,
-                            lds_march_every=args.lds_march_every)
+                            lds_march_every=args.lds_march_every,
+                            hbm_march_every=args.hbm_march_every,
+                            min_xcd_ratio=args.min_xcd_ratio)
     if args.once:
         import json
 

@@ -51,6 +51,8 @@ def collect_node_health(
     burn: bool = False,
     min_mfma_tflops: Optional[float] = None,
     lds_march: bool = False,
+    hbm_march: bool = False,
+    min_xcd_ratio: Optional[float] = None,
 ) -> dict:
     """One health sweep over all visible GPUs. deep=True also runs the HIP
     kernels (HBM + MFMA); sweep=True adds the 16 GiB HBM stuck-bit pattern
@@ -68,6 +70,17 @@ def collect_node_health(
     `lds_bad_cus` (the CUs whose LDS read back wrong; a key of its own, so
     `bad_cus` keeps meaning the burn-in's), and a failed march marks the leaf
     bad.
+
+    hbm_march=True (with deep) adds the HBM march (both bit polarities, 16 B
+    accesses, fault location, bandwidth per XCD): per GPU it records
+    `hbm_march_ok`, `hbm_march_errors`, `hbm_bad_bits`,
+    `hbm_first_bad_offset` (absent when nothing was wrong), `xcd_gbps` (the
+    verify rate of each XCD, ordered by XCC id) and `slow_xcds`. A failed
+    march marks the leaf bad; one skipped for lack of free memory does not.
+    min_xcd_ratio marks a GPU bad when one XCD reads below that fraction of
+    the median XCD; there is no default because the healthy spread is
+    site-measured (docs/user-manual.md). Like the stuck-bit scan it holds up
+    to 16 GiB while it runs, and the same warning applies.
 
     The stuck-bit scan transiently holds up to 16 GiB of HBM; on a GPU
     running tenant jobs this can make the tenant's own allocations fail.
@@ -96,6 +109,8 @@ def collect_node_health(
                 kwargs = {"burn": True} if burn else {}
                 if lds_march:
                     kwargs["lds_march"] = True
+                if hbm_march:
+                    kwargs["hbm_march"] = True
                 rep = gpu_health_report(i, quick=True, deep=sweep, bw_samples=3, **kwargs)
                 report["gpus"][str(i)].update(
                     hbm_gbps=round(rep["hbm_gbps"], 1),
@@ -128,6 +143,24 @@ def collect_node_health(
                                      for c in m["bad_cus"]],
                     )
                     if not m["ok"] or m["bad_cus"]:
+                        report["gpus"][str(i)]["healthy"] = False
+                if hbm_march:
+                    from ..ops import hbm_slow_xcds
+
+                    h = rep["hbm_march"]
+                    slow = hbm_slow_xcds(h["xcds"], min_xcd_ratio)
+                    report["gpus"][str(i)].update(
+                        hbm_march_ok=bool(h["ok"] and not slow),
+                        hbm_march_errors=int(h["errors"]),
+                        hbm_bad_bits=list(h["bad_bits"]),
+                        xcd_gbps=[round(x["verify_gbps"], 1)
+                                  for x in sorted(h["xcds"], key=lambda x: x["xcc"])],
+                        slow_xcds=slow,
+                    )
+                    if h["first_bad"] is not None:
+                        report["gpus"][str(i)]["hbm_first_bad_offset"] = int(
+                            h["first_bad"]["offset"])
+                    if not h["skipped"] and (not h["ok"] or slow):
                         report["gpus"][str(i)]["healthy"] = False
             except Exception as e:
                 report["gpus"][str(i)].update(healthy=False, error=str(e)[:200])
@@ -201,7 +234,8 @@ class NodeHealthAgent:
                  interval_s: float = 60.0, deep_every: int = 10,
                  sweep_every: int = 60, probe_pairs: bool = True,
                  p2p_matrix_every: int = 30, burn_every: int = 0,
-                 min_mfma_tflops: Optional[float] = None, lds_march_every: int = 0):
+                 min_mfma_tflops: Optional[float] = None, lds_march_every: int = 0,
+                 hbm_march_every: int = 0, min_xcd_ratio: Optional[float] = None):
         self.scheduler_url = scheduler_url.rstrip("/")
         self.node_name = node_name or socket.gethostname()
         self.interval_s = interval_s
@@ -221,6 +255,13 @@ class NodeHealthAgent:
         # full-LDS march cadence, same pattern; 0 = never (about a millisecond
         # per GPU, but it takes every CU's whole LDS while it runs)
         self.lds_march_every = lds_march_every
+        # HBM march cadence, same pattern; 0 = never. Like the stuck-bit sweep
+        # it transiently holds up to 16 GiB of HBM (and takes about four times
+        # as long: two polarities, written and verified), which on a GPU
+        # running tenant jobs can make the tenant's own allocations fail:
+        # keep it on a low-frequency cadence and prefer idle GPUs
+        self.hbm_march_every = hbm_march_every
+        self.min_xcd_ratio = min_xcd_ratio
         self._rounds = 0
 
     def post_report(self, report: dict) -> bool:
@@ -270,12 +311,15 @@ class NodeHealthAgent:
         matrix = (self._rounds % self.p2p_matrix_every) == 0
         burn = self.burn_every > 0 and (self._rounds % self.burn_every) == 0
         march = self.lds_march_every > 0 and (self._rounds % self.lds_march_every) == 0
+        hbm = self.hbm_march_every > 0 and (self._rounds % self.hbm_march_every) == 0
         self._rounds += 1
         kwargs = {}
         if burn and deep:
             kwargs = {"burn": True, "min_mfma_tflops": self.min_mfma_tflops}
         if march and deep:
             kwargs["lds_march"] = True
+        if hbm and deep:
+            kwargs.update(hbm_march=True, min_xcd_ratio=self.min_xcd_ratio)
         report = collect_node_health(deep=deep, probe_pairs=self.probe_pairs and deep,
                                      sweep=sweep and deep, **kwargs)
         report["node"] = self.node_name

@@ -11,6 +11,9 @@
 //                the kernel; TFLOP/s plus the CU of any wave that was wrong
 //  - lds_march:  all 160 KiB of every CU's LDS, both bit polarities, narrow
 //                and wide reads, timed; the CU, word and bits of any mismatch
+//  - hbm_march:  a bounded span of HBM, both bit polarities, 16 B per lane,
+//                values unique across the sweep; the offset, bits and direction
+//                of any mismatch, and a bandwidth per XCD from device clocks
 //  - p2p copy:   xGMI link bandwidth between two GPUs (expected ~153 GB/s per
 //                link per direction); a degraded link marks the PAIR cell bad
 //
@@ -20,6 +23,8 @@
 #include <ATen/cuda/CUDAContext.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstring>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -1009,6 +1014,367 @@ py::dict hbm_sweep(long max_gib, long chunk_gib, long seed) {
   return d;
 }
 
+// ---------------------------------------------------------------------------
+// HBM march: a timed write/read-verify of a bounded span of HBM in both bit
+// polarities through the widest access path, with the location, bits and
+// direction of any mismatch recorded, and with each workgroup's XCD and
+// realtime-clock span recorded so the host can give a bandwidth per XCD.
+// hbm_sweep above returns one error count from one polarity through 8-byte
+// accesses, and seeds every chunk separately.
+//
+// Pattern: p(seed, g) = mix64(seed ^ g), g the GLOBAL qword index in the whole
+// sweep (chunk byte offset / 8 + index inside the chunk). For a fixed seed
+// mix64(seed ^ .) is a bijection on 64 bits, so all values of a sweep are
+// distinct and an address-decoder alias inside or across chunks reads back as
+// a data mismatch. Pass 0 writes p, pass 1 writes ~p; each write launch is
+// followed by a verify launch of its own (the kernel boundary provides the
+// visibility; no workgroup waits for another).
+//
+// Geometry: a tile is 16 KiB = 256 threads x 16 B x 4 accesses; in access k
+// thread t touches the 16 B at tile_base + (k*256 + t)*16, so each wave
+// instruction covers 1 KiB contiguous. Workgroup b handles tiles b, b+blocks,
+// b+2*blocks, ... of the chunk: a static assignment, so a slow XCD finishes
+// late instead of handing its work to a fast one. Chunks are a multiple of
+// 16 KiB, so there is no tail. All index arithmetic is 64-bit.
+//
+// Checked in the gfx950 disassembly: the write loop issues four
+// global_store_dwordx4 per tile, the verify loop four global_load_dwordx4
+// (all four issued before the first compare), the records leave as
+// global_store_dwordx4, and wall_clock64() is s_memrealtime (100 MHz).
+//
+// Per-workgroup record, 16 x int32, four int4 vector stores by thread 0 after
+// a shuffle reduction per wave and a four-entry LDS reduction across waves
+// (a workgroup that received no tile still writes one):
+//   [0]      (XCC_ID<<16)|HW_ID of wave 0 (the cu_coverage_kernel encoding)
+//   [1]      tiles this workgroup processed
+//   [2],[3]  realtime clock before the first access, lo / hi
+//   [4],[5]  realtime clock after the last access has completed and the
+//            workgroup has passed a barrier, lo / hi
+//   verify only (the write kernel leaves these 0):
+//   [6],[7]   mismatched qwords, lo / hi
+//   [8],[9]   lowest mismatching global qword index, lo / hi (-1,-1 if none)
+//   [10],[11] dropped mask: OR of (want & ~got)
+//   [12],[13] raised mask:  OR of (got & ~want)
+//   [14],[15] sum mod 2^64 of every qword read
+//
+// Bad-location log: [max_log, 4] int64 rows {global qword index, pass, want,
+// got} plus a device counter. A thread appends at most one row per launch, for
+// its first mismatch: it takes a slot with atomicAdd and writes only if the
+// slot is < max_log, so a wholly broken chunk costs at most blocks x 256
+// atomics per launch. The order is not deterministic; the host sorts.
+//
+// hbm_march_poke_kernel: one thread xors one bit of one qword of the sweep's
+// own allocation, launched on the same stream between the write and the
+// verify launch of one pass. A plain store that sends a known one-bit fault
+// through the real verify path on healthy hardware.
+// ---------------------------------------------------------------------------
+constexpr int HBM_MARCH_THREADS = 256;
+constexpr int HBM_MARCH_ACCESSES = 4;
+constexpr long HBM_MARCH_TILE_BYTES = 16384;
+constexpr long HBM_MARCH_TILE_QWORDS = HBM_MARCH_TILE_BYTES / 8;
+constexpr long HBM_MARCH_TILE_VECS = HBM_MARCH_TILE_BYTES / 16;
+static_assert(HBM_MARCH_THREADS * 16 * HBM_MARCH_ACCESSES == HBM_MARCH_TILE_BYTES,
+              "a tile is threads x 16 B x accesses");
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+
+__device__ __forceinline__ unsigned long long hbm_march_shfl_xor(unsigned long long v, int off) {
+  int lo = __shfl_xor((int)(unsigned)v, off);
+  int hi = __shfl_xor((int)(unsigned)(v >> 32), off);
+  return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
+}
+
+__device__ __forceinline__ int4 hbm_march_pair(unsigned long long a, unsigned long long b) {
+  return make_int4((int)(unsigned)a, (int)(unsigned)(a >> 32), (int)(unsigned)b,
+                   (int)(unsigned)(b >> 32));
+}
+
+__global__ void __launch_bounds__(HBM_MARCH_THREADS)
+hbm_march_write_kernel(u32x4* __restrict__ p, unsigned long long chunk_qword_base, long tiles,
+                       unsigned long long seed, int invert, int4* __restrict__ records) {
+  const int t = threadIdx.x;
+  unsigned hwid, xcc;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  const unsigned long long inv = invert ? ~0ull : 0ull;
+  const unsigned long long start = wall_clock64();
+  asm volatile("" ::: "memory");
+  int done = 0;
+  for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    u32x4* tp = p + tile * HBM_MARCH_TILE_VECS + t;
+    const unsigned long long g0 =
+        chunk_qword_base + (unsigned long long)tile * HBM_MARCH_TILE_QWORDS + 2ull * t;
+    u32x4 val[HBM_MARCH_ACCESSES];
+#pragma unroll
+    for (int k = 0; k < HBM_MARCH_ACCESSES; k++) {
+      const unsigned long long g = g0 + 2ull * k * HBM_MARCH_THREADS;
+      const unsigned long long a = mix64(seed ^ g) ^ inv;
+      const unsigned long long b = mix64(seed ^ (g + 1)) ^ inv;
+      val[k] = (u32x4){(unsigned)a, (unsigned)(a >> 32), (unsigned)b, (unsigned)(b >> 32)};
+    }
+#pragma unroll
+    for (int k = 0; k < HBM_MARCH_ACCESSES; k++) tp[k * HBM_MARCH_THREADS] = val[k];
+    done++;
+  }
+  // every wave waits for its own stores, then the barrier: past it, all of the
+  // workgroup's stores have completed
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  const unsigned long long end = wall_clock64();
+  if (t == 0) {
+    int4* rec = records + 4 * (long)blockIdx.x;
+    rec[0] = make_int4((int)((xcc << 16) | (hwid & 0xffff)), done, (int)(unsigned)start,
+                       (int)(unsigned)(start >> 32));
+    // the empty asm keeps each a global_store_dwordx4 of its own: the compiler
+    // otherwise regroups the constant words across the four stores
+    asm volatile("" ::: "memory");
+    rec[1] = make_int4((int)(unsigned)end, (int)(unsigned)(end >> 32), 0, 0);
+    asm volatile("" ::: "memory");
+    rec[2] = make_int4(0, 0, 0, 0);
+    asm volatile("" ::: "memory");
+    rec[3] = make_int4(0, 0, 0, 0);
+  }
+}
+
+struct HbmMarchState {
+  unsigned long long mismatched, first, dropped, raised, sum;
+};
+
+// a thread visits its qwords in ascending global order, so the first mismatch
+// it sees in a launch is its lowest
+__device__ __forceinline__ void hbm_march_compare(HbmMarchState& s, unsigned long long got,
+                                                  unsigned long long want, unsigned long long g,
+                                                  int pass, long long* __restrict__ log,
+                                                  unsigned long long* __restrict__ log_count,
+                                                  int max_log) {
+  s.sum += got;
+  const unsigned long long diff = got ^ want;
+  if (diff != 0) {  // not taken on healthy memory
+    if (s.mismatched == 0) {
+      s.first = g;
+      const unsigned long long slot = atomicAdd(log_count, 1ull);
+      if (slot < (unsigned long long)max_log) {
+        long long* row = log + 4 * slot;
+        row[0] = (long long)g;
+        row[1] = pass;
+        row[2] = (long long)want;
+        row[3] = (long long)got;
+      }
+    }
+    s.mismatched++;
+    s.dropped |= want & diff;
+    s.raised |= got & diff;
+  }
+}
+
+__global__ void __launch_bounds__(HBM_MARCH_THREADS)
+hbm_march_verify_kernel(const u32x4* __restrict__ p, unsigned long long chunk_qword_base,
+                        long tiles, unsigned long long seed, int invert, int pass,
+                        int4* __restrict__ records, long long* __restrict__ log,
+                        unsigned long long* __restrict__ log_count, int max_log) {
+  __shared__ unsigned long long red[HBM_MARCH_THREADS / 64][5];
+  const int t = threadIdx.x;
+  unsigned hwid, xcc;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  const unsigned long long inv = invert ? ~0ull : 0ull;
+  HbmMarchState s = {0ull, ~0ull, 0ull, 0ull, 0ull};
+  const unsigned long long start = wall_clock64();
+  asm volatile("" ::: "memory");
+  int done = 0;
+  for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const u32x4* tp = p + tile * HBM_MARCH_TILE_VECS + t;
+    const unsigned long long g0 =
+        chunk_qword_base + (unsigned long long)tile * HBM_MARCH_TILE_QWORDS + 2ull * t;
+    // all four loads of the tile are in flight before the first compare
+    u32x4 got[HBM_MARCH_ACCESSES];
+#pragma unroll
+    for (int k = 0; k < HBM_MARCH_ACCESSES; k++) got[k] = tp[k * HBM_MARCH_THREADS];
+#pragma unroll
+    for (int k = 0; k < HBM_MARCH_ACCESSES; k++) {
+      const unsigned long long g = g0 + 2ull * k * HBM_MARCH_THREADS;
+      const unsigned long long a = ((unsigned long long)got[k].y << 32) | got[k].x;
+      const unsigned long long b = ((unsigned long long)got[k].w << 32) | got[k].z;
+      hbm_march_compare(s, a, mix64(seed ^ g) ^ inv, g, pass, log, log_count, max_log);
+      hbm_march_compare(s, b, mix64(seed ^ (g + 1)) ^ inv, g + 1, pass, log, log_count, max_log);
+    }
+    done++;
+  }
+  // the compares consumed every load, so the last access has completed here
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  const unsigned long long end = wall_clock64();
+  // opaque to the scheduler: the reduction stays behind the clock read
+  asm volatile("" : "+v"(s.mismatched), "+v"(s.first), "+v"(s.dropped), "+v"(s.raised),
+               "+v"(s.sum));
+  for (int off = 32; off > 0; off >>= 1) {
+    s.mismatched += hbm_march_shfl_xor(s.mismatched, off);
+    s.first = min(s.first, hbm_march_shfl_xor(s.first, off));
+    s.dropped |= hbm_march_shfl_xor(s.dropped, off);
+    s.raised |= hbm_march_shfl_xor(s.raised, off);
+    s.sum += hbm_march_shfl_xor(s.sum, off);
+  }
+  if ((t & 63) == 0) {
+    unsigned long long* r = red[t >> 6];
+    r[0] = s.mismatched;
+    r[1] = s.first;
+    r[2] = s.dropped;
+    r[3] = s.raised;
+    r[4] = s.sum;
+  }
+  __syncthreads();
+  if (t == 0) {
+    for (int w = 1; w < HBM_MARCH_THREADS / 64; w++) {
+      s.mismatched += red[w][0];
+      s.first = min(s.first, red[w][1]);
+      s.dropped |= red[w][2];
+      s.raised |= red[w][3];
+      s.sum += red[w][4];
+    }
+    int4* rec = records + 4 * (long)blockIdx.x;
+    rec[0] = make_int4((int)((xcc << 16) | (hwid & 0xffff)), done, (int)(unsigned)start,
+                       (int)(unsigned)(start >> 32));
+    asm volatile("" ::: "memory");  // four stores, as in the write kernel
+    rec[1] = make_int4((int)(unsigned)end, (int)(unsigned)(end >> 32), (int)(unsigned)s.mismatched,
+                       (int)(unsigned)(s.mismatched >> 32));
+    asm volatile("" ::: "memory");
+    rec[2] = hbm_march_pair(s.first, s.dropped);
+    asm volatile("" ::: "memory");
+    rec[3] = hbm_march_pair(s.raised, s.sum);
+  }
+}
+
+__global__ void hbm_march_poke_kernel(unsigned long long* __restrict__ p, long index, int bit) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) p[index] ^= 1ull << bit;
+}
+
+// frees whatever a march holds when it ends, also when a HIP_CHECK throws
+struct HbmMarchHold {
+  std::vector<void*> ptrs;
+  hipEvent_t start = nullptr, stop = nullptr;
+  ~HbmMarchHold() {
+    for (void* p : ptrs) (void)hipFree(p);
+    if (start) (void)hipEventDestroy(start);
+    if (stop) (void)hipEventDestroy(stop);
+  }
+};
+
+// March up to max_bytes of this device's HBM in chunks of chunk_bytes. Like
+// hbm_sweep, chunks come from plain hipMalloc and are all HELD until the end
+// (a free/alloc loop would get the same physical block back), the budget is
+// min(max_bytes, free - 8 GiB headroom), and an allocation failure ends the
+// march quietly. The headroom applies only above 1 GiB, so small shapes run on
+// a busy card. Per chunk four launches run in order (write p, verify, write
+// ~p, verify: pass 0 and pass 1), each bracketed by HIP events.
+// Returns {records int32 [launches, blocks, 16] in launch order, elapsed_ms
+// float64 [launches], log int64 [min(log_count, max_log), 4], log_count,
+// bytes_tested, chunk_bytes, chunks, skipped}; the tensors are on the host.
+py::dict hbm_march(long max_bytes, long chunk_bytes, long seed, long blocks, long max_log,
+                   long inject_index, long inject_pass, long inject_bit) {
+  TORCH_CHECK(blocks >= 1 && blocks <= (1L << 16), "blocks must be in [1, 2^16]");
+  TORCH_CHECK(max_bytes > 0 && max_bytes <= (1L << 40), "max_bytes must be in [1, 2^40]");
+  TORCH_CHECK(chunk_bytes > 0 && chunk_bytes % HBM_MARCH_TILE_BYTES == 0 &&
+                  chunk_bytes <= max_bytes,
+              "chunk_bytes must be a positive multiple of 16384 and <= max_bytes");
+  TORCH_CHECK(max_log >= 0 && max_log <= (1L << 16), "max_log must be in [0, 2^16]");
+  TORCH_CHECK(inject_index >= -1 && inject_index < max_bytes / 8, "inject_index out of range");
+  TORCH_CHECK(inject_pass >= -1 && inject_pass <= 1, "inject_pass out of range");
+  TORCH_CHECK(inject_bit >= 0 && inject_bit <= 63, "inject_bit out of range");
+  size_t freeB = 0, totalB = 0;
+  HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
+  const long headroom = max_bytes > (1L << 30) ? (8L << 30) : 0;
+  const long budget = std::min(max_bytes, (long)freeB - headroom);
+  const long tiles = chunk_bytes / HBM_MARCH_TILE_BYTES;
+  const long chunk_qwords = chunk_bytes / 8;
+  const size_t record_bytes = (size_t)blocks * 16 * sizeof(int);
+
+  HbmMarchHold hold;
+  auto dev_alloc = [&](size_t bytes) {
+    void* p = nullptr;
+    HIP_CHECK(hipMalloc(&p, bytes));
+    hold.ptrs.push_back(p);
+    HIP_CHECK(hipMemset(p, 0, bytes));
+    return p;
+  };
+  int4* records_d = static_cast<int4*>(dev_alloc(record_bytes));
+  long long* log_d = static_cast<long long*>(dev_alloc((size_t)std::max(max_log, 1L) * 32));
+  unsigned long long* count_d = static_cast<unsigned long long*>(dev_alloc(8));
+  HIP_CHECK(hipDeviceSynchronize());  // the memsets ran on the legacy stream
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  HIP_CHECK(hipEventCreate(&hold.start));
+  HIP_CHECK(hipEventCreate(&hold.stop));
+
+  std::vector<int> records_h;
+  std::vector<double> elapsed_h;
+  // one launch, bracketed by events; its records are copied out after the
+  // stop event (the torch stream is non-blocking, see lds_check)
+  auto timed = [&](auto&& launch) {
+    HIP_CHECK(hipEventRecord(hold.start, stream));
+    launch();
+    HIP_CHECK(hipEventRecord(hold.stop, stream));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventSynchronize(hold.stop));
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, hold.start, hold.stop));
+    elapsed_h.push_back((double)ms);
+    const size_t at = records_h.size();
+    records_h.resize(at + (size_t)blocks * 16);
+    HIP_CHECK(hipMemcpy(records_h.data() + at, records_d, record_bytes, hipMemcpyDeviceToHost));
+  };
+
+  long tested = 0, chunks = 0;
+  for (long off = 0; off + chunk_bytes <= budget; off += chunk_bytes) {
+    void* chunk = nullptr;
+    if (hipMalloc(&chunk, chunk_bytes) != hipSuccess) { (void)hipGetLastError(); break; }
+    hold.ptrs.push_back(chunk);
+    u32x4* p = static_cast<u32x4*>(chunk);
+    const unsigned long long base = (unsigned long long)(off / 8);
+    const long local = inject_index - off / 8;
+    const bool inject_here = inject_index >= 0 && local >= 0 && local < chunk_qwords;
+    for (int pass = 0; pass < 2; pass++) {
+      timed([&]() {
+        hipLaunchKernelGGL(hbm_march_write_kernel, dim3(blocks), dim3(HBM_MARCH_THREADS), 0,
+                           stream, p, base, tiles, (unsigned long long)seed, pass, records_d);
+      });
+      if (inject_here && pass == inject_pass) {
+        hipLaunchKernelGGL(hbm_march_poke_kernel, dim3(1), dim3(64), 0, stream,
+                           static_cast<unsigned long long*>(chunk), local, (int)inject_bit);
+        HIP_CHECK(hipGetLastError());
+      }
+      timed([&]() {
+        hipLaunchKernelGGL(hbm_march_verify_kernel, dim3(blocks), dim3(HBM_MARCH_THREADS), 0,
+                           stream, p, base, tiles, (unsigned long long)seed, pass, pass,
+                           records_d, log_d, count_d, (int)max_log);
+      });
+    }
+    tested += chunk_bytes;
+    chunks++;
+  }
+  unsigned long long log_count = 0;
+  HIP_CHECK(hipMemcpy(&log_count, count_d, sizeof(log_count), hipMemcpyDeviceToHost));
+  const long rows = (long)std::min<unsigned long long>(log_count, (unsigned long long)max_log);
+  auto log = torch::empty({rows, 4}, torch::TensorOptions().dtype(torch::kInt64));
+  if (rows > 0)
+    HIP_CHECK(hipMemcpy(log.data_ptr<int64_t>(), log_d, (size_t)rows * 32, hipMemcpyDeviceToHost));
+  const long launches = (long)elapsed_h.size();
+  auto records = torch::empty({launches, blocks, 16}, torch::TensorOptions().dtype(torch::kInt32));
+  if (launches > 0)
+    std::memcpy(records.data_ptr<int>(), records_h.data(), records_h.size() * sizeof(int));
+  auto elapsed = torch::empty({launches}, torch::TensorOptions().dtype(torch::kFloat64));
+  if (launches > 0)
+    std::memcpy(elapsed.data_ptr<double>(), elapsed_h.data(), elapsed_h.size() * sizeof(double));
+  py::dict d;
+  d["records"] = records;
+  d["elapsed_ms"] = elapsed;
+  d["log"] = log;
+  d["log_count"] = (long long)log_count;
+  d["bytes_tested"] = (long long)tested;
+  d["chunk_bytes"] = (long long)chunk_bytes;
+  d["chunks"] = (long long)chunks;
+  // as for hbm_sweep: a zero-byte march is not evidence of health
+  d["skipped"] = (bool)(tested == 0);
+  return d;
+}
+
 py::dict device_info(int dev) {
   hipDeviceProp_t prop;
   HIP_CHECK(hipGetDeviceProperties(&prop, dev));
@@ -1053,6 +1419,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hbm_sweep", &hbm_sweep, py::arg("max_gib") = 16, py::arg("chunk_gib") = 4,
         py::arg("seed") = 1,
         "Stuck-bit pattern sweep over up to max_gib GiB of HBM; returns error count");
+  m.def("hbm_march", &hbm_march, py::arg("max_bytes") = 16L << 30,
+        py::arg("chunk_bytes") = 4L << 30, py::arg("seed") = 1, py::arg("blocks") = 2048,
+        py::arg("max_log") = 64, py::arg("inject_index") = -1, py::arg("inject_pass") = -1,
+        py::arg("inject_bit") = 0,
+        "HBM march: write/verify in both polarities, 16 B per lane, sweep-unique pattern, each "
+        "launch timed; returns per-workgroup records [launches,blocks,16], a bad-location log "
+        "and the bytes tested");
   m.def("lds_check", &lds_check, py::arg("blocks") = 2048, py::arg("seed") = 1,
         "LDS slab write/read-verify across the chip; returns error count");
   m.def("lds_march", &lds_march, py::arg("blocks"), py::arg("rounds"), py::arg("seed"),
