@@ -42,6 +42,11 @@ def main() -> None:
                     help="mark a GPU bad when one XCD's march read rate is below this "
                          "fraction of the median XCD (no default: measure your fleet, see "
                          "docs/user-manual.md)")
+    ap.add_argument("--simd-probe-every", type=int, default=0,
+                    help="SIMD probe (exact VALU burn and register-file march, per-SIMD "
+                         "attribution) every N sweeps (on deep sweeps); 0 = never")
+    ap.add_argument("--simd-probe", action="store_true",
+                    help="with --local: also run the SIMD probe")
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
@@ -55,7 +60,8 @@ def main() -> None:
                                      probe_pairs=args.probe_pairs, burn=args.burn,
                                      min_mfma_tflops=args.min_mfma_tflops,
                                      lds_march=args.lds_march, hbm_march=args.hbm_march,
-                                     min_xcd_ratio=args.min_xcd_ratio)
+                                     min_xcd_ratio=args.min_xcd_ratio,
+                                     simd_probe=args.simd_probe)
         if args.p2p_matrix:
             try:
                 m = p2p_link_matrix()
@@ -76,7 +82,8 @@ def main() -> None:
                             min_mfma_tflops=args.min_mfma_tflops,
                             lds_march_every=args.lds_march_every,
                             hbm_march_every=args.hbm_march_every,
-                            min_xcd_ratio=args.min_xcd_ratio)
+                            min_xcd_ratio=args.min_xcd_ratio,
+                            simd_probe_every=args.simd_probe_every)
     if args.once:
         import json
 

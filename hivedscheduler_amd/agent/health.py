@@ -53,6 +53,7 @@ def collect_node_health(
     lds_march: bool = False,
     hbm_march: bool = False,
     min_xcd_ratio: Optional[float] = None,
+    simd_probe: bool = False,
 ) -> dict:
     """One health sweep over all visible GPUs. deep=True also runs the HIP
     kernels (HBM + MFMA); sweep=True adds the 16 GiB HBM stuck-bit pattern
@@ -81,6 +82,14 @@ def collect_node_health(
     the median XCD; there is no default because the healthy spread is
     site-measured (docs/user-manual.md). Like the stuck-bit scan it holds up
     to 16 GiB while it runs, and the same warning applies.
+
+    simd_probe=True (with deep) adds the SIMD probe (the exact VALU burn and
+    the register-file march): per GPU it records `simd_probe_ok`,
+    `valu_burn_ok`, `vgpr_march_ok` and `bad_simds` (the SIMDs of any wave
+    that computed or read back wrong, as xcc, se, sh, cu, simd; a key of its
+    own beside `bad_cus` and `lds_bad_cus`), and a failed probe marks the
+    leaf bad. The march holds every SIMD's whole register file for about a
+    millisecond, during which tenant waves wait.
 
     The stuck-bit scan transiently holds up to 16 GiB of HBM; on a GPU
     running tenant jobs this can make the tenant's own allocations fail.
@@ -111,6 +120,8 @@ def collect_node_health(
                     kwargs["lds_march"] = True
                 if hbm_march:
                     kwargs["hbm_march"] = True
+                if simd_probe:
+                    kwargs["simd_probe"] = True
                 rep = gpu_health_report(i, quick=True, deep=sweep, bw_samples=3, **kwargs)
                 report["gpus"][str(i)].update(
                     hbm_gbps=round(rep["hbm_gbps"], 1),
@@ -161,6 +172,17 @@ def collect_node_health(
                         report["gpus"][str(i)]["hbm_first_bad_offset"] = int(
                             h["first_bad"]["offset"])
                     if not h["skipped"] and (not h["ok"] or slow):
+                        report["gpus"][str(i)]["healthy"] = False
+                if simd_probe:
+                    p = rep["simd_probe"]
+                    report["gpus"][str(i)].update(
+                        simd_probe_ok=bool(p["ok"]),
+                        valu_burn_ok=bool(p["valu"]["ok"]),
+                        vgpr_march_ok=bool(p["vgpr_march"]["ok"]),
+                        bad_simds=[{k: c[k] for k in ("xcc", "se", "sh", "cu", "simd")}
+                                   for c in p["bad_simds"]],
+                    )
+                    if not p["ok"] or p["bad_simds"]:
                         report["gpus"][str(i)]["healthy"] = False
             except Exception as e:
                 report["gpus"][str(i)].update(healthy=False, error=str(e)[:200])
@@ -235,7 +257,8 @@ class NodeHealthAgent:
                  sweep_every: int = 60, probe_pairs: bool = True,
                  p2p_matrix_every: int = 30, burn_every: int = 0,
                  min_mfma_tflops: Optional[float] = None, lds_march_every: int = 0,
-                 hbm_march_every: int = 0, min_xcd_ratio: Optional[float] = None):
+                 hbm_march_every: int = 0, min_xcd_ratio: Optional[float] = None,
+                 simd_probe_every: int = 0):
         self.scheduler_url = scheduler_url.rstrip("/")
         self.node_name = node_name or socket.gethostname()
         self.interval_s = interval_s
@@ -262,6 +285,10 @@ class NodeHealthAgent:
         # keep it on a low-frequency cadence and prefer idle GPUs
         self.hbm_march_every = hbm_march_every
         self.min_xcd_ratio = min_xcd_ratio
+        # SIMD probe cadence (VALU burn + register-file march), same pattern;
+        # 0 = never (tens of milliseconds per GPU, and the march takes every
+        # SIMD's whole register file for about one of them)
+        self.simd_probe_every = simd_probe_every
         self._rounds = 0
 
     def post_report(self, report: dict) -> bool:
@@ -312,6 +339,7 @@ class NodeHealthAgent:
         burn = self.burn_every > 0 and (self._rounds % self.burn_every) == 0
         march = self.lds_march_every > 0 and (self._rounds % self.lds_march_every) == 0
         hbm = self.hbm_march_every > 0 and (self._rounds % self.hbm_march_every) == 0
+        simd = self.simd_probe_every > 0 and (self._rounds % self.simd_probe_every) == 0
         self._rounds += 1
         kwargs = {}
         if burn and deep:
@@ -320,6 +348,8 @@ class NodeHealthAgent:
             kwargs["lds_march"] = True
         if hbm and deep:
             kwargs.update(hbm_march=True, min_xcd_ratio=self.min_xcd_ratio)
+        if simd and deep:
+            kwargs["simd_probe"] = True
         report = collect_node_health(deep=deep, probe_pairs=self.probe_pairs and deep,
                                      sweep=sweep and deep, **kwargs)
         report["node"] = self.node_name

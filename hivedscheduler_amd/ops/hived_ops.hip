@@ -11,6 +11,11 @@
 //                the kernel; TFLOP/s plus the CU of any wave that was wrong
 //  - lds_march:  all 160 KiB of every CU's LDS, both bit polarities, narrow
 //                and wide reads, timed; the CU, word and bits of any mismatch
+//  - valu_burn:  sustained, timed vector-ALU issue per section (integer, f32,
+//                f64, cross-lane, transcendental), verified bitwise in the
+//                kernel; the SIMD of any wave that was wrong
+//  - vgpr_march: 480 of the 512 vector registers per lane of every SIMD, both
+//                bit polarities; the SIMD, register and bits of any mismatch
 //  - hbm_march:  a bounded span of HBM, both bit polarities, 16 B per lane,
 //                values unique across the sweep; the offset, bits and direction
 //                of any mismatch, and a bandwidth per XCD from device clocks
@@ -871,6 +876,534 @@ std::tuple<torch::Tensor, double> lds_march(long blocks, long rounds, long seed,
 }
 
 // ---------------------------------------------------------------------------
+// VALU burn: a bounded, timed, exactly verifiable run of sustained vector-ALU
+// issue on every SIMD, built like the MFMA burn-in above. Each lane carries
+// one small state, seeded from (seed, section, lane) only, so every wave
+// computes the same 64 values. Each round re-seeds the state, applies `chain`
+// dependent steps and compares the state bitwise against expected[lane],
+// which the host mirror (ops.valu_burn_expected) computes. The hot loop has
+// no memory traffic. SEC selects what a step is made of:
+//   int    v_mul_lo_u32, v_mul_hi_u32, v_mad_u64_u32, add, xor, v_alignbit
+//          rotate, v_bfe_u32, v_bcnt popcount
+//   f32    v_cvt_f32_u32, v_ldexp_f32, the f32 FMA (emitted in its v_fmac_f32
+//          encoding), v_pk_fma_f32, v_cvt_u32_f32
+//   f64    v_cvt_f64_u32, the f64 FMA twice (v_fmac_f64), and v_trunc_f64,
+//          v_ldexp_f64, v_floor_f64, v_cvt_u32_f64 on the way back
+//   xlane  DPP quad_perm, row_shr and row_mirror, v_permlane32_swap,
+//          ds_bpermute, v_readlane
+//   trans  v_exp_f32, v_log_f32, v_rcp_f32, v_rsq_f32, v_sqrt_f32, v_sin_f32
+// Exactness by construction: the int and xlane steps are integer arithmetic
+// and data movement. The f32 step multiplies two 12-bit integers and adds a
+// 13-bit one, 4095*4095 + 8191 = 2^24, so every fma result is an integer that
+// fp32 holds exactly; the power-of-two scaling around the scalar fma is exact
+// and only moves the exponent path. The f64 step multiplies two 26-bit
+// integers and adds one below 2^52: below 2^53, exact in fp64. So a
+// pure-integer mirror reproduces these four sections bit for bit, whatever
+// the rounding mode or evaluation order. (Checked in the gfx950 disassembly:
+// each section's inner loop issues the instructions listed; BENCHMARKS.md
+// "SIMD probe".)
+//
+// The trans section is different. The low bits of the transcendental unit's
+// results are hardware-defined, so there is no host golden: `expected` is
+// ignored, nothing is compared in the kernel, and the host checks consensus,
+// every wave's checksum against the majority. It can name a SIMD that
+// disagrees with the others; it CANNOT catch a fault common to all SIMDs.
+//
+// Lane 0 of each wave writes one record of eight int32 (two int4 stores):
+//   [0] (XCC_ID<<16)|HW_ID      (the cu_coverage_kernel encoding; SIMD_ID is
+//                                HW_ID[5:4] in the gfx9-family layout)
+//   [1] mismatched lane-rounds
+//   [2] first bad round (-1 if none)
+//   [3] lowest bad lane in that round (-1 if none)
+//   [4] [5] xor over lanes and rounds of the state, low and high word
+//   [6] [7] 0 (reserved)
+// Every round ends in the same state, so the xor over an even number of
+// rounds cancels: a checksum says something for odd `rounds` only.
+//
+// inject_* (default -1 = off): in wave inject_wave, at round inject_round,
+// lane inject_lane xors bit inject_bit into its state before the compare.
+// Register arithmetic only, as in the MFMA burn-in.
+// ---------------------------------------------------------------------------
+enum { VALU_INT = 0, VALU_F32 = 1, VALU_F64 = 2, VALU_XLANE = 3, VALU_TRANS = 4 };
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+
+// rotate left by k in [1,31] with v_alignbit_b32: ({x,x} >> (32-k))[31:0]
+__device__ __forceinline__ unsigned rotl32(unsigned x, int k) {
+  return __builtin_amdgcn_alignbit(x, x, 32 - k);
+}
+
+// low word: the u32 sections' state; both words: the f64 section's
+__device__ __forceinline__ unsigned long long valu_seed_state(unsigned seed, int section,
+                                                              int lane) {
+  unsigned lo = fmix32(seed + (unsigned)section * 0x9E3779B9u + (unsigned)lane * 0x85EBCA6Bu);
+  unsigned hi = fmix32(lo ^ 0xC2B2AE35u);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+template <int SEC> struct ValuStep;
+
+template <> struct ValuStep<VALU_INT> {
+  typedef unsigned state;
+  static __device__ __forceinline__ state step(state s, int lane, int c) {
+    unsigned lo = s * 0x9E3779B1u;
+    unsigned hi = __umulhi(s, 0x85EBCA6Bu);
+    unsigned long long m = (unsigned long long)lo * (hi | 1u) + (((unsigned long long)hi << 32) | s);
+    unsigned t = ((unsigned)m ^ (unsigned)(m >> 32)) + lo;
+    return (rotl32(t, 13) ^ __builtin_amdgcn_ubfe(hi, 7, 11)) + (unsigned)__popc(lo);
+  }
+};
+
+template <> struct ValuStep<VALU_F32> {
+  typedef unsigned state;
+  static __device__ __forceinline__ state step(state s, int lane, int c) {
+    // a, b < 2^12 and c < 2^13: a*b + c <= 2^24, exact in fp32. The scalar
+    // fma runs scaled by 2^k, k in [-8, 7], and is scaled back: exact too
+    const int k = (int)((s >> 5) & 15u) - 8;
+    float a = __builtin_amdgcn_ldexpf((float)(s & 0xFFFu), k);
+    float b = (float)((s >> 12) & 0xFFFu);
+    float cc = __builtin_amdgcn_ldexpf((float)(s >> 19), k);
+    unsigned r0 = (unsigned)__builtin_amdgcn_ldexpf(__builtin_fmaf(a, b, cc), -k);
+    f32x2 pa = {(float)((s >> 3) & 0xFFFu), (float)((s >> 9) & 0xFFFu)};
+    f32x2 pb = {(float)((s >> 16) & 0xFFFu), (float)((s >> 1) & 0xFFFu)};
+    f32x2 pc = {(float)((s >> 7) & 0x1FFFu), (float)((s >> 13) & 0x1FFFu)};
+    f32x2 pr = __builtin_elementwise_fma(pa, pb, pc);
+    unsigned r1 = (unsigned)pr.x, r2 = (unsigned)pr.y;
+    return (s * 0x9E3779B1u + 0x7F4A7C15u) ^ (r0 + (r1 << 5) + (r2 << 9));
+  }
+};
+
+template <> struct ValuStep<VALU_F64> {
+  typedef unsigned long long state;
+  static __device__ __forceinline__ state step(state s, int lane, int c) {
+    // a, b, ch, cl < 2^26: cc = ch*2^26 + cl < 2^52 and a*b < 2^52, so
+    // a*b + cc < 2^53: both fmas are exact in fp64
+    const unsigned m26 = 0x3FFFFFFu;
+    double a = (double)((unsigned)s & m26);
+    double b = (double)((unsigned)(s >> 26) & m26);
+    double cc = __builtin_fma((double)(unsigned)(s >> 38), 67108864.0,
+                              (double)((unsigned)(s >> 7) & m26));
+    unsigned long long r = (unsigned long long)__builtin_fma(a, b, cc);
+    return (s * 0x9E3779B97F4A7C15ull + 0xBF58476D1CE4E5B9ull) ^ r ^ (r << 11);
+  }
+};
+
+template <> struct ValuStep<VALU_XLANE> {
+  typedef unsigned state;
+  // old = src in every DPP move: a lane whose source is outside its row keeps
+  // its own value
+  template <int CTRL> static __device__ __forceinline__ unsigned dpp(unsigned x) {
+    return (unsigned)__builtin_amdgcn_update_dpp((int)x, (int)x, CTRL, 0xF, 0xF, false);
+  }
+  static __device__ __forceinline__ state step(state s, int lane, int c) {
+    unsigned x = s;
+    x = rotl32(x, 5) + dpp<0xB1>(x);    // quad_perm:[1,0,3,2]: lane l reads l^1
+    x = rotl32(x, 7) ^ dpp<0x111>(x);   // row_shr:1: l reads l-1, l%16 == 0 itself
+    x = x + rotl32(dpp<0x140>(x), 13);  // row_mirror: l reads l^15
+    // vdst lanes 32-63 swap with src lanes 0-31; the other halves stay
+    auto sw = __builtin_amdgcn_permlane32_swap(x, rotl32(x, 3), false, false);
+    x = sw[0] + (sw[1] ^ 0x9E3779B9u);
+    unsigned from = (unsigned)(lane * 13 + 7) & 63u;  // a bijection on the lanes
+    x = rotl32(x, 9) ^ (unsigned)__builtin_amdgcn_ds_bpermute((int)(from << 2), (int)x);
+    return x + (unsigned)__builtin_amdgcn_readlane((int)x, (c * 11 + 5) & 63);
+  }
+};
+
+template <> struct ValuStep<VALU_TRANS> {
+  typedef unsigned state;
+  static __device__ __forceinline__ state step(state s, int lane, int c) {
+    float f = __uint_as_float(0x3F800000u | (s & 0x7FFFFFu));  // [1, 2)
+    unsigned e = __float_as_uint(__builtin_amdgcn_exp2f(f));
+    unsigned l = __float_as_uint(__builtin_amdgcn_logf(f));
+    unsigned rc = __float_as_uint(__builtin_amdgcn_rcpf(f));
+    unsigned rq = __float_as_uint(__builtin_amdgcn_rsqf(f));
+    unsigned sq = __float_as_uint(__builtin_amdgcn_sqrtf(f));
+    unsigned sn = __float_as_uint(__builtin_amdgcn_sinf(f * 0.125f));  // argument in turns
+    return (s * 0x9E3779B1u + 0x7F4A7C15u) ^ e ^ rotl32(l, 3) ^ rotl32(rc, 7) ^ rotl32(rq, 11) ^
+           rotl32(sq, 17) ^ rotl32(sn, 23);
+  }
+};
+
+template <int SEC>
+__global__ void __launch_bounds__(256)
+valu_burn_kernel(const long long* __restrict__ expected, int4* __restrict__ records,
+                 unsigned seed, int chain, int rounds, int inject_wave, int inject_round,
+                 int inject_lane, int inject_bit) {
+  typedef ValuStep<SEC> V;
+  typedef typename V::state state;
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  unsigned hwid, xcc;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+
+  const state seeded = (state)valu_seed_state(seed, SEC, lane);
+  state want = 0;
+  if constexpr (SEC != VALU_TRANS) want = (state)expected[lane];
+  const state flip =
+      (wave == inject_wave && lane == inject_lane) ? (state)1 << (inject_bit & (int)(8 * sizeof(state) - 1)) : (state)0;
+  int mismatched = 0, first_round = -1, first_lane = -1;
+  state checksum = 0;
+  for (int round = 0; round < rounds; round++) {
+    state s = seeded;
+    // opaque to the optimiser: every round really recomputes its chain
+    asm volatile("" : "+v"(s));
+    for (int c = 0; c < chain; c++) s = V::step(s, lane, c);
+    if (round == inject_round) s ^= flip;
+    checksum ^= s;
+    if constexpr (SEC != VALU_TRANS) {
+      const unsigned long long bad = __ballot(s != want);  // wave-uniform
+      if (bad) {
+        mismatched += __popcll(bad);
+        if (first_round < 0) {
+          first_round = round;
+          first_lane = __ffsll((long long)bad) - 1;
+        }
+      }
+    }
+  }
+  unsigned lo = (unsigned)checksum, hi = (unsigned)((unsigned long long)checksum >> 32);
+  for (int off = 32; off > 0; off >>= 1) {
+    lo ^= (unsigned)__shfl_xor((int)lo, off);
+    hi ^= (unsigned)__shfl_xor((int)hi, off);
+  }
+  if (lane == 0) {
+    records[2 * wave] = make_int4((int)((xcc << 16) | (hwid & 0xffff)), mismatched, first_round,
+                                  first_lane);
+    records[2 * wave + 1] = make_int4((int)lo, (int)hi, 0, 0);
+  }
+}
+
+
+// ---------------------------------------------------------------------------
+// VGPR march: a timed write/read-verify of a SIMD's vector register file in
+// both bit polarities. VGPRs and AGPRs are one file of 512 entries per lane
+// per SIMD (128 KiB per SIMD, 512 KiB per CU). This kernel allocates all 512
+// (256 + 256), so its wave is the only one its SIMD can hold and owns the
+// file; the host entry asserts that occupancy on every run.
+//
+// A pass is ONE asm statement: it writes v32..v255 and a0..a255 in ascending
+// order, xors the two injection masks into one fixed VGPR and one fixed AGPR,
+// then reads all of them back in ascending order and compares. The statement
+// names every register it marches as a clobber (which also makes the kernel
+// descriptor allocate 256 + 256); between statements the compiler is free to
+// use them, so nothing of a pass may straddle two statements. v0..v31 are
+// where the compiler keeps the kernel's own values and the statement's
+// operands: 480 of the 512 entries are marched.
+//
+// Pattern: in round r register R (0..255 architectural, 256..511 the
+// accumulators) of lane l holds
+//   p(r, R, l) = ((R*64 + l) * 0x9E3779B1 mod 2^32) ^ rs,
+//   rs = fmix32(seed + r*0x9E3779B9),
+// then its complement in the round's second pass. Multiplication by an odd
+// constant and xor with a constant are bijections on 32 bits, so the 32768
+// values of a pass are distinct and an aliased register or lane reads back
+// as wrong data. In the asm that is v_add_u32 v[R], (R*64*K) mod 2^32, l*K
+// and v_xor_b32 with rs (or ~rs).
+//
+// Several hundred independent instructions separate a register's write from
+// its read-back. Where a temporary is produced and consumed back to back
+// around a v_accvgpr_* move it is padded with s_nop 1: that is a precaution,
+// not a measured requirement.
+//
+// Lane 0 of each wave writes one record of eight int32 (two int4 stores):
+//   [0] (XCC_ID<<16)|HW_ID
+//   [1] mismatched (register, lane) pairs over all passes
+//   [2] first bad global pass, round*2 + polarity (-1 if none)
+//   [3] lowest mismatching register index R in that pass (-1 if none)
+//   [4] dropped mask: OR of (want & ~got), bits that should be 1 and read 0
+//   [5] raised mask:  OR of (got & ~want), bits that should be 0 and read 1
+//   [6] sum mod 2^32 of every value read in the pattern passes
+//   [7] registers marched per pass (480)
+//
+// inject_* (default -1 = off): in wave inject_wave, at global pass
+// inject_pass, lane inject_lane's mask for v[VGPR_MARCH_INJECT_V] (target 0)
+// or a[VGPR_MARCH_INJECT_A] (target 1) holds bit inject_bit; everywhere else
+// both masks are zero. They are xored in unconditionally, between the write
+// and the read phase, inside the statement. Registers only.
+// ---------------------------------------------------------------------------
+constexpr int VGPR_MARCH_FIRST = 32;     // v0..v31 stay the compiler's
+constexpr int VGPR_MARCH_MARCHED = 480;  // v32..v255 and a0..a255
+constexpr int VGPR_MARCH_INJECT_V = 77;  // R = 77
+constexpr int VGPR_MARCH_INJECT_A = 141; // R = 256 + 141 = 397
+
+// compare the value in GOT against the pattern of register index R (both
+// assembler expressions); t0 = want, t1 = diff, t2 = scratch. Plain VALU
+// arithmetic on VGPRs only: no VCC or SGPR is written and read back, so no
+// VALU-writes-SGPR wait states are owed inside the string. t2 = min(1, diff)
+// is 1 on a mismatch; t2 - 1 is then 0 on a mismatch and all ones otherwise,
+// and or-ing R into it leaves R or all ones for the running min
+#define VGPR_MARCH_CHECK(GOT, R)                                        \
+  "v_add_u32 %[t0], ((" R ")*64*0x9E3779B1)&0xffffffff, %[base]\n\t"    \
+  "v_xor_b32 %[t0], %[xr], %[t0]\n\t"                                   \
+  "v_xor_b32 %[t1], %[t0], " GOT "\n\t"                                 \
+  "v_and_b32 %[t2], %[smask], " GOT "\n\t"                              \
+  "v_add_u32 %[sum], %[sum], %[t2]\n\t"                                 \
+  "v_and_or_b32 %[dropped], %[t0], %[t1], %[dropped]\n\t"               \
+  "v_and_or_b32 %[raised], " GOT ", %[t1], %[raised]\n\t"               \
+  "v_min_u32 %[t2], 1, %[t1]\n\t"                                       \
+  "v_add_u32 %[mism], %[mism], %[t2]\n\t"                               \
+  "v_add_u32 %[t2], -1, %[t2]\n\t"                                      \
+  "v_or_b32 %[t2], " R ", %[t2]\n\t"                                    \
+  "v_min_u32 %[first], %[first], %[t2]\n\t"
+
+// the clobber list: "v32".."v255", "a0".."a255", ten names per HVD_C10
+#define HVD_C10(P, d)                                                                  \
+  P #d "0", P #d "1", P #d "2", P #d "3", P #d "4", P #d "5", P #d "6", P #d "7", P #d "8", \
+      P #d "9"
+#define HVD_C50(P, a, b, c, d, e) \
+  HVD_C10(P, a), HVD_C10(P, b), HVD_C10(P, c), HVD_C10(P, d), HVD_C10(P, e)
+#define HVD_C40_249(P)                                                                   \
+  HVD_C10(P, 4), HVD_C50(P, 5, 6, 7, 8, 9), HVD_C50(P, 10, 11, 12, 13, 14),              \
+      HVD_C50(P, 15, 16, 17, 18, 19), HVD_C50(P, 20, 21, 22, 23, 24), P "250", P "251", \
+      P "252", P "253", P "254", P "255"
+#define VGPR_MARCH_CLOBBERS                                                              \
+  "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", HVD_C40_249("v"), "a0", "a1", \
+      "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", HVD_C10("a", 1), HVD_C10("a", 2),  \
+      HVD_C10("a", 3), HVD_C40_249("a")
+
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
+vgpr_march_kernel(int4* __restrict__ records, int rounds, unsigned seed, int inject_wave,
+                  int inject_target, int inject_lane, int inject_bit, int inject_pass) {
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  unsigned hwid, xcc;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+
+  const unsigned base = (unsigned)lane * 0x9E3779B1u;
+  const unsigned flip =
+      (wave == inject_wave && lane == inject_lane) ? 1u << (inject_bit & 31) : 0u;
+  unsigned mism = 0, dropped = 0, raised = 0, sum = 0;
+  int first_pass = -1;
+  unsigned first_reg = 0xFFFFFFFFu;
+#pragma nounroll
+  for (int pass = 0; pass < 2 * rounds; pass++) {
+    const unsigned rs = fmix32(seed + (unsigned)(pass >> 1) * 0x9E3779B9u);
+    const unsigned xr = (pass & 1) ? ~rs : rs;            // wave-uniform
+    const unsigned smask = (pass & 1) ? 0u : 0xFFFFFFFFu;  // sum pattern passes only
+    const unsigned m0 = (pass == inject_pass && inject_target == 0) ? flip : 0u;
+    const unsigned m1 = (pass == inject_pass && inject_target == 1) ? flip : 0u;
+    unsigned first = 0xFFFFFFFFu, t0, t1, t2, t3;
+    asm volatile(
+        // write phase, architectural registers v32..v255
+        ".set hvd_r, 32\n\t"
+        ".rept 224\n\t"
+        "v_add_u32 v[hvd_r], (hvd_r*64*0x9E3779B1)&0xffffffff, %[base]\n\t"
+        "v_xor_b32 v[hvd_r], %[xr], v[hvd_r]\n\t"
+        ".set hvd_r, hvd_r+1\n\t"
+        ".endr\n\t"
+        // write phase, accumulators a0..a255 (R = 256..511)
+        ".set hvd_r, 0\n\t"
+        ".rept 256\n\t"
+        "v_add_u32 %[t0], ((hvd_r+256)*64*0x9E3779B1)&0xffffffff, %[base]\n\t"
+        "v_xor_b32 %[t0], %[xr], %[t0]\n\t"
+        "s_nop 1\n\t"
+        "v_accvgpr_write_b32 a[hvd_r], %[t0]\n\t"
+        "s_nop 1\n\t"
+        ".set hvd_r, hvd_r+1\n\t"
+        ".endr\n\t"
+        // injection: masks are zero except in one wave, lane and pass
+        "v_xor_b32 v77, %[m0], v77\n\t"
+        "v_accvgpr_read_b32 %[t0], a141\n\t"
+        "s_nop 1\n\t"
+        "v_xor_b32 %[t0], %[m1], %[t0]\n\t"
+        "s_nop 1\n\t"
+        "v_accvgpr_write_b32 a141, %[t0]\n\t"
+        "s_nop 1\n\t"
+        // read phase, architectural registers
+        ".set hvd_r, 32\n\t"
+        ".rept 224\n\t"
+        VGPR_MARCH_CHECK("v[hvd_r]", "hvd_r")
+        ".set hvd_r, hvd_r+1\n\t"
+        ".endr\n\t"
+        // read phase, accumulators
+        ".set hvd_r, 0\n\t"
+        ".rept 256\n\t"
+        "v_accvgpr_read_b32 %[t3], a[hvd_r]\n\t"
+        "s_nop 1\n\t"
+        VGPR_MARCH_CHECK("%[t3]", "hvd_r+256")
+        ".set hvd_r, hvd_r+1\n\t"
+        ".endr\n\t"
+        : [mism] "+v"(mism), [dropped] "+v"(dropped), [raised] "+v"(raised), [sum] "+v"(sum),
+          [first] "+v"(first), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3)
+        : [base] "v"(base), [xr] "s"(xr), [smask] "v"(smask), [m0] "v"(m0), [m1] "v"(m1)
+        : VGPR_MARCH_CLOBBERS);
+    const bool first_here = first != 0xFFFFFFFFu && first_pass < 0;
+    first_pass = first_here ? pass : first_pass;
+    first_reg = first_here ? first : first_reg;
+  }
+  // wave reduction as in lds_march_kernel: the earliest pass, then the lowest
+  // register among the lanes that failed in it
+  unsigned fp = (unsigned)first_pass;
+  for (int off = 32; off > 0; off >>= 1) {
+    mism += (unsigned)__shfl_xor((int)mism, off);
+    dropped |= (unsigned)__shfl_xor((int)dropped, off);
+    raised |= (unsigned)__shfl_xor((int)raised, off);
+    sum += (unsigned)__shfl_xor((int)sum, off);
+    fp = min(fp, (unsigned)__shfl_xor((int)fp, off));
+  }
+  unsigned fr = (unsigned)first_pass == fp ? first_reg : 0xFFFFFFFFu;
+  for (int off = 32; off > 0; off >>= 1) fr = min(fr, (unsigned)__shfl_xor((int)fr, off));
+  if (lane == 0) {
+    records[2 * wave] = make_int4((int)((xcc << 16) | (hwid & 0xffff)), (int)mism, (int)fp, (int)fr);
+    records[2 * wave + 1] = make_int4((int)dropped, (int)raised, (int)sum, VGPR_MARCH_MARCHED);
+  }
+}
+
+template <int SEC>
+static void launch_valu_burn(long blocks, hipStream_t stream, const long long* expected,
+                             int4* records, long seed, long chain, long rounds, long inject_wave,
+                             long inject_round, long inject_lane, long inject_bit) {
+  hipLaunchKernelGGL((valu_burn_kernel<SEC>), dim3(blocks), dim3(256), 0, stream, expected, records,
+                     (unsigned)seed, (int)chain, (int)rounds, (int)inject_wave, (int)inject_round,
+                     (int)inject_lane, (int)inject_bit);
+}
+
+// expected: 64 int64 on the current device, the state every lane must reach
+// after `chain` steps (ops.valu_burn_expected); section "trans" compares
+// nothing and may pass an empty tensor. One untimed warm-up launch, then one
+// launch timed with HIP events.
+// Returns (records [waves,8] int32, elapsed_ms of the timed launch).
+std::tuple<torch::Tensor, double> valu_burn(torch::Tensor expected, const std::string& section,
+                                            long seed, long blocks, long chain, long rounds,
+                                            long inject_wave, long inject_round,
+                                            long inject_lane, long inject_bit) {
+  int sec = section == "int" ? VALU_INT : section == "f32" ? VALU_F32 : section == "f64" ? VALU_F64
+            : section == "xlane" ? VALU_XLANE : section == "trans" ? VALU_TRANS : -1;
+  TORCH_CHECK(sec >= 0, "section must be one of int, f32, f64, xlane, trans; got ", section);
+  TORCH_CHECK(blocks >= 1 && blocks <= (1L << 20), "blocks must be in [1, 2^20]");
+  TORCH_CHECK(chain >= 1 && rounds >= 1, "chain and rounds must be >= 1");
+  // the checksum is all the trans section has, and over an even number of
+  // (identical) rounds it is zero whatever the hardware computed
+  TORCH_CHECK(sec != VALU_TRANS || rounds % 2 == 1,
+              "section trans needs an odd number of rounds (its xor checksum cancels over an "
+              "even number)");
+  // bounded run: at most 2^22 steps per wave. At eight waves per SIMD the
+  // slowest section (f32) measures ~0.5 us per step (BENCHMARKS.md "SIMD
+  // probe"), ~2 s for 2^22 of them at the default grid
+  TORCH_CHECK(chain <= (1L << 22) && rounds <= (1L << 22) && chain * rounds <= (1L << 22),
+              "chain*rounds must be <= 2^22");
+  const long state_bits = sec == VALU_F64 ? 64 : 32;
+  TORCH_CHECK(inject_wave >= -1 && inject_wave < blocks * 4 && inject_round >= -1 &&
+                  inject_round < rounds && inject_lane >= -1 && inject_lane < 64 &&
+                  inject_bit >= -1 && inject_bit < state_bits,
+              "inject_wave/inject_round/inject_lane/inject_bit out of range");
+  TORCH_CHECK(inject_wave < 0 || (inject_round >= 0 && inject_lane >= 0 && inject_bit >= 0),
+              "an injection needs inject_round, inject_lane and inject_bit");
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  const long long* want = nullptr;
+  if (sec != VALU_TRANS || expected.numel() != 0) {
+    TORCH_CHECK(expected.is_cuda() && expected.get_device() == dev,
+                "expected must be on the current GPU");
+    TORCH_CHECK(expected.dtype() == torch::kInt64 && expected.numel() == 64,
+                "expected must hold 64 int64 values (one state per lane)");
+    expected = expected.contiguous();
+    want = reinterpret_cast<const long long*>(expected.data_ptr<int64_t>());
+  }
+  long waves = blocks * 4;
+  auto records = torch::zeros(
+      {waves, 8}, torch::TensorOptions().dtype(torch::kInt32).device(torch::kCUDA, dev));
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  auto launch = [&]() {
+    int4* rec = reinterpret_cast<int4*>(records.data_ptr<int>());
+    switch (sec) {
+      case VALU_INT:
+        launch_valu_burn<VALU_INT>(blocks, stream, want, rec, seed, chain, rounds, inject_wave,
+                                   inject_round, inject_lane, inject_bit);
+        break;
+      case VALU_F32:
+        launch_valu_burn<VALU_F32>(blocks, stream, want, rec, seed, chain, rounds, inject_wave,
+                                   inject_round, inject_lane, inject_bit);
+        break;
+      case VALU_F64:
+        launch_valu_burn<VALU_F64>(blocks, stream, want, rec, seed, chain, rounds, inject_wave,
+                                   inject_round, inject_lane, inject_bit);
+        break;
+      case VALU_XLANE:
+        launch_valu_burn<VALU_XLANE>(blocks, stream, want, rec, seed, chain, rounds, inject_wave,
+                                     inject_round, inject_lane, inject_bit);
+        break;
+      default:
+        launch_valu_burn<VALU_TRANS>(blocks, stream, want, rec, seed, chain, rounds, inject_wave,
+                                     inject_round, inject_lane, inject_bit);
+    }
+  };
+  launch();  // warm-up: code-object load and clock ramp stay out of the timing
+  HIP_CHECK(hipGetLastError());
+  hipEvent_t start, stop;
+  HIP_CHECK(hipEventCreate(&start));
+  HIP_CHECK(hipEventCreate(&stop));
+  HIP_CHECK(hipEventRecord(start, stream));
+  launch();
+  HIP_CHECK(hipEventRecord(stop, stream));
+  HIP_CHECK(hipGetLastError());
+  // the torch stream is non-blocking (see lds_check): wait on the stop event
+  // before anything reads the records or the timing
+  HIP_CHECK(hipEventSynchronize(stop));
+  float ms = 0;
+  HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
+  HIP_CHECK(hipEventDestroy(start));
+  HIP_CHECK(hipEventDestroy(stop));
+  return std::make_tuple(records, (double)ms);
+}
+
+// One untimed warm-up launch, then one launch timed with HIP events.
+// Returns (records [blocks*4, 8] int32, elapsed_ms of the timed launch,
+// resident workgroups per CU as the occupancy query reports them: always 1).
+std::tuple<torch::Tensor, double, long> vgpr_march(long blocks, long rounds, long seed,
+                                                   long inject_wave, long inject_target,
+                                                   long inject_lane, long inject_bit,
+                                                   long inject_pass) {
+  TORCH_CHECK(blocks >= 1 && blocks <= (1L << 16), "blocks must be in [1, 2^16]");
+  TORCH_CHECK(rounds >= 1, "rounds must be >= 1");
+  // bounded run: a round (two passes) of one workgroup measures ~34 us on an
+  // MI355X (BENCHMARKS.md "SIMD probe"); one workgroup per CU on 256 CUs then
+  // puts 2^20 block-rounds at ~0.14 s
+  TORCH_CHECK(rounds <= (1L << 20) && blocks * rounds <= (1L << 20),
+              "blocks*rounds must be <= 2^20");
+  TORCH_CHECK(inject_wave >= -1 && inject_wave < blocks * 4, "inject_wave out of range");
+  TORCH_CHECK(inject_target == 0 || inject_target == 1, "inject_target must be 0 or 1");
+  TORCH_CHECK(inject_lane >= 0 && inject_lane < 64, "inject_lane out of range");
+  TORCH_CHECK(inject_bit >= 0 && inject_bit < 32, "inject_bit out of range");
+  TORCH_CHECK(inject_pass >= -1 && inject_pass < rounds * 2, "inject_pass out of range");
+  // the premise of the march, asserted on every run: a wave that holds all
+  // 512 registers per lane is alone on its SIMD, so one 256-thread workgroup
+  // is all a CU can hold
+  int per_cu = 0;
+  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, vgpr_march_kernel, 256, 0));
+  TORCH_CHECK(per_cu == 1, "vgpr_march needs exactly one resident workgroup per CU (one wave ",
+              "per SIMD); the occupancy query reports ", per_cu);
+  long waves = blocks * 4;
+  auto records = torch::zeros({waves, 8},
+                              torch::TensorOptions().dtype(torch::kInt32).device(torch::kCUDA));
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  auto launch = [&]() {
+    hipLaunchKernelGGL(vgpr_march_kernel, dim3(blocks), dim3(256), 0, stream,
+                       reinterpret_cast<int4*>(records.data_ptr<int>()), (int)rounds,
+                       (unsigned)seed, (int)inject_wave, (int)inject_target, (int)inject_lane,
+                       (int)inject_bit, (int)inject_pass);
+  };
+  launch();  // warm-up: code-object load and clock ramp stay out of the timing
+  HIP_CHECK(hipGetLastError());
+  hipEvent_t start, stop;
+  HIP_CHECK(hipEventCreate(&start));
+  HIP_CHECK(hipEventCreate(&stop));
+  HIP_CHECK(hipEventRecord(start, stream));
+  launch();
+  HIP_CHECK(hipEventRecord(stop, stream));
+  HIP_CHECK(hipGetLastError());
+  // the torch stream is non-blocking (see lds_check): wait on the stop event
+  // before anything reads the records or the timing
+  HIP_CHECK(hipEventSynchronize(stop));
+  float ms = 0;
+  HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
+  HIP_CHECK(hipEventDestroy(start));
+  HIP_CHECK(hipEventDestroy(stop));
+  return std::make_tuple(records, (double)ms, (long)per_cu);
+}
+
+// ---------------------------------------------------------------------------
 // xGMI p2p bandwidth between two devices (one direction).
 // ---------------------------------------------------------------------------
 double p2p_gbps(int src_dev, int dst_dev, long size_mb, long iters) {
@@ -1433,6 +1966,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("inject_bit") = 0,
         "Full-LDS (160 KiB per CU) march: both polarities, b32 and b128 read-back, timed; "
         "returns (per-wave records [blocks*4,8], ms)");
+  m.def("valu_burn", &valu_burn, py::arg("expected"), py::arg("section"), py::arg("seed") = 1,
+        py::arg("blocks") = 2048, py::arg("chain") = 1024, py::arg("rounds") = 33,
+        py::arg("inject_wave") = -1, py::arg("inject_round") = -1, py::arg("inject_lane") = -1,
+        py::arg("inject_bit") = -1,
+        "Sustained VALU burn (section int|f32|f64|xlane|trans): rounds x chain dependent steps "
+        "per lane, verified bitwise against expected; returns (per-wave records [waves,8], ms)");
+  m.def("vgpr_march", &vgpr_march, py::arg("blocks"), py::arg("rounds"), py::arg("seed"),
+        py::arg("inject_wave") = -1, py::arg("inject_target") = 0, py::arg("inject_lane") = 0,
+        py::arg("inject_bit") = 0, py::arg("inject_pass") = -1,
+        "Register-file march (480 of the 512 VGPR+AGPR entries per lane of every SIMD): both "
+        "polarities, timed; returns (per-wave records [blocks*4,8], ms, workgroups per CU)");
   m.def("cu_coverage", &cu_coverage, py::arg("blocks") = 4096,
         "Per-wave (XCC_ID<<16 | HW_ID) placement words for CU-coverage checks");
   m.def("device_info", &device_info, py::arg("dev") = 0);
