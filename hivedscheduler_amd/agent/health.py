@@ -42,6 +42,11 @@ def _rocm_smi_gpu_state() -> Dict[int, bool]:
         return {}
 
 
+def _set_flags(**flags) -> dict:
+    """The set flags as keyword arguments; none set leaves a call as it was."""
+    return {name: True for name, on in flags.items() if on}
+
+
 def collect_node_health(
     deep: bool = False,
     min_hbm_gbps: float = 2000.0,
@@ -109,34 +114,30 @@ def collect_node_health(
         gpu = {"healthy": alive.get(i, True)}
         report["gpus"][str(i)] = gpu
     if deep and n > 0:
-        from ..ops import gpu_health_report
+        from ..ops import gpu_health_report, hbm_slow_xcds
 
+        kwargs = _set_flags(burn=burn, lds_march=lds_march, hbm_march=hbm_march,
+                            simd_probe=simd_probe)
         for i in range(n):
+            gpu = report["gpus"][str(i)]
             try:
                 # best-of-3 bandwidth: a tenant job on the GPU can halve a
                 # single triad sample (see profiles/interference_r01.md)
-                kwargs = {"burn": True} if burn else {}
-                if lds_march:
-                    kwargs["lds_march"] = True
-                if hbm_march:
-                    kwargs["hbm_march"] = True
-                if simd_probe:
-                    kwargs["simd_probe"] = True
                 rep = gpu_health_report(i, quick=True, deep=sweep, bw_samples=3, **kwargs)
-                report["gpus"][str(i)].update(
+                gpu.update(
                     hbm_gbps=round(rep["hbm_gbps"], 1),
                     mfma_ok=rep["mfma_ok"],
                     cu_coverage=rep["cu_coverage"],
                     lds_errors=rep["lds_errors"],
                 )
                 if "hbm_sweep" in rep:
-                    report["gpus"][str(i)]["hbm_sweep_errors"] = rep["hbm_sweep"]["errors"]
+                    gpu["hbm_sweep_errors"] = rep["hbm_sweep"]["errors"]
                 if not rep["healthy"] or rep["hbm_gbps"] < min_hbm_gbps:
-                    report["gpus"][str(i)]["healthy"] = False
+                    gpu["healthy"] = False
                 if burn:
                     b = rep["mfma_burn"]
                     tflops = {f: round(s["tflops"], 1) for f, s in b["formats"].items()}
-                    report["gpus"][str(i)].update(
+                    gpu.update(
                         mfma_tflops=tflops,
                         mfma_burn_ok=bool(b["ok"]),
                         bad_cus=b["bad_cus"],
@@ -144,23 +145,21 @@ def collect_node_health(
                     bf16 = b["formats"].get("bf16", {}).get("tflops", 0.0)
                     slow = min_mfma_tflops is not None and bf16 < min_mfma_tflops
                     if not b["ok"] or b["bad_cus"] or slow:
-                        report["gpus"][str(i)]["healthy"] = False
+                        gpu["healthy"] = False
                 if lds_march:
                     m = rep["lds_march"]
-                    report["gpus"][str(i)].update(
+                    gpu.update(
                         lds_march_ok=bool(m["ok"]),
                         lds_gbps=round(m["gbps"], 1),
                         lds_bad_cus=[{k: c[k] for k in ("xcc", "se", "sh", "cu")}
                                      for c in m["bad_cus"]],
                     )
                     if not m["ok"] or m["bad_cus"]:
-                        report["gpus"][str(i)]["healthy"] = False
+                        gpu["healthy"] = False
                 if hbm_march:
-                    from ..ops import hbm_slow_xcds
-
                     h = rep["hbm_march"]
                     slow = hbm_slow_xcds(h["xcds"], min_xcd_ratio)
-                    report["gpus"][str(i)].update(
+                    gpu.update(
                         hbm_march_ok=bool(h["ok"] and not slow),
                         hbm_march_errors=int(h["errors"]),
                         hbm_bad_bits=list(h["bad_bits"]),
@@ -169,13 +168,12 @@ def collect_node_health(
                         slow_xcds=slow,
                     )
                     if h["first_bad"] is not None:
-                        report["gpus"][str(i)]["hbm_first_bad_offset"] = int(
-                            h["first_bad"]["offset"])
+                        gpu["hbm_first_bad_offset"] = int(h["first_bad"]["offset"])
                     if not h["skipped"] and (not h["ok"] or slow):
-                        report["gpus"][str(i)]["healthy"] = False
+                        gpu["healthy"] = False
                 if simd_probe:
                     p = rep["simd_probe"]
-                    report["gpus"][str(i)].update(
+                    gpu.update(
                         simd_probe_ok=bool(p["ok"]),
                         valu_burn_ok=bool(p["valu"]["ok"]),
                         vgpr_march_ok=bool(p["vgpr_march"]["ok"]),
@@ -183,9 +181,9 @@ def collect_node_health(
                                    for c in p["bad_simds"]],
                     )
                     if not p["ok"] or p["bad_simds"]:
-                        report["gpus"][str(i)]["healthy"] = False
+                        gpu["healthy"] = False
             except Exception as e:
-                report["gpus"][str(i)].update(healthy=False, error=str(e)[:200])
+                gpu.update(healthy=False, error=str(e)[:200])
     if probe_pairs and n >= 2:
         from ..probe import CellProbeRunner
 
@@ -332,24 +330,24 @@ class NodeHealthAgent:
             results.append(res)
         return results
 
+    def _due(self, every: int) -> bool:
+        """Is a cadence of one in `every` rounds due this round? 0 = never."""
+        return every > 0 and (self._rounds % every) == 0
+
     def run_once(self) -> dict:
         deep = (self._rounds % self.deep_every) == 0
-        sweep = (self._rounds % self.sweep_every) == 0
+        sweep = self._due(self.sweep_every)
         matrix = (self._rounds % self.p2p_matrix_every) == 0
-        burn = self.burn_every > 0 and (self._rounds % self.burn_every) == 0
-        march = self.lds_march_every > 0 and (self._rounds % self.lds_march_every) == 0
-        hbm = self.hbm_march_every > 0 and (self._rounds % self.hbm_march_every) == 0
-        simd = self.simd_probe_every > 0 and (self._rounds % self.simd_probe_every) == 0
+        # the opt-in probes ride on the deep rounds
+        kwargs = _set_flags(burn=deep and self._due(self.burn_every),
+                            lds_march=deep and self._due(self.lds_march_every),
+                            hbm_march=deep and self._due(self.hbm_march_every),
+                            simd_probe=deep and self._due(self.simd_probe_every))
         self._rounds += 1
-        kwargs = {}
-        if burn and deep:
-            kwargs = {"burn": True, "min_mfma_tflops": self.min_mfma_tflops}
-        if march and deep:
-            kwargs["lds_march"] = True
-        if hbm and deep:
-            kwargs.update(hbm_march=True, min_xcd_ratio=self.min_xcd_ratio)
-        if simd and deep:
-            kwargs["simd_probe"] = True
+        if "burn" in kwargs:
+            kwargs["min_mfma_tflops"] = self.min_mfma_tflops
+        if "hbm_march" in kwargs:
+            kwargs["min_xcd_ratio"] = self.min_xcd_ratio
         report = collect_node_health(deep=deep, probe_pairs=self.probe_pairs and deep,
                                      sweep=sweep and deep, **kwargs)
         report["node"] = self.node_name

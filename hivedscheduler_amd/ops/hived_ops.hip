@@ -24,6 +24,10 @@
 //
 // Written CDNA4-native: 64-wide wavefronts, float4 coalesced loads,
 // __builtin_amdgcn_mfma_f32_16x16x32_bf16 per-wave tiles.
+//
+// What the probes share is defined once, right below: host guards and event
+// timing (EventPair, DeviceAllocs, OwnedStream, timed_ms, warm_then_timed_ms,
+// zero_records, dispatch_int), device helpers (hw_word, wave_*, store_record8).
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include <hip/hip_runtime.h>
@@ -32,14 +36,187 @@
 #include <cstring>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #define HIP_CHECK(cmd)                                                                     \
   do {                                                                                     \
-    hipError_t e = (cmd);                                                                  \
-    TORCH_CHECK(e == hipSuccess, "HIP error: ", hipGetErrorString(e), " at ", __FILE__,    \
-                ":", __LINE__);                                                            \
+    hipError_t hip_check_e = (cmd); /* a name no argument uses */                          \
+    TORCH_CHECK(hip_check_e == hipSuccess, "HIP error: ", hipGetErrorString(hip_check_e),  \
+                " at ", __FILE__, ":", __LINE__);                                          \
   } while (0)
+
+// ---------------------------------------------------------------------------
+// Host scaffolding. The agent calls the entry points every round in a
+// long-lived process on a GPU that may be failing, so a guard owns whatever
+// they create: a check that throws leaves no event, stream or allocation behind.
+// ---------------------------------------------------------------------------
+// a start/stop event pair
+struct EventPair {
+  hipEvent_t start = nullptr, stop = nullptr;
+  EventPair() {
+    HIP_CHECK(hipEventCreate(&start));
+    hipError_t e = hipEventCreate(&stop);
+    if (e != hipSuccess) (void)hipEventDestroy(start);  // no destructor will run
+    HIP_CHECK(e);
+  }
+  ~EventPair() {
+    (void)hipEventDestroy(start);
+    (void)hipEventDestroy(stop);
+  }
+  EventPair(const EventPair&) = delete;
+  EventPair& operator=(const EventPair&) = delete;
+};
+
+// Device allocations from plain hipMalloc, freed on scope exit. free_all() is
+// the checked release of the success path, in allocation order; what a failed
+// hipFree leaves in the list, the destructor still tries.
+struct DeviceAllocs {
+  std::vector<void*> ptrs;
+  DeviceAllocs() = default;
+  ~DeviceAllocs() {
+    for (void* p : ptrs) (void)hipFree(p);
+  }
+  DeviceAllocs(const DeviceAllocs&) = delete;
+  DeviceAllocs& operator=(const DeviceAllocs&) = delete;
+  // !required: nullptr, and no error left pending, when no such block is left
+  void* alloc(size_t bytes, bool required = true) {
+    ptrs.reserve(ptrs.size() + 1);  // the push_back below cannot throw
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess && !required) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    HIP_CHECK(e);
+    ptrs.push_back(p);
+    return p;
+  }
+  void* alloc_zeroed(size_t bytes) {
+    void* p = alloc(bytes);
+    HIP_CHECK(hipMemset(p, 0, bytes));
+    return p;
+  }
+  void free_all() {
+    while (!ptrs.empty()) {
+      void* p = ptrs.front();
+      ptrs.erase(ptrs.begin());
+      HIP_CHECK(hipFree(p));
+    }
+  }
+};
+
+// a stream of our own (the p2p copy must not queue behind torch's work)
+struct OwnedStream {
+  hipStream_t s = nullptr;
+  OwnedStream() { HIP_CHECK(hipStreamCreate(&s)); }
+  ~OwnedStream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+  OwnedStream(const OwnedStream&) = delete;
+  OwnedStream& operator=(const OwnedStream&) = delete;
+  void destroy() {
+    hipStream_t mine = s;
+    s = nullptr;
+    HIP_CHECK(hipStreamDestroy(mine));
+  }
+};
+
+// Milliseconds that what `launch` enqueues on `stream` takes, between two
+// events. The torch stream is non-blocking: a legacy-stream hipMemcpy does not
+// order against it, so nothing may read what the launch wrote, or the timing,
+// before the stop event has been waited for. That wait is in here.
+template <typename F>
+static double timed_ms(hipStream_t stream, F&& launch) {
+  EventPair ev;
+  HIP_CHECK(hipEventRecord(ev.start, stream));
+  launch();
+  HIP_CHECK(hipEventRecord(ev.stop, stream));
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventSynchronize(ev.stop));
+  float ms = 0;
+  HIP_CHECK(hipEventElapsedTime(&ms, ev.start, ev.stop));
+  return (double)ms;
+}
+
+// one untimed warm-up launch (code-object load and clock ramp stay out of the
+// timing), then one timed launch
+template <typename F>
+static double warm_then_timed_ms(hipStream_t stream, F&& launch) {
+  launch();
+  HIP_CHECK(hipGetLastError());
+  return timed_ms(stream, launch);
+}
+
+// the zeroed int32 [waves, width] tensor the per-wave records land in
+static torch::Tensor zero_records(long waves, long width, torch::Device device = torch::kCUDA) {
+  return torch::zeros({waves, width}, torch::TensorOptions().dtype(torch::kInt32).device(device));
+}
+
+// f(std::integral_constant<int, I>{}) for the I in [0, N) that equals `value`:
+// a runtime enum becomes the template argument of a kernel
+template <int N, typename F>
+static void dispatch_int(int value, F&& f) {
+  if constexpr (N > 1) {
+    if (value != N - 1) return dispatch_int<N - 1>(value, f);
+  }
+  f(std::integral_constant<int, N - 1>{});
+}
+
+// ---------------------------------------------------------------------------
+// Device scaffolding.
+//
+// Placement word: where a wave runs, for the host to join a result to the
+// hardware that produced it (ops.decode_hw_word / decode_hw_simd). HW_ID
+// (gfx9-family layout): SIMD_ID[5:4], CU_ID[11:8], SH_ID[12], SE_ID[15:13];
+// XCC_ID identifies the XCD (0-7). The word is (XCC_ID << 16) | HW_ID[15:0].
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ unsigned hw_word() {
+  unsigned hwid, xcc;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  return (xcc << 16) | (hwid & 0xffff);
+}
+
+// Wave reductions with xor-butterfly shuffles: every lane ends up with the
+// result over all 64 lanes. T is unsigned (one shuffle per step) or unsigned
+// long long (two, one per half). They use no LDS of the workgroup's own.
+// Users: the burn-in's checksum and the HBM march's verify kernel. The
+// reductions of lds_march_kernel, valu_burn_kernel and vgpr_march_kernel, and
+// the one in the burn-in's round loop, stay written out on __shfl_xor: through
+// these (or lane_xor alone) the compiler allocates registers differently in
+// those kernels' timed loops (BENCHMARKS.md "Probe scaffolding").
+__device__ __forceinline__ unsigned lane_xor(unsigned v, int off) {
+  return (unsigned)__shfl_xor((int)v, off);
+}
+__device__ __forceinline__ unsigned long long lane_xor(unsigned long long v, int off) {
+  int lo = __shfl_xor((int)(unsigned)v, off);
+  int hi = __shfl_xor((int)(unsigned)(v >> 32), off);
+  return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
+}
+template <typename T> __device__ __forceinline__ T wave_add(T v) {
+  for (int off = 32; off > 0; off >>= 1) v += lane_xor(v, off);
+  return v;
+}
+template <typename T> __device__ __forceinline__ T wave_or(T v) {
+  for (int off = 32; off > 0; off >>= 1) v |= lane_xor(v, off);
+  return v;
+}
+template <typename T> __device__ __forceinline__ T wave_xor(T v) {
+  for (int off = 32; off > 0; off >>= 1) v ^= lane_xor(v, off);
+  return v;
+}
+template <typename T> __device__ __forceinline__ T wave_min(T v) {
+  for (int off = 32; off > 0; off >>= 1) v = min(v, lane_xor(v, off));
+  return v;
+}
+
+// a per-wave record of eight int32 leaves as two int4 vector stores
+__device__ __forceinline__ void store_record8(int4* __restrict__ records, int wave, int r0, int r1,
+                                              int r2, int r3, int r4, int r5, int r6, int r7) {
+  records[2 * wave] = make_int4(r0, r1, r2, r3);
+  records[2 * wave + 1] = make_int4(r4, r5, r6, r7);
+}
 
 // ---------------------------------------------------------------------------
 // HBM streaming bandwidth: c = a + 2*b (triad), float4 per lane.
@@ -70,27 +247,16 @@ double hbm_triad_gbps(long size_mb, long iters, long blocks, long threads) {
   auto b = torch::ones({bytes / 4}, opts);
   auto c = torch::empty({bytes / 4}, opts);
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
-  // warmup
-  hipLaunchKernelGGL(triad_kernel, dim3(blocks), dim3(threads), 0, stream,
-                     reinterpret_cast<const float4*>(a.data_ptr<float>()),
-                     reinterpret_cast<const float4*>(b.data_ptr<float>()),
-                     reinterpret_cast<float4*>(c.data_ptr<float>()), n);
-  hipEvent_t start, stop;
-  HIP_CHECK(hipEventCreate(&start));
-  HIP_CHECK(hipEventCreate(&stop));
-  HIP_CHECK(hipEventRecord(start, stream));
-  for (long it = 0; it < iters; it++) {
+  auto launch = [&]() {
     hipLaunchKernelGGL(triad_kernel, dim3(blocks), dim3(threads), 0, stream,
                        reinterpret_cast<const float4*>(a.data_ptr<float>()),
                        reinterpret_cast<const float4*>(b.data_ptr<float>()),
                        reinterpret_cast<float4*>(c.data_ptr<float>()), n);
-  }
-  HIP_CHECK(hipEventRecord(stop, stream));
-  HIP_CHECK(hipEventSynchronize(stop));
-  float ms = 0;
-  HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
-  HIP_CHECK(hipEventDestroy(start));
-  HIP_CHECK(hipEventDestroy(stop));
+  };
+  launch();  // warm-up, untimed
+  const double ms = timed_ms(stream, [&]() {
+    for (long it = 0; it < iters; it++) launch();
+  });
   double sec = ms / 1e3;
   return (3.0 * bytes * iters) / sec / 1e9;
 }
@@ -108,6 +274,12 @@ double hbm_triad_gbps(long size_mb, long iters, long blocks, long threads) {
 // ---------------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(8))) short frag8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+
+// the [waves, 16, 16] fp32 tiles the single-tile checks return
+static torch::Tensor tile_output(long waves, torch::Device device) {
+  return torch::empty({waves, 16, 16},
+                      torch::TensorOptions().dtype(torch::kFloat32).device(device));
+}
 
 __global__ void mfma_check_kernel(const short* __restrict__ A, const short* __restrict__ B,
                                   float* __restrict__ C, int repeats) {
@@ -142,9 +314,7 @@ torch::Tensor mfma_check(torch::Tensor A, torch::Tensor B, long blocks, long rep
   A = A.contiguous();
   B = B.contiguous();
   int threads = 256;
-  long waves = blocks * (threads / 64);
-  auto C = torch::empty({waves, 16, 16},
-                        torch::TensorOptions().dtype(torch::kFloat32).device(A.device()));
+  auto C = tile_output(blocks * (threads / 64), A.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL(mfma_check_kernel, dim3(blocks), dim3(threads), 0, stream,
                      reinterpret_cast<const short*>(A.data_ptr()),
@@ -199,9 +369,7 @@ torch::Tensor mfma_check_fp8(torch::Tensor A, torch::Tensor B, long blocks) {
   A = A.contiguous();
   B = B.contiguous();
   int threads = 256;
-  long waves = blocks * (threads / 64);
-  auto C = torch::empty({waves, 16, 16},
-                        torch::TensorOptions().dtype(torch::kFloat32).device(A.device()));
+  auto C = tile_output(blocks * (threads / 64), A.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL(mfma_check_fp8_kernel, dim3(blocks), dim3(threads), 0, stream,
                      A.data_ptr<unsigned char>(), B.data_ptr<unsigned char>(),
@@ -268,19 +436,11 @@ torch::Tensor mfma_check_mx(torch::Tensor A, torch::Tensor B, long blocks, long 
   A = A.contiguous();
   B = B.contiguous();
   int threads = 256;
-  long waves = blocks * (threads / 64);
-  auto C = torch::empty({waves, 16, 16},
-                        torch::TensorOptions().dtype(torch::kFloat32).device(A.device()));
+  auto C = tile_output(blocks * (threads / 64), A.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
-  if (fmt == 0) {
-    hipLaunchKernelGGL((mfma_check_mx_kernel<0>), dim3(blocks), dim3(threads), 0, stream,
-                       A.data_ptr<unsigned char>(), B.data_ptr<unsigned char>(),
-                       C.data_ptr<float>());
-  } else {
-    hipLaunchKernelGGL((mfma_check_mx_kernel<4>), dim3(blocks), dim3(threads), 0, stream,
-                       A.data_ptr<unsigned char>(), B.data_ptr<unsigned char>(),
-                       C.data_ptr<float>());
-  }
+  auto kernel = fmt == 0 ? mfma_check_mx_kernel<0> : mfma_check_mx_kernel<4>;
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, stream, A.data_ptr<unsigned char>(),
+                     B.data_ptr<unsigned char>(), C.data_ptr<float>());
   HIP_CHECK(hipGetLastError());
   return C;
 }
@@ -312,9 +472,9 @@ __global__ void lds_check_kernel(unsigned long long* __restrict__ errors,
 // Run the LDS slab check across a grid >> 256 CUs; returns error count.
 long lds_check(long blocks, long seed) {
   TORCH_CHECK(blocks > 0);
-  unsigned long long* errs_d = nullptr;
-  HIP_CHECK(hipMalloc(&errs_d, sizeof(unsigned long long)));
-  HIP_CHECK(hipMemset(errs_d, 0, sizeof(unsigned long long)));
+  DeviceAllocs counter;
+  unsigned long long* errs_d =
+      static_cast<unsigned long long*>(counter.alloc_zeroed(sizeof(unsigned long long)));
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL(lds_check_kernel, dim3(blocks), dim3(256), 0, stream, errs_d,
                      (unsigned long long)seed);
@@ -325,25 +485,22 @@ long lds_check(long blocks, long seed) {
   HIP_CHECK(hipStreamSynchronize(stream));
   unsigned long long errs = 0;
   HIP_CHECK(hipMemcpy(&errs, errs_d, sizeof(errs), hipMemcpyDeviceToHost));
-  HIP_CHECK(hipFree(errs_d));
+  counter.free_all();
   return (long)errs;
 }
 
 // ---------------------------------------------------------------------------
 // CU coverage: record each wave's hardware placement so the host can verify
 // that a health-check grid actually touched every CU on every XCD (a hung or
-// fused-off CU shows up as missing coverage). HW_ID (gfx9-family layout):
-// CU_ID[11:8], SH_ID[12], SE_ID[15:13]; XCC_ID identifies the XCD (0-7).
+// fused-off CU shows up as missing coverage): one hw_word() per wave.
 // ---------------------------------------------------------------------------
 __global__ void cu_coverage_kernel(unsigned* __restrict__ out) {
-  unsigned hwid, xcc;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  const unsigned place = hw_word();
   int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if ((threadIdx.x & 63) == 0) out[wave] = (xcc << 16) | (hwid & 0xffff);
+  if ((threadIdx.x & 63) == 0) out[wave] = place;
 }
 
-// Returns an int32 tensor of per-wave (XCC_ID<<16 | HW_ID) words; the host
+// Returns an int32 tensor of per-wave placement words (hw_word); the host
 // derives the set of distinct (xcc, se, sh, cu) tuples.
 torch::Tensor cu_coverage(long blocks) {
   TORCH_CHECK(blocks > 0);
@@ -374,7 +531,7 @@ torch::Tensor cu_coverage(long blocks) {
 // is chain * (A_i @ B) whatever order the hardware accumulates in.
 //
 // Lane 0 of each wave writes one int4 record:
-//   { (XCC_ID<<16)|HW_ID   (the cu_coverage_kernel encoding),
+//   { placement word (hw_word),
 //     mismatched elements over all rounds,
 //     first bad round (-1 if none),
 //     xor of all accumulator bits over all lanes and rounds }
@@ -482,9 +639,7 @@ mfma_burn_kernel(const void* __restrict__ A, const void* __restrict__ B,
   int lane = threadIdx.x & 63;
   int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   int m = lane & 15;
-  unsigned hwid, xcc;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  const unsigned place = hw_word();
 
   typename M::frag a[BURN_NACC];
   for (int i = 0; i < BURN_NACC; i++) a[i] = M::load_a(A, i * 16 + m, lane);
@@ -525,24 +680,15 @@ mfma_burn_kernel(const void* __restrict__ A, const void* __restrict__ B,
     mismatched += bad;
     if (bad && first_bad < 0) first_bad = round;
   }
-  for (int off = 32; off > 0; off >>= 1) checksum ^= (unsigned)__shfl_xor((int)checksum, off);
-  if (lane == 0)
-    records[wave] = make_int4((int)((xcc << 16) | (hwid & 0xffff)), mismatched, first_bad,
-                              (int)checksum);
-}
-
-template <int FMT>
-static void launch_mfma_burn(long blocks, hipStream_t stream, const void* A, const void* B,
-                             const float* expected, int4* records, long chain, long rounds,
-                             long inject_wave, long inject_round) {
-  hipLaunchKernelGGL((mfma_burn_kernel<FMT>), dim3(blocks), dim3(256), 0, stream, A, B, expected,
-                     records, (int)chain, (int)rounds, (int)inject_wave, (int)inject_round);
+  checksum = wave_xor(checksum);
+  if (lane == 0) records[wave] = make_int4((int)place, mismatched, first_bad, (int)checksum);
 }
 
 // A: [64,K], B: [K,16], expected: [4,16,16] fp32 (= chain * A_i @ B).
 // fmt "bf16": bf16 tensors, K=32. "fp8": uint8 raw e4m3 bytes, K=32.
 // "mx8": uint8 raw e4m3 bytes, K=128. "mx4": uint8 e2m1 codes one per byte,
-// K=128. One untimed warm-up launch, then one launch timed with HIP events.
+// K=128. One untimed warm-up launch, then one timed launch
+// (warm_then_timed_ms).
 // Returns (records [waves,4] int32, elapsed_ms of the timed launch).
 std::tuple<torch::Tensor, double> mfma_burn(torch::Tensor A, torch::Tensor B,
                                             torch::Tensor expected, const std::string& fmt,
@@ -583,50 +729,17 @@ std::tuple<torch::Tensor, double> mfma_burn(torch::Tensor A, torch::Tensor B,
   A = A.contiguous();
   B = B.contiguous();
   expected = expected.contiguous();
-  long waves = blocks * 4;
-  auto records = torch::zeros({waves, 4},
-                              torch::TensorOptions().dtype(torch::kInt32).device(A.device()));
+  auto records = zero_records(blocks * 4, 4, A.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
-  auto launch = [&]() {
-    const void* a = A.data_ptr();
-    const void* b = B.data_ptr();
-    const float* e = expected.data_ptr<float>();
-    int4* rec = reinterpret_cast<int4*>(records.data_ptr<int>());
-    switch (f) {
-      case BURN_BF16:
-        launch_mfma_burn<BURN_BF16>(blocks, stream, a, b, e, rec, chain, rounds, inject_wave,
-                                    inject_round);
-        break;
-      case BURN_FP8:
-        launch_mfma_burn<BURN_FP8>(blocks, stream, a, b, e, rec, chain, rounds, inject_wave,
-                                   inject_round);
-        break;
-      case BURN_MX8:
-        launch_mfma_burn<BURN_MX8>(blocks, stream, a, b, e, rec, chain, rounds, inject_wave,
-                                   inject_round);
-        break;
-      default:
-        launch_mfma_burn<BURN_MX4>(blocks, stream, a, b, e, rec, chain, rounds, inject_wave,
-                                   inject_round);
-    }
-  };
-  launch();  // warm-up: code-object load and clock ramp stay out of the timing
-  HIP_CHECK(hipGetLastError());
-  hipEvent_t start, stop;
-  HIP_CHECK(hipEventCreate(&start));
-  HIP_CHECK(hipEventCreate(&stop));
-  HIP_CHECK(hipEventRecord(start, stream));
-  launch();
-  HIP_CHECK(hipEventRecord(stop, stream));
-  HIP_CHECK(hipGetLastError());
-  // the torch stream is non-blocking (see lds_check): wait on the stop event
-  // before anything reads the records or the timing
-  HIP_CHECK(hipEventSynchronize(stop));
-  float ms = 0;
-  HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
-  HIP_CHECK(hipEventDestroy(start));
-  HIP_CHECK(hipEventDestroy(stop));
-  return std::make_tuple(records, (double)ms);
+  const double ms = warm_then_timed_ms(stream, [&]() {
+    dispatch_int<4>(f, [&](auto fmt_c) {
+      hipLaunchKernelGGL((mfma_burn_kernel<decltype(fmt_c)::value>), dim3(blocks), dim3(256), 0,
+                         stream, A.data_ptr(), B.data_ptr(), expected.data_ptr<float>(),
+                         reinterpret_cast<int4*>(records.data_ptr<int>()), (int)chain, (int)rounds,
+                         (int)inject_wave, (int)inject_round);
+    });
+  });
+  return std::make_tuple(records, ms);
 }
 
 // ---------------------------------------------------------------------------
@@ -658,8 +771,8 @@ std::tuple<torch::Tensor, double> mfma_burn(torch::Tensor A, torch::Tensor B,
 // the writes ds_write_b32).
 //
 // No LDS is left for a reduction: each wave reduces with shuffles and lane 0
-// writes its own record of eight int32 (two int4 vector stores):
-//   [0] (XCC_ID<<16)|HW_ID      (the cu_coverage_kernel encoding)
+// writes its own record of eight int32 (store_record8):
+//   [0] placement word (hw_word)
 //   [1] mismatched dwords over all passes
 //   [2] first bad global pass index (-1 if none)
 //   [3] lowest mismatching word index within that pass (-1 if none)
@@ -725,9 +838,7 @@ lds_march_kernel(int4* __restrict__ records, int rounds, unsigned seed, int inje
   const int t = threadIdx.x;
   const int lane = t & 63;
   const int wave = blockIdx.x * (LDS_MARCH_THREADS >> 6) + (t >> 6);
-  unsigned hwid, xcc;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  const unsigned place = hw_word();
 
   const bool inject_block_here = (int)blockIdx.x == inject_block &&
                                  (unsigned)inject_word < (unsigned)LDS_MARCH_WORDS;
@@ -799,9 +910,9 @@ lds_march_kernel(int4* __restrict__ records, int rounds, unsigned seed, int inje
       __syncthreads();
     }
   }
-  // wave reduction with shuffles; -1 as unsigned is the largest value, so an
-  // unsigned min picks the earliest pass, then the lowest word among the
-  // lanes that failed in that pass
+  // Wave reduction, written out (see the wave_* helpers for why). -1 as
+  // unsigned is the largest value, so an unsigned min picks the earliest pass,
+  // then the lowest word among the lanes that failed in that pass
   unsigned first_pass = (unsigned)s.first_pass;
   for (int off = 32; off > 0; off >>= 1) {
     s.mismatched += __shfl_xor(s.mismatched, off);
@@ -813,14 +924,12 @@ lds_march_kernel(int4* __restrict__ records, int rounds, unsigned seed, int inje
   unsigned first_word = (unsigned)s.first_pass == first_pass ? (unsigned)s.first_word : 0xFFFFFFFFu;
   for (int off = 32; off > 0; off >>= 1)
     first_word = min(first_word, (unsigned)__shfl_xor((int)first_word, off));
-  if (lane == 0) {
-    records[2 * wave] = make_int4((int)((xcc << 16) | (hwid & 0xffff)), s.mismatched,
-                                  (int)first_pass, (int)first_word);
-    records[2 * wave + 1] = make_int4((int)s.dropped, (int)s.raised, (int)checksum, 0);
-  }
+  if (lane == 0)
+    store_record8(records, wave, (int)place, s.mismatched, (int)first_pass, (int)first_word,
+                  (int)s.dropped, (int)s.raised, (int)checksum, 0);
 }
 
-// One untimed warm-up launch, then one launch timed with HIP events.
+// One untimed warm-up launch, then one timed launch (warm_then_timed_ms).
 // Returns (records [blocks*4, 8] int32, elapsed_ms of the timed launch).
 std::tuple<torch::Tensor, double> lds_march(long blocks, long rounds, long seed,
                                             long inject_block, long inject_word,
@@ -846,33 +955,15 @@ std::tuple<torch::Tensor, double> lds_march(long blocks, long rounds, long seed,
   const size_t need = LDS_MARCH_WORDS * sizeof(unsigned);
   TORCH_CHECK(prop.sharedMemPerBlock >= need, "lds_march needs ", need,
               " B of LDS per workgroup; this device offers ", prop.sharedMemPerBlock);
-  long waves = blocks * (LDS_MARCH_THREADS / 64);
-  auto records = torch::zeros({waves, 8},
-                              torch::TensorOptions().dtype(torch::kInt32).device(torch::kCUDA));
+  auto records = zero_records(blocks * (LDS_MARCH_THREADS / 64), 8);
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
-  auto launch = [&]() {
+  const double ms = warm_then_timed_ms(stream, [&]() {
     hipLaunchKernelGGL(lds_march_kernel, dim3(blocks), dim3(LDS_MARCH_THREADS), 0, stream,
                        reinterpret_cast<int4*>(records.data_ptr<int>()), (int)rounds,
                        (unsigned)seed, (int)inject_block, (int)inject_word, (int)inject_pass,
                        (int)inject_bit);
-  };
-  launch();  // warm-up: code-object load and clock ramp stay out of the timing
-  HIP_CHECK(hipGetLastError());
-  hipEvent_t start, stop;
-  HIP_CHECK(hipEventCreate(&start));
-  HIP_CHECK(hipEventCreate(&stop));
-  HIP_CHECK(hipEventRecord(start, stream));
-  launch();
-  HIP_CHECK(hipEventRecord(stop, stream));
-  HIP_CHECK(hipGetLastError());
-  // the torch stream is non-blocking (see lds_check): wait on the stop event
-  // before anything reads the records or the timing
-  HIP_CHECK(hipEventSynchronize(stop));
-  float ms = 0;
-  HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
-  HIP_CHECK(hipEventDestroy(start));
-  HIP_CHECK(hipEventDestroy(stop));
-  return std::make_tuple(records, (double)ms);
+  });
+  return std::make_tuple(records, ms);
 }
 
 // ---------------------------------------------------------------------------
@@ -909,9 +1000,8 @@ std::tuple<torch::Tensor, double> lds_march(long blocks, long rounds, long seed,
 // every wave's checksum against the majority. It can name a SIMD that
 // disagrees with the others; it CANNOT catch a fault common to all SIMDs.
 //
-// Lane 0 of each wave writes one record of eight int32 (two int4 stores):
-//   [0] (XCC_ID<<16)|HW_ID      (the cu_coverage_kernel encoding; SIMD_ID is
-//                                HW_ID[5:4] in the gfx9-family layout)
+// Lane 0 of each wave writes one record of eight int32 (store_record8):
+//   [0] placement word (hw_word; the SIMD is HW_ID[5:4])
 //   [1] mismatched lane-rounds
 //   [2] first bad round (-1 if none)
 //   [3] lowest bad lane in that round (-1 if none)
@@ -1032,9 +1122,7 @@ valu_burn_kernel(const long long* __restrict__ expected, int4* __restrict__ reco
   typedef typename V::state state;
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  unsigned hwid, xcc;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  const unsigned place = hw_word();
 
   const state seeded = (state)valu_seed_state(seed, SEC, lane);
   state want = 0;
@@ -1061,18 +1149,16 @@ valu_burn_kernel(const long long* __restrict__ expected, int4* __restrict__ reco
       }
     }
   }
+  // wave reduction, written out (see the wave_* helpers for why)
   unsigned lo = (unsigned)checksum, hi = (unsigned)((unsigned long long)checksum >> 32);
   for (int off = 32; off > 0; off >>= 1) {
     lo ^= (unsigned)__shfl_xor((int)lo, off);
     hi ^= (unsigned)__shfl_xor((int)hi, off);
   }
-  if (lane == 0) {
-    records[2 * wave] = make_int4((int)((xcc << 16) | (hwid & 0xffff)), mismatched, first_round,
-                                  first_lane);
-    records[2 * wave + 1] = make_int4((int)lo, (int)hi, 0, 0);
-  }
+  if (lane == 0)
+    store_record8(records, wave, (int)place, mismatched, first_round, first_lane, (int)lo, (int)hi,
+                  0, 0);
 }
-
 
 // ---------------------------------------------------------------------------
 // VGPR march: a timed write/read-verify of a SIMD's vector register file in
@@ -1105,8 +1191,8 @@ valu_burn_kernel(const long long* __restrict__ expected, int4* __restrict__ reco
 // around a v_accvgpr_* move it is padded with s_nop 1: that is a precaution,
 // not a measured requirement.
 //
-// Lane 0 of each wave writes one record of eight int32 (two int4 stores):
-//   [0] (XCC_ID<<16)|HW_ID
+// Lane 0 of each wave writes one record of eight int32 (store_record8):
+//   [0] placement word (hw_word)
 //   [1] mismatched (register, lane) pairs over all passes
 //   [2] first bad global pass, round*2 + polarity (-1 if none)
 //   [3] lowest mismatching register index R in that pass (-1 if none)
@@ -1166,9 +1252,7 @@ vgpr_march_kernel(int4* __restrict__ records, int rounds, unsigned seed, int inj
                   int inject_target, int inject_lane, int inject_bit, int inject_pass) {
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  unsigned hwid, xcc;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  const unsigned place = hw_word();
 
   const unsigned base = (unsigned)lane * 0x9E3779B1u;
   const unsigned flip =
@@ -1232,8 +1316,9 @@ vgpr_march_kernel(int4* __restrict__ records, int rounds, unsigned seed, int inj
     first_pass = first_here ? pass : first_pass;
     first_reg = first_here ? first : first_reg;
   }
-  // wave reduction as in lds_march_kernel: the earliest pass, then the lowest
-  // register among the lanes that failed in it
+  // Wave reduction, written out (see the wave_* helpers for why): the earliest
+  // pass by unsigned min (-1 is the largest value), then the lowest register
+  // among the lanes that failed in that pass
   unsigned fp = (unsigned)first_pass;
   for (int off = 32; off > 0; off >>= 1) {
     mism += (unsigned)__shfl_xor((int)mism, off);
@@ -1244,25 +1329,15 @@ vgpr_march_kernel(int4* __restrict__ records, int rounds, unsigned seed, int inj
   }
   unsigned fr = (unsigned)first_pass == fp ? first_reg : 0xFFFFFFFFu;
   for (int off = 32; off > 0; off >>= 1) fr = min(fr, (unsigned)__shfl_xor((int)fr, off));
-  if (lane == 0) {
-    records[2 * wave] = make_int4((int)((xcc << 16) | (hwid & 0xffff)), (int)mism, (int)fp, (int)fr);
-    records[2 * wave + 1] = make_int4((int)dropped, (int)raised, (int)sum, VGPR_MARCH_MARCHED);
-  }
-}
-
-template <int SEC>
-static void launch_valu_burn(long blocks, hipStream_t stream, const long long* expected,
-                             int4* records, long seed, long chain, long rounds, long inject_wave,
-                             long inject_round, long inject_lane, long inject_bit) {
-  hipLaunchKernelGGL((valu_burn_kernel<SEC>), dim3(blocks), dim3(256), 0, stream, expected, records,
-                     (unsigned)seed, (int)chain, (int)rounds, (int)inject_wave, (int)inject_round,
-                     (int)inject_lane, (int)inject_bit);
+  if (lane == 0)
+    store_record8(records, wave, (int)place, (int)mism, (int)fp, (int)fr, (int)dropped,
+                  (int)raised, (int)sum, VGPR_MARCH_MARCHED);
 }
 
 // expected: 64 int64 on the current device, the state every lane must reach
 // after `chain` steps (ops.valu_burn_expected); section "trans" compares
 // nothing and may pass an empty tensor. One untimed warm-up launch, then one
-// launch timed with HIP events.
+// timed launch (warm_then_timed_ms).
 // Returns (records [waves,8] int32, elapsed_ms of the timed launch).
 std::tuple<torch::Tensor, double> valu_burn(torch::Tensor expected, const std::string& section,
                                             long seed, long blocks, long chain, long rounds,
@@ -1301,54 +1376,20 @@ std::tuple<torch::Tensor, double> valu_burn(torch::Tensor expected, const std::s
     expected = expected.contiguous();
     want = reinterpret_cast<const long long*>(expected.data_ptr<int64_t>());
   }
-  long waves = blocks * 4;
-  auto records = torch::zeros(
-      {waves, 8}, torch::TensorOptions().dtype(torch::kInt32).device(torch::kCUDA, dev));
+  auto records = zero_records(blocks * 4, 8);
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
-  auto launch = [&]() {
-    int4* rec = reinterpret_cast<int4*>(records.data_ptr<int>());
-    switch (sec) {
-      case VALU_INT:
-        launch_valu_burn<VALU_INT>(blocks, stream, want, rec, seed, chain, rounds, inject_wave,
-                                   inject_round, inject_lane, inject_bit);
-        break;
-      case VALU_F32:
-        launch_valu_burn<VALU_F32>(blocks, stream, want, rec, seed, chain, rounds, inject_wave,
-                                   inject_round, inject_lane, inject_bit);
-        break;
-      case VALU_F64:
-        launch_valu_burn<VALU_F64>(blocks, stream, want, rec, seed, chain, rounds, inject_wave,
-                                   inject_round, inject_lane, inject_bit);
-        break;
-      case VALU_XLANE:
-        launch_valu_burn<VALU_XLANE>(blocks, stream, want, rec, seed, chain, rounds, inject_wave,
-                                     inject_round, inject_lane, inject_bit);
-        break;
-      default:
-        launch_valu_burn<VALU_TRANS>(blocks, stream, want, rec, seed, chain, rounds, inject_wave,
-                                     inject_round, inject_lane, inject_bit);
-    }
-  };
-  launch();  // warm-up: code-object load and clock ramp stay out of the timing
-  HIP_CHECK(hipGetLastError());
-  hipEvent_t start, stop;
-  HIP_CHECK(hipEventCreate(&start));
-  HIP_CHECK(hipEventCreate(&stop));
-  HIP_CHECK(hipEventRecord(start, stream));
-  launch();
-  HIP_CHECK(hipEventRecord(stop, stream));
-  HIP_CHECK(hipGetLastError());
-  // the torch stream is non-blocking (see lds_check): wait on the stop event
-  // before anything reads the records or the timing
-  HIP_CHECK(hipEventSynchronize(stop));
-  float ms = 0;
-  HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
-  HIP_CHECK(hipEventDestroy(start));
-  HIP_CHECK(hipEventDestroy(stop));
-  return std::make_tuple(records, (double)ms);
+  const double ms = warm_then_timed_ms(stream, [&]() {
+    dispatch_int<5>(sec, [&](auto sec_c) {
+      hipLaunchKernelGGL((valu_burn_kernel<decltype(sec_c)::value>), dim3(blocks), dim3(256), 0,
+                         stream, want, reinterpret_cast<int4*>(records.data_ptr<int>()),
+                         (unsigned)seed, (int)chain, (int)rounds, (int)inject_wave,
+                         (int)inject_round, (int)inject_lane, (int)inject_bit);
+    });
+  });
+  return std::make_tuple(records, ms);
 }
 
-// One untimed warm-up launch, then one launch timed with HIP events.
+// One untimed warm-up launch, then one timed launch (warm_then_timed_ms).
 // Returns (records [blocks*4, 8] int32, elapsed_ms of the timed launch,
 // resident workgroups per CU as the occupancy query reports them: always 1).
 std::tuple<torch::Tensor, double, long> vgpr_march(long blocks, long rounds, long seed,
@@ -1374,33 +1415,15 @@ std::tuple<torch::Tensor, double, long> vgpr_march(long blocks, long rounds, lon
   HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, vgpr_march_kernel, 256, 0));
   TORCH_CHECK(per_cu == 1, "vgpr_march needs exactly one resident workgroup per CU (one wave ",
               "per SIMD); the occupancy query reports ", per_cu);
-  long waves = blocks * 4;
-  auto records = torch::zeros({waves, 8},
-                              torch::TensorOptions().dtype(torch::kInt32).device(torch::kCUDA));
+  auto records = zero_records(blocks * 4, 8);
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
-  auto launch = [&]() {
+  const double ms = warm_then_timed_ms(stream, [&]() {
     hipLaunchKernelGGL(vgpr_march_kernel, dim3(blocks), dim3(256), 0, stream,
                        reinterpret_cast<int4*>(records.data_ptr<int>()), (int)rounds,
                        (unsigned)seed, (int)inject_wave, (int)inject_target, (int)inject_lane,
                        (int)inject_bit, (int)inject_pass);
-  };
-  launch();  // warm-up: code-object load and clock ramp stay out of the timing
-  HIP_CHECK(hipGetLastError());
-  hipEvent_t start, stop;
-  HIP_CHECK(hipEventCreate(&start));
-  HIP_CHECK(hipEventCreate(&stop));
-  HIP_CHECK(hipEventRecord(start, stream));
-  launch();
-  HIP_CHECK(hipEventRecord(stop, stream));
-  HIP_CHECK(hipGetLastError());
-  // the torch stream is non-blocking (see lds_check): wait on the stop event
-  // before anything reads the records or the timing
-  HIP_CHECK(hipEventSynchronize(stop));
-  float ms = 0;
-  HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
-  HIP_CHECK(hipEventDestroy(start));
-  HIP_CHECK(hipEventDestroy(stop));
-  return std::make_tuple(records, (double)ms, (long)per_cu);
+  });
+  return std::make_tuple(records, ms, (long)per_cu);
 }
 
 // ---------------------------------------------------------------------------
@@ -1411,11 +1434,11 @@ double p2p_gbps(int src_dev, int dst_dev, long size_mb, long iters) {
   long bytes = size_mb * 1024 * 1024;
   int canAccess = 0;
   HIP_CHECK(hipDeviceCanAccessPeer(&canAccess, dst_dev, src_dev));
-  void *src = nullptr, *dst = nullptr;
+  DeviceAllocs src_buf, dst_buf;  // one per device: below, each is freed under its own
   HIP_CHECK(hipSetDevice(src_dev));
-  HIP_CHECK(hipMalloc(&src, bytes));
+  void* src = src_buf.alloc(bytes);
   HIP_CHECK(hipSetDevice(dst_dev));
-  HIP_CHECK(hipMalloc(&dst, bytes));
+  void* dst = dst_buf.alloc(bytes);
   if (canAccess) {
     HIP_CHECK(hipSetDevice(dst_dev));
     hipError_t e = hipDeviceEnablePeerAccess(src_dev, 0);
@@ -1423,26 +1446,17 @@ double p2p_gbps(int src_dev, int dst_dev, long size_mb, long iters) {
                 "enable peer access failed: ", hipGetErrorString(e));
   }
   HIP_CHECK(hipSetDevice(src_dev));
-  hipStream_t stream;
-  HIP_CHECK(hipStreamCreate(&stream));
-  HIP_CHECK(hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, stream));  // warmup
-  hipEvent_t start, stop;
-  HIP_CHECK(hipEventCreate(&start));
-  HIP_CHECK(hipEventCreate(&stop));
-  HIP_CHECK(hipEventRecord(start, stream));
-  for (long i = 0; i < iters; i++) {
-    HIP_CHECK(hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, stream));
-  }
-  HIP_CHECK(hipEventRecord(stop, stream));
-  HIP_CHECK(hipEventSynchronize(stop));
-  float ms = 0;
-  HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
-  HIP_CHECK(hipEventDestroy(start));
-  HIP_CHECK(hipEventDestroy(stop));
-  HIP_CHECK(hipStreamDestroy(stream));
-  HIP_CHECK(hipFree(src));
+  OwnedStream stream;
+  HIP_CHECK(hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, stream.s));  // warmup
+  const double ms = timed_ms(stream.s, [&]() {
+    for (long i = 0; i < iters; i++) {
+      HIP_CHECK(hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, stream.s));
+    }
+  });
+  stream.destroy();
+  src_buf.free_all();
   HIP_CHECK(hipSetDevice(dst_dev));
-  HIP_CHECK(hipFree(dst));
+  dst_buf.free_all();
   HIP_CHECK(hipSetDevice(src_dev));
   double sec = ms / 1e3;
   return (double)bytes * iters / sec / 1e9;
@@ -1496,45 +1510,31 @@ py::dict hbm_sweep(long max_gib, long chunk_gib, long seed) {
   HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
   const long headroom = 8L << 30;
   long budget = std::min(max_gib << 30, (long)freeB - headroom);
-  unsigned long long* errs_d = nullptr;
-  HIP_CHECK(hipMalloc(&errs_d, sizeof(unsigned long long)));
-  HIP_CHECK(hipMemset(errs_d, 0, sizeof(unsigned long long)));
+  DeviceAllocs counter, chunks;
+  unsigned long long* errs_d =
+      static_cast<unsigned long long*>(counter.alloc_zeroed(sizeof(unsigned long long)));
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
-  hipEvent_t start, stop;
-  HIP_CHECK(hipEventCreate(&start));
-  HIP_CHECK(hipEventCreate(&stop));
   double write_s = 0, verify_s = 0;
   long tested = 0;
   int blocks = 8192, threads = 256;  // >> 256 CUs, fills all 8 XCDs
-  std::vector<unsigned long long*> chunks;
   for (long off = 0; off + chunk_bytes <= budget; off += chunk_bytes) {
-    unsigned long long* p = nullptr;
-    if (hipMalloc(&p, chunk_bytes) != hipSuccess) { (void)hipGetLastError(); break; }
-    chunks.push_back(p);
+    unsigned long long* p = static_cast<unsigned long long*>(chunks.alloc(chunk_bytes, false));
+    if (p == nullptr) break;
     unsigned long long chunk_seed = (unsigned long long)seed ^ (unsigned long long)off;
-    float ms = 0;
-    HIP_CHECK(hipEventRecord(start, stream));
-    hipLaunchKernelGGL(pattern_write_kernel, dim3(blocks), dim3(threads), 0, stream, p, n,
-                       chunk_seed);
-    HIP_CHECK(hipEventRecord(stop, stream));
-    HIP_CHECK(hipEventSynchronize(stop));
-    HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
-    write_s += ms / 1e3;
-    HIP_CHECK(hipEventRecord(start, stream));
-    hipLaunchKernelGGL(pattern_verify_kernel, dim3(blocks), dim3(threads), 0, stream, p, n,
-                       chunk_seed, errs_d);
-    HIP_CHECK(hipEventRecord(stop, stream));
-    HIP_CHECK(hipEventSynchronize(stop));
-    HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
-    verify_s += ms / 1e3;
+    write_s += timed_ms(stream, [&]() {
+      hipLaunchKernelGGL(pattern_write_kernel, dim3(blocks), dim3(threads), 0, stream, p, n,
+                         chunk_seed);
+    }) / 1e3;
+    verify_s += timed_ms(stream, [&]() {
+      hipLaunchKernelGGL(pattern_verify_kernel, dim3(blocks), dim3(threads), 0, stream, p, n,
+                         chunk_seed, errs_d);
+    }) / 1e3;
     tested += chunk_bytes;
   }
-  for (unsigned long long* p : chunks) HIP_CHECK(hipFree(p));
+  chunks.free_all();
   unsigned long long errs = 0;
   HIP_CHECK(hipMemcpy(&errs, errs_d, sizeof(errs), hipMemcpyDeviceToHost));
-  HIP_CHECK(hipFree(errs_d));
-  HIP_CHECK(hipEventDestroy(start));
-  HIP_CHECK(hipEventDestroy(stop));
+  counter.free_all();
   py::dict d;
   d["bytes_tested"] = (long long)tested;
   d["errors"] = (long long)errs;
@@ -1578,7 +1578,7 @@ py::dict hbm_sweep(long max_gib, long chunk_gib, long seed) {
 // Per-workgroup record, 16 x int32, four int4 vector stores by thread 0 after
 // a shuffle reduction per wave and a four-entry LDS reduction across waves
 // (a workgroup that received no tile still writes one):
-//   [0]      (XCC_ID<<16)|HW_ID of wave 0 (the cu_coverage_kernel encoding)
+//   [0]      placement word of wave 0 (hw_word)
 //   [1]      tiles this workgroup processed
 //   [2],[3]  realtime clock before the first access, lo / hi
 //   [4],[5]  realtime clock after the last access has completed and the
@@ -1610,12 +1610,6 @@ static_assert(HBM_MARCH_THREADS * 16 * HBM_MARCH_ACCESSES == HBM_MARCH_TILE_BYTE
               "a tile is threads x 16 B x accesses");
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
-__device__ __forceinline__ unsigned long long hbm_march_shfl_xor(unsigned long long v, int off) {
-  int lo = __shfl_xor((int)(unsigned)v, off);
-  int hi = __shfl_xor((int)(unsigned)(v >> 32), off);
-  return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
-}
-
 __device__ __forceinline__ int4 hbm_march_pair(unsigned long long a, unsigned long long b) {
   return make_int4((int)(unsigned)a, (int)(unsigned)(a >> 32), (int)(unsigned)b,
                    (int)(unsigned)(b >> 32));
@@ -1625,9 +1619,7 @@ __global__ void __launch_bounds__(HBM_MARCH_THREADS)
 hbm_march_write_kernel(u32x4* __restrict__ p, unsigned long long chunk_qword_base, long tiles,
                        unsigned long long seed, int invert, int4* __restrict__ records) {
   const int t = threadIdx.x;
-  unsigned hwid, xcc;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  const unsigned place = hw_word();
   const unsigned long long inv = invert ? ~0ull : 0ull;
   const unsigned long long start = wall_clock64();
   asm volatile("" ::: "memory");
@@ -1655,7 +1647,7 @@ hbm_march_write_kernel(u32x4* __restrict__ p, unsigned long long chunk_qword_bas
   const unsigned long long end = wall_clock64();
   if (t == 0) {
     int4* rec = records + 4 * (long)blockIdx.x;
-    rec[0] = make_int4((int)((xcc << 16) | (hwid & 0xffff)), done, (int)(unsigned)start,
+    rec[0] = make_int4((int)place, done, (int)(unsigned)start,
                        (int)(unsigned)(start >> 32));
     // the empty asm keeps each a global_store_dwordx4 of its own: the compiler
     // otherwise regroups the constant words across the four stores
@@ -1706,9 +1698,7 @@ hbm_march_verify_kernel(const u32x4* __restrict__ p, unsigned long long chunk_qw
                         unsigned long long* __restrict__ log_count, int max_log) {
   __shared__ unsigned long long red[HBM_MARCH_THREADS / 64][5];
   const int t = threadIdx.x;
-  unsigned hwid, xcc;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  const unsigned place = hw_word();
   const unsigned long long inv = invert ? ~0ull : 0ull;
   HbmMarchState s = {0ull, ~0ull, 0ull, 0ull, 0ull};
   const unsigned long long start = wall_clock64();
@@ -1739,13 +1729,11 @@ hbm_march_verify_kernel(const u32x4* __restrict__ p, unsigned long long chunk_qw
   // opaque to the scheduler: the reduction stays behind the clock read
   asm volatile("" : "+v"(s.mismatched), "+v"(s.first), "+v"(s.dropped), "+v"(s.raised),
                "+v"(s.sum));
-  for (int off = 32; off > 0; off >>= 1) {
-    s.mismatched += hbm_march_shfl_xor(s.mismatched, off);
-    s.first = min(s.first, hbm_march_shfl_xor(s.first, off));
-    s.dropped |= hbm_march_shfl_xor(s.dropped, off);
-    s.raised |= hbm_march_shfl_xor(s.raised, off);
-    s.sum += hbm_march_shfl_xor(s.sum, off);
-  }
+  s.mismatched = wave_add(s.mismatched);
+  s.first = wave_min(s.first);
+  s.dropped = wave_or(s.dropped);
+  s.raised = wave_or(s.raised);
+  s.sum = wave_add(s.sum);
   if ((t & 63) == 0) {
     unsigned long long* r = red[t >> 6];
     r[0] = s.mismatched;
@@ -1764,7 +1752,7 @@ hbm_march_verify_kernel(const u32x4* __restrict__ p, unsigned long long chunk_qw
       s.sum += red[w][4];
     }
     int4* rec = records + 4 * (long)blockIdx.x;
-    rec[0] = make_int4((int)((xcc << 16) | (hwid & 0xffff)), done, (int)(unsigned)start,
+    rec[0] = make_int4((int)place, done, (int)(unsigned)start,
                        (int)(unsigned)(start >> 32));
     asm volatile("" ::: "memory");  // four stores, as in the write kernel
     rec[1] = make_int4((int)(unsigned)end, (int)(unsigned)(end >> 32), (int)(unsigned)s.mismatched,
@@ -1780,24 +1768,13 @@ __global__ void hbm_march_poke_kernel(unsigned long long* __restrict__ p, long i
   if (blockIdx.x == 0 && threadIdx.x == 0) p[index] ^= 1ull << bit;
 }
 
-// frees whatever a march holds when it ends, also when a HIP_CHECK throws
-struct HbmMarchHold {
-  std::vector<void*> ptrs;
-  hipEvent_t start = nullptr, stop = nullptr;
-  ~HbmMarchHold() {
-    for (void* p : ptrs) (void)hipFree(p);
-    if (start) (void)hipEventDestroy(start);
-    if (stop) (void)hipEventDestroy(stop);
-  }
-};
-
 // March up to max_bytes of this device's HBM in chunks of chunk_bytes. Like
 // hbm_sweep, chunks come from plain hipMalloc and are all HELD until the end
 // (a free/alloc loop would get the same physical block back), the budget is
 // min(max_bytes, free - 8 GiB headroom), and an allocation failure ends the
 // march quietly. The headroom applies only above 1 GiB, so small shapes run on
 // a busy card. Per chunk four launches run in order (write p, verify, write
-// ~p, verify: pass 0 and pass 1), each bracketed by HIP events.
+// ~p, verify: pass 0 and pass 1), each timed on its own (timed_ms).
 // Returns {records int32 [launches, blocks, 16] in launch order, elapsed_ms
 // float64 [launches], log int64 [min(log_count, max_log), 4], log_count,
 // bytes_tested, chunk_bytes, chunks, skipped}; the tensors are on the host.
@@ -1820,35 +1797,20 @@ py::dict hbm_march(long max_bytes, long chunk_bytes, long seed, long blocks, lon
   const long chunk_qwords = chunk_bytes / 8;
   const size_t record_bytes = (size_t)blocks * 16 * sizeof(int);
 
-  HbmMarchHold hold;
-  auto dev_alloc = [&](size_t bytes) {
-    void* p = nullptr;
-    HIP_CHECK(hipMalloc(&p, bytes));
-    hold.ptrs.push_back(p);
-    HIP_CHECK(hipMemset(p, 0, bytes));
-    return p;
-  };
-  int4* records_d = static_cast<int4*>(dev_alloc(record_bytes));
-  long long* log_d = static_cast<long long*>(dev_alloc((size_t)std::max(max_log, 1L) * 32));
-  unsigned long long* count_d = static_cast<unsigned long long*>(dev_alloc(8));
+  DeviceAllocs hold;  // freed when the march ends, also when a HIP_CHECK throws
+  int4* records_d = static_cast<int4*>(hold.alloc_zeroed(record_bytes));
+  long long* log_d =
+      static_cast<long long*>(hold.alloc_zeroed((size_t)std::max(max_log, 1L) * 32));
+  unsigned long long* count_d = static_cast<unsigned long long*>(hold.alloc_zeroed(8));
   HIP_CHECK(hipDeviceSynchronize());  // the memsets ran on the legacy stream
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
-  HIP_CHECK(hipEventCreate(&hold.start));
-  HIP_CHECK(hipEventCreate(&hold.stop));
 
   std::vector<int> records_h;
   std::vector<double> elapsed_h;
-  // one launch, bracketed by events; its records are copied out after the
-  // stop event (the torch stream is non-blocking, see lds_check)
+  // one timed launch; its records are copied out once timed_ms has waited for
+  // the stop event
   auto timed = [&](auto&& launch) {
-    HIP_CHECK(hipEventRecord(hold.start, stream));
-    launch();
-    HIP_CHECK(hipEventRecord(hold.stop, stream));
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventSynchronize(hold.stop));
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, hold.start, hold.stop));
-    elapsed_h.push_back((double)ms);
+    elapsed_h.push_back(timed_ms(stream, launch));
     const size_t at = records_h.size();
     records_h.resize(at + (size_t)blocks * 16);
     HIP_CHECK(hipMemcpy(records_h.data() + at, records_d, record_bytes, hipMemcpyDeviceToHost));
@@ -1856,9 +1818,8 @@ py::dict hbm_march(long max_bytes, long chunk_bytes, long seed, long blocks, lon
 
   long tested = 0, chunks = 0;
   for (long off = 0; off + chunk_bytes <= budget; off += chunk_bytes) {
-    void* chunk = nullptr;
-    if (hipMalloc(&chunk, chunk_bytes) != hipSuccess) { (void)hipGetLastError(); break; }
-    hold.ptrs.push_back(chunk);
+    void* chunk = hold.alloc(chunk_bytes, false);
+    if (chunk == nullptr) break;
     u32x4* p = static_cast<u32x4*>(chunk);
     const unsigned long long base = (unsigned long long)(off / 8);
     const long local = inject_index - off / 8;
