@@ -20,14 +20,15 @@ namespace {
 // longest wait reason plus slack: one allocation, then appended to in place
 constexpr size_t kWaitReasonReserve = 128;
 
-// node -> victim pod keys; overlapping Preempting groups touching the placement
-struct Victims {
-  std::map<std::string, std::set<std::string>> byNode;
-  std::set<Group*> overlappingPreemptors;
-};
+// Preempting groups whose reservations touch a placement, each once, in the
+// order the placement's cells meet them
+using OverlappingPreemptors = std::vector<Group*>;
 
-Victims collectPreemptionVictims(const Placement<PhysicalCell>& placement) {
-  Victims v;
+// Fills *victims (see VictimList) with the pods the placement would evict.
+OverlappingPreemptors collectPreemptionVictims(const Placement<PhysicalCell>& placement,
+                                               VictimList* victims) {
+  OverlappingPreemptors overlapping;
+  victims->clear();
   for (auto& [leafNum, pods] : placement) {
     (void)leafNum;
     for (auto& pod : pods) {
@@ -37,38 +38,42 @@ Victims collectPreemptionVictims(const Placement<PhysicalCell>& placement) {
             c->usingGroup != nullptr) {
           // gang semantics: preempting any cell of a group victimizes the
           // whole group
-          for (auto& [ln, victims] : c->usingGroup->allocatedPods) {
+          for (auto& [ln, slots] : c->usingGroup->allocatedPods) {
             (void)ln;
-            for (auto& p : victims) {
-              if (p.present) v.byNode[p.node].insert(p.key);
+            for (auto& p : slots) {
+              if (p.present) victims->add(p.node, p.key);
             }
           }
         }
         if (c->state == CState::Reserving || c->state == CState::Reserved) {
-          v.overlappingPreemptors.insert(c->reservingGroup);
+          if (std::find(overlapping.begin(), overlapping.end(), c->reservingGroup) ==
+              overlapping.end()) {
+            overlapping.push_back(c->reservingGroup);
+          }
         }
       }
     }
   }
-  return v;
+  if (!victims->empty()) victims->seal();
+  return overlapping;
 }
 
-std::set<std::string> collectBadOrNonSuggestedNodes(const Placement<PhysicalCell>& placement,
-                                                    const std::set<std::string>& suggestedNodes,
-                                                    bool ignoreSuggestedNodes) {
-  std::set<std::string> bad;
+// whether the placement touches a bad node or, unless ignored, a non-suggested one
+bool usesBadOrNonSuggestedNode(const Placement<PhysicalCell>& placement,
+                               const std::set<std::string>& suggestedNodes,
+                               bool ignoreSuggestedNodes) {
   for (auto& [leafNum, pods] : placement) {
     (void)leafNum;
     for (auto& pod : pods) {
       for (PhysicalCell* c : pod) {
         if (c == nullptr) continue;
         if (!c->healthy || (!ignoreSuggestedNodes && !suggestedNodes.count(c->nodes[0]))) {
-          bad.insert(c->nodes[0]);
+          return true;
         }
       }
     }
   }
-  return bad;
+  return false;
 }
 
 std::pair<PodPlacementInfo, std::string> retrieveMissingPodPlacement(Group* g, int leafCellNum,
@@ -77,10 +82,10 @@ std::pair<PodPlacementInfo, std::string> retrieveMissingPodPlacement(Group* g, i
     (void)ln;
     for (auto& p : pods) {
       if (!p.present) continue;
-      for (auto& mbi : p.bindInfo.memberBindInfo) {
+      for (auto& mbi : p.bindInfo->memberBindInfo) {
         if (!mbi.empty() && static_cast<int>(mbi[0].leafIndices.size()) == leafCellNum &&
             podIndex < static_cast<int>(mbi.size())) {
-          return {mbi[podIndex], p.bindInfo.chain};
+          return {mbi[podIndex], p.bindInfo->chain};
         }
       }
     }
@@ -103,7 +108,7 @@ VirtualCell* retrieveVirtualCell(const Placement<PhysicalCell>& phys,
   return nullptr;
 }
 
-int getNewPodIndex(const std::vector<AllocatedPod>& pods) {
+int getNewPodIndex(const PodSlots& pods) {
   for (size_t i = 0; i < pods.size(); i++) {
     if (!pods[i].present) return static_cast<int>(i);
   }
@@ -125,7 +130,7 @@ int getAllocatedPodIndex(const BindInfo& info, int leafCellNum) {
   return -1;
 }
 
-bool allPodsReleased(const std::map<int, std::vector<AllocatedPod>>& allocatedPods) {
+bool allPodsReleased(const FlatLeafMap<PodSlots>& allocatedPods) {
   for (auto& [ln, pods] : allocatedPods) {
     (void)ln;
     for (auto& p : pods) {
@@ -143,8 +148,8 @@ bool anyBoundUnder(PhysicalCell* c) {
   return false;
 }
 
-std::unique_ptr<Group> newGroup(const PodSpec& s, GState state) {
-  auto g = std::make_unique<Group>();
+// g: default-constructed or reset
+void initGroup(Group* g, const PodSpec& s, GState state) {
   g->name = s.groupName;
   g->vc = s.vc;
   g->lazyPreemptionEnable = s.lazyPreemptionEnable;
@@ -155,15 +160,9 @@ std::unique_ptr<Group> newGroup(const PodSpec& s, GState state) {
   g->totalPodNums = s.groupPodNums;
   for (auto& [leafNum, podNum] : s.groupPodNums) {
     g->allocatedPods[leafNum].resize(podNum);
-    // filled in place: no prototype vector to copy from and throw away
-    auto& phys = g->physPlacement[leafNum];
-    phys.resize(podNum);
-    for (auto& pod : phys) pod.assign(leafNum, nullptr);
-    auto& virt = g->virtPlacement[leafNum];
-    virt.resize(podNum);
-    for (auto& pod : virt) pod.assign(leafNum, nullptr);
+    g->physPlacement[leafNum].assign(podNum, leafNum);
+    g->virtPlacement[leafNum].assign(podNum, leafNum);
   }
-  return g;
 }
 
 }  // namespace
@@ -179,7 +178,8 @@ ScheduleResult HivedCore::schedule(const PodSpec& s, const std::string& podKey,
   Placement<PhysicalCell> phys;
   Placement<VirtualCell> virt;
   bool hasVirtual = true;
-  std::map<std::string, std::set<std::string>> victims;
+  VictimList& victims = victimScratch_;
+  victims.clear();
   std::string waitReason;
   waitReason.reserve(kWaitReasonReserve);  // the reason is built by appending in place
   int podIndex = 0;
@@ -213,7 +213,7 @@ ScheduleResult HivedCore::schedule(const PodSpec& s, const std::string& podKey,
 
 ScheduleResult HivedCore::generateResult(const Placement<PhysicalCell>& phys, bool hasVirtual,
                                          const Placement<VirtualCell>& virt,
-                                         const std::map<std::string, std::set<std::string>>& victims,
+                                         const VictimList& victims,
                                          std::string&& waitReason, int currentLeafNum,
                                          int podIndex, Group* group,
                                          const std::string& groupName) {
@@ -233,14 +233,14 @@ ScheduleResult HivedCore::generateResult(const Placement<PhysicalCell>& phys, bo
     // under contention instead of herding on the first map key (reference
     // utils.go:82-103 randomizes for the same reason).
     r.kind = ScheduleResult::Kind::Preempt;
-    auto it = victims.begin();
-    std::advance(it, static_cast<long>(victimRng_() % victims.size()));
-    r.victimNode = it->first;
-    r.victimPodKeys.assign(it->second.begin(), it->second.end());
+    victims.nodeAt(victimRng_() % victims.nodeCount(), &r.victimNode, &r.victimPodKeys);
     return r;
   }
   r.kind = ScheduleResult::Kind::Bind;
-  BindInfo& info = r.bindInfo;
+  // built here once; from now on it is shared and read-only
+  auto built = std::make_shared<BindInfo>();
+  BindInfo& info = *built;
+  info.memberBindInfo.reserve(phys.size());
   for (auto& [leafNum, pods] : phys) {
     std::vector<PodPlacementInfo> placements(pods.size());
     for (size_t pi = 0; pi < pods.size(); pi++) {
@@ -285,6 +285,7 @@ ScheduleResult HivedCore::generateResult(const Placement<PhysicalCell>& phys, bo
     }
     info.memberBindInfo.push_back(std::move(placements));
   }
+  r.bindInfo = std::move(built);
   return r;
 }
 
@@ -295,10 +296,8 @@ ScheduleResult HivedCore::generateResult(const Placement<PhysicalCell>& phys, bo
 bool HivedCore::schedulePodFromExistingGroup(
     Group* g, const PodSpec& s, const std::set<std::string>& suggestedNodes, Phase phase,
     const std::string& podKey, Placement<PhysicalCell>* phys, bool* hasVirtual,
-    Placement<VirtualCell>* virt, std::map<std::string, std::set<std::string>>* victims,
+    Placement<VirtualCell>* virt, VictimList* victims,
     int* podIndex) {
-  std::set<std::string> badNodes =
-      collectBadOrNonSuggestedNodes(g->physPlacement, suggestedNodes, g->ignoreK8sSuggestedNodes);
   if (g->state == GState::Allocated) {
     *phys = g->physPlacement;
     *hasVirtual = g->hasVirtualPlacement;
@@ -314,7 +313,8 @@ bool HivedCore::schedulePodFromExistingGroup(
     return true;
   }
   // groupPreempting
-  if (phase == Phase::Preempting && !badNodes.empty()) {
+  if (phase == Phase::Preempting &&
+      usesBadOrNonSuggestedNode(g->physPlacement, suggestedNodes, g->ignoreK8sSuggestedNodes)) {
     // placement no longer fully healthy / suggested: cancel and reschedule
     deletePreemptingGroup(g, podKey);
     return false;
@@ -322,8 +322,7 @@ bool HivedCore::schedulePodFromExistingGroup(
   *phys = g->physPlacement;
   *hasVirtual = g->hasVirtualPlacement;
   *virt = g->virtPlacement;
-  Victims v = collectPreemptionVictims(g->physPlacement);
-  *victims = std::move(v.byNode);
+  collectPreemptionVictims(g->physPlacement, victims);
   g->preemptingPods.insert(podKey);
   return true;
 }
@@ -332,17 +331,16 @@ void HivedCore::schedulePodFromNewGroup(const PodSpec& s,
                                         const std::set<std::string>& suggestedNodes, Phase phase,
                                         const std::string& podKey, Placement<PhysicalCell>* phys,
                                         bool* hasVirtual, Placement<VirtualCell>* virt,
-                                        std::map<std::string, std::set<std::string>>* victims,
+                                        VictimList* victims,
                                         std::string* waitReason) {
   if (!scheduleNewAffinityGroup(s, suggestedNodes, podKey, phys, hasVirtual, virt, waitReason)) {
     phys->clear();
     return;
   }
-  Victims v = collectPreemptionVictims(*phys);
-  *victims = std::move(v.byNode);  // v.byNode is not read below
+  OverlappingPreemptors overlapping = collectPreemptionVictims(*phys, victims);
   if (phase == Phase::Preempting) {
     // cancel lower-priority preemptors whose reservations overlap ours
-    for (Group* preemptor : v.overlappingPreemptors) {
+    for (Group* preemptor : overlapping) {
       deletePreemptingGroup(preemptor, podKey);
     }
     if (!victims->empty()) {
@@ -563,11 +561,10 @@ bool HivedCore::scheduleGuaranteedGroup(SchedulingRequest& sr, Placement<Physica
     if (mapped) {
       phys->clear();
       for (auto& [leafNum, pods] : *virt) {
+        PodCells<PhysicalCell>& physPods = (*phys)[leafNum];
         for (auto& pod : pods) {
-          std::vector<PhysicalCell*> cells;
-          cells.reserve(pod.size());
-          for (VirtualCell* v : pod) cells.push_back(bindings.at(v));
-          (*phys)[leafNum].push_back(std::move(cells));
+          PhysicalCell** cells = physPods.appendPod(pod.size());
+          for (size_t i = 0; i < pod.size(); i++) cells[i] = bindings.at(pod[i]);
         }
       }
       return true;
@@ -666,21 +663,12 @@ std::map<std::string, Placement<VirtualCell>> HivedCore::tryLazyPreempt(
 bool HivedCore::scheduleOpportunisticGroup(const SchedulingRequest& sr,
                                            Placement<PhysicalCell>* phys,
                                            std::string* failedReason) {
-  Placement<Cell> generic;
-  // sr.topo: the chain's opportunistic engine (scheduleForLeafCellType)
+  // sr.topo: the chain's opportunistic engine (scheduleForLeafCellType); its
+  // view holds physical cells only, so the engine writes them as such
   if (!sr.topo->Schedule(sr.podLeafCellNums, kOpportunisticPriority, *sr.suggestedNodes,
-                         sr.ignoreSuggestedNodes, &generic, failedReason, sr.hbmBytes)) {
+                         sr.ignoreSuggestedNodes, phys, failedReason, sr.hbmBytes)) {
     failedReason->append(" when scheduling in physical cluster");
     return false;
-  }
-  phys->clear();
-  for (auto& [leafNum, pods] : generic) {
-    for (auto& pod : pods) {
-      std::vector<PhysicalCell*> cells;
-      cells.reserve(pod.size());
-      for (Cell* c : pod) cells.push_back(static_cast<PhysicalCell*>(c));
-      (*phys)[leafNum].push_back(std::move(cells));
-    }
   }
   return true;
 }
@@ -701,6 +689,18 @@ void HivedCore::deleteUnallocatedPod(const PodSpec& s, const std::string& podKey
 }
 
 void HivedCore::addAllocatedPod(const PodSpec& s, const BindInfo& info, const std::string& podKey) {
+  addAllocatedPodShared(s, info, nullptr, podKey);
+}
+
+void HivedCore::addAllocatedPod(const PodSpec& s, const std::shared_ptr<const BindInfo>& info,
+                                const std::string& podKey) {
+  addAllocatedPodShared(s, *info, &info, podKey);
+}
+
+// shared: the handle that owns info, or null for a bind info from outside
+void HivedCore::addAllocatedPodShared(const PodSpec& s, const BindInfo& info,
+                                      const std::shared_ptr<const BindInfo>* shared,
+                                      const std::string& podKey) {
   OpGuard opGuard(this);
   int podIndex = 0;
   bool releasable = true;
@@ -719,7 +719,8 @@ void HivedCore::addAllocatedPod(const PodSpec& s, const BindInfo& info, const st
       releasable = false;  // deleteAllocatedPod will not find this pod either
     }
   }
-  setPodSlot(g, s.leafCellNumber, podIndex, releasable, podKey, info);
+  setPodSlot(g, s.leafCellNumber, podIndex, releasable, podKey,
+             shared != nullptr ? *shared : std::make_shared<const BindInfo>(info));
 }
 
 void HivedCore::deleteAllocatedPod(const PodSpec& s, const BindInfo& info,
@@ -754,15 +755,15 @@ bool HivedCore::deleteAllocatedPodByKey(const std::string& podKey) {
 
 // The three writers of an allocatedPods slot; they keep podIndex_ in step.
 void HivedCore::setPodSlot(Group* g, int leafCellNum, int podIndex, bool releasable,
-                           const std::string& podKey, const BindInfo& info) {
+                           const std::string& podKey, std::shared_ptr<const BindInfo> info) {
   auto& slots = g->allocatedPods[leafCellNum];
   if (podIndex >= static_cast<int>(slots.size())) slots.resize(podIndex + 1);
   AllocatedPod& slot = slots[podIndex];
   if (slot.present && slot.key != podKey) clearPodSlot(g, leafCellNum, podIndex);
   slot.present = true;
   slot.key = podKey;
-  slot.node = info.node;
-  slot.bindInfo = info;
+  slot.node = info->node;
+  slot.bindInfo = std::move(info);
   podIndex_[podKey] = PodSlotRef{g, leafCellNum, podIndex, releasable};
 }
 
@@ -786,7 +787,37 @@ void HivedCore::eraseGroup(Group* g) {
       if (pods[i].present) clearPodSlot(g, leafNum, static_cast<int>(i));
     }
   }
-  groups_.erase(g->name);
+  auto it = groups_.find(g->name);
+  if (it == groups_.end()) return;
+  if (groupPool_.size() >= kGroupPoolMax) {
+    groups_.erase(it);
+    return;
+  }
+  GroupNode node = groups_.extract(it);
+  node.mapped()->reset();
+  groupPool_.push_back(std::move(node));
+}
+
+// A group named s.groupName, set up from the spec and entered in groups_: a
+// pooled one, reset by eraseGroup, or a new one. Both callers have just found
+// that groups_ holds no group of that name.
+Group* HivedCore::insertNewGroup(const PodSpec& s, GState state) {
+  Group* g = nullptr;
+  if (!groupPool_.empty()) {
+    GroupNode node = std::move(groupPool_.back());
+    groupPool_.pop_back();
+    node.key() = s.groupName;
+    g = node.mapped().get();
+    auto entered = groups_.insert(std::move(node));
+    if (!entered.inserted) {
+      groupPool_.push_back(std::move(entered.node));
+      throw HivedError::Internal("group " + s.groupName + " already exists");
+    }
+  } else {
+    g = (groups_[s.groupName] = std::make_unique<Group>()).get();
+  }
+  initGroup(g, s, state);
+  return g;
 }
 
 // ---------------------------------------------------------------------------
@@ -795,19 +826,15 @@ void HivedCore::eraseGroup(Group* g) {
 
 Group* HivedCore::createAllocatedGroup(const PodSpec& s, const BindInfo& info,
                                        const std::string& podKey) {
-  auto group = newGroup(s, GState::Allocated);
-  Group* g = group.get();
-  groups_[s.groupName] = std::move(group);
+  Group* g = insertNewGroup(s, GState::Allocated);
   bool shouldLazyPreempt = false;
   for (auto& mbi : info.memberBindInfo) {
     if (mbi.empty()) continue;
     int leafCellNumber = static_cast<int>(mbi[0].leafIndices.size());
     if (!g->physPlacement.count(leafCellNumber)) {
       // bind info inconsistent with the group spec; tolerate by extending
-      g->physPlacement[leafCellNumber].assign(mbi.size(),
-                                              std::vector<PhysicalCell*>(leafCellNumber, nullptr));
-      g->virtPlacement[leafCellNumber].assign(mbi.size(),
-                                              std::vector<VirtualCell*>(leafCellNumber, nullptr));
+      g->physPlacement[leafCellNumber].assign(mbi.size(), leafCellNumber);
+      g->virtPlacement[leafCellNumber].assign(mbi.size(), leafCellNumber);
       g->allocatedPods[leafCellNumber].resize(mbi.size());
     }
     for (size_t podIndex = 0; podIndex < mbi.size(); podIndex++) {
@@ -884,8 +911,7 @@ void HivedCore::deleteAllocatedGroup(Group* g, const std::string& podKey) {
 void HivedCore::createPreemptingGroup(const PodSpec& s, const Placement<PhysicalCell>& phys,
                                       const Placement<VirtualCell>& virt,
                                       const std::string& podKey) {
-  auto group = newGroup(s, GState::Preempting);
-  Group* g = group.get();
+  Group* g = insertNewGroup(s, GState::Preempting);
   g->physPlacement = phys;
   g->virtPlacement = virt;
   for (auto& [leafNum, pods] : phys) {
@@ -910,7 +936,6 @@ void HivedCore::createPreemptingGroup(const PodSpec& s, const Placement<Physical
     }
   }
   g->preemptingPods.insert(podKey);
-  groups_[s.groupName] = std::move(group);
 }
 
 void HivedCore::deletePreemptingGroup(Group* g, const std::string& podKey) {

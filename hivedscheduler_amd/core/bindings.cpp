@@ -493,11 +493,61 @@ void setItem(py::dict& d, PyObject* key, py::handle value) {
   if (PyDict_SetItem(d.ptr(), key, value.ptr()) != 0) throw py::error_already_set();
 }
 
-py::dict bindInfoToDict(const BindInfo& info) {
+// The str objects of the names a bind info is made of: node names, chain names
+// and cell-type names (and the empty type of an opportunistic leaf). They are
+// fixed when the core is built, so each is created once per core and every bind
+// info handed out refers to it, instead of a new str per name and bind. A name
+// the core does not know (a bind info that came from outside) gets a new str.
+// Held by the core and by every result it gave out, so a result that outlives
+// its core still finds it; built and released with the GIL held.
+class NameStrs {
+ public:
+  NameStrs() { add(std::string()); }
+  NameStrs(const NameStrs&) = delete;
+  NameStrs& operator=(const NameStrs&) = delete;
+  ~NameStrs() {
+    for (auto& [name, o] : strs_) {
+      (void)name;
+      Py_DECREF(o);
+    }
+  }
+  void add(const std::string& name) {
+    if (strs_.count(name)) return;
+    PyObject* o = PyUnicode_FromStringAndSize(name.data(), static_cast<Py_ssize_t>(name.size()));
+    if (o == nullptr) throw py::error_already_set();
+    strs_.emplace(name, o);
+  }
+  // a new reference
+  PyObject* get(const std::string& name) const {
+    auto it = strs_.find(name);
+    if (it == strs_.end()) {
+      PyObject* o = PyUnicode_FromStringAndSize(name.data(), static_cast<Py_ssize_t>(name.size()));
+      if (o == nullptr) throw py::error_already_set();
+      return o;
+    }
+    Py_INCREF(it->second);
+    return it->second;
+  }
+  py::object str(const std::string& name) const {
+    return py::reinterpret_steal<py::object>(get(name));
+  }
+  py::object strList(const std::vector<std::string>& v) const {
+    py::list l(v.size());
+    for (size_t i = 0; i < v.size(); i++) {
+      PyList_SET_ITEM(l.ptr(), static_cast<Py_ssize_t>(i), get(v[i]));
+    }
+    return std::move(l);
+  }
+
+ private:
+  std::unordered_map<std::string, PyObject*> strs_;
+};
+
+py::dict bindInfoToDict(const BindInfo& info, const NameStrs& names) {
   py::dict d;
-  setItem(d, N.node, pyStr(info.node));
+  setItem(d, N.node, names.str(info.node));
   setItem(d, N.leafCellIsolation, pyIntList(info.isolation));
-  setItem(d, N.cellChain, pyStr(info.chain));
+  setItem(d, N.cellChain, names.str(info.chain));
   py::list mbis(info.memberBindInfo.size());
   for (size_t m = 0; m < info.memberBindInfo.size(); m++) {
     auto& mbi = info.memberBindInfo[m];
@@ -505,9 +555,9 @@ py::dict bindInfoToDict(const BindInfo& info) {
     for (size_t p = 0; p < mbi.size(); p++) {
       auto& pl = mbi[p];
       py::dict pd;
-      setItem(pd, N.physicalNode, pyStr(pl.node));
+      setItem(pd, N.physicalNode, names.str(pl.node));
       setItem(pd, N.physicalLeafCellIndices, pyIntList(pl.leafIndices));
-      setItem(pd, N.preassignedCellTypes, pyStrList(pl.preassignedTypes));
+      setItem(pd, N.preassignedCellTypes, names.strList(pl.preassignedTypes));
       PyList_SET_ITEM(placements.ptr(), static_cast<Py_ssize_t>(p), pd.release().ptr());
     }
     py::dict md;
@@ -651,8 +701,8 @@ PodSpec parseValidatedPodSpec(py::handle spec, py::handle podKey, const std::str
 }
 
 // C++ BindInfo -> PodBindInfo object, with no dict in between; equal to
-// PodBindInfo.from_dict(bindInfoToDict(info)).
-py::object bindInfoToObject(const BindInfo& info) {
+// PodBindInfo.from_dict(bindInfoToDict(info, names)).
+py::object bindInfoToObject(const BindInfo& info, const NameStrs& names) {
   py::list mbis(info.memberBindInfo.size());
   for (size_t m = 0; m < info.memberBindInfo.size(); m++) {
     auto& mbi = info.memberBindInfo[m];
@@ -660,9 +710,9 @@ py::object bindInfoToObject(const BindInfo& info) {
     for (size_t p = 0; p < mbi.size(); p++) {
       auto& pl = mbi[p];
       py::object po = newInstance(T.PodPlacementInfo);
-      setAttr(po, N.physicalNode, pyStr(pl.node));
+      setAttr(po, N.physicalNode, names.str(pl.node));
       setAttr(po, N.physicalLeafCellIndices, pyIntList(pl.leafIndices));
-      setAttr(po, N.preassignedCellTypes, pyStrList(pl.preassignedTypes));
+      setAttr(po, N.preassignedCellTypes, names.strList(pl.preassignedTypes));
       PyList_SET_ITEM(placements.ptr(), static_cast<Py_ssize_t>(p), po.release().ptr());
     }
     py::object mo = newInstance(T.AffinityGroupMemberBindInfo);
@@ -670,9 +720,9 @@ py::object bindInfoToObject(const BindInfo& info) {
     PyList_SET_ITEM(mbis.ptr(), static_cast<Py_ssize_t>(m), mo.release().ptr());
   }
   py::object o = newInstance(T.PodBindInfo);
-  setAttr(o, N.node, pyStr(info.node));
+  setAttr(o, N.node, names.str(info.node));
   setAttr(o, N.leafCellIsolation, pyIntList(info.isolation));
-  setAttr(o, N.cellChain, pyStr(info.chain));
+  setAttr(o, N.cellChain, names.str(info.chain));
   setAttr(o, N.affinityGroupBindInfo, mbis);
   return o;
 }
@@ -690,6 +740,7 @@ struct PyScheduleResult {
   PyObject* victimPodKeys;
   PyObject* waitReason;
   hived::ScheduleResult r;
+  std::shared_ptr<const NameStrs> names;  // of the core that decided
 };
 
 void resultDealloc(PyObject* self) {
@@ -699,6 +750,7 @@ void resultDealloc(PyObject* self) {
   Py_XDECREF(o->victimPodKeys);
   Py_XDECREF(o->waitReason);
   o->r.~ScheduleResult();
+  o->names.~shared_ptr();
   Py_TYPE(self)->tp_free(self);
 }
 
@@ -734,7 +786,7 @@ PyObject* resultKind(PyObject* self, void*) {
 PyObject* resultBindInfo(PyObject* self, void*) {
   auto* o = reinterpret_cast<PyScheduleResult*>(self);
   if (o->r.kind != hived::ScheduleResult::Kind::Bind) Py_RETURN_NONE;
-  return cachedAttr(&o->bindInfo, [o] { return bindInfoToObject(o->r.bindInfo); });
+  return cachedAttr(&o->bindInfo, [o] { return bindInfoToObject(*o->r.bindInfo, *o->names); });
 }
 PyObject* resultVictimNode(PyObject* self, void*) {
   auto* o = reinterpret_cast<PyScheduleResult*>(self);
@@ -805,11 +857,12 @@ void initResultType(py::module_& m) {
   m.add_object("ScheduleResult", reinterpret_cast<PyObject*>(&ResultType));
 }
 
-py::object makeResult(hived::ScheduleResult&& r) {
+py::object makeResult(hived::ScheduleResult&& r, const std::shared_ptr<const NameStrs>& names) {
   PyScheduleResult* o = PyObject_New(PyScheduleResult, &ResultType);
   if (o == nullptr) throw py::error_already_set();
   o->bindInfo = o->victimNode = o->victimPodKeys = o->waitReason = nullptr;
   new (&o->r) hived::ScheduleResult(std::move(r));
+  new (&o->names) std::shared_ptr<const NameStrs>(names);
   return py::reinterpret_steal<py::object>(reinterpret_cast<PyObject*>(o));
 }
 
@@ -944,10 +997,20 @@ struct CoreSection {
 class PyHivedCore {
  public:
   explicit PyHivedCore(const py::dict& spec) : core_(parseClusterSpec(spec)) {
+    auto names = std::make_shared<NameStrs>();
     for (auto& node : core_.allNodes()) {
-      nodeNames_.push_back(pyStr(node));
+      names->add(node);
+      nodeNames_.push_back(names->str(node));
       allNodeSet_.insert(node);
     }
+    for (auto& chain : core_.chains()) {
+      names->add(chain);
+      for (auto& [level, type] : core_.chainLevelTypes(chain)) {
+        (void)level;
+        names->add(type);
+      }
+    }
+    nameStrs_ = std::move(names);
   }
 
   void setNodeHealthy(const std::string& node, bool healthy) {
@@ -1018,7 +1081,7 @@ class PyHivedCore {
     switch (r.kind) {
       case ScheduleResult::Kind::Bind:
         setItem(d, N.kind, N.bind);
-        setItem(d, N.bindInfo, bindInfoToDict(r.bindInfo));
+        setItem(d, N.bindInfo, bindInfoToDict(*r.bindInfo, *nameStrs_));
         break;
       case ScheduleResult::Kind::Preempt:
         setItem(d, N.kind, N.preempt);
@@ -1093,7 +1156,7 @@ class PyHivedCore {
       }
       return decided;
     }();
-    return makeResult(std::move(r));
+    return makeResult(std::move(r), nameStrs_);
   }
 
   void deleteUnallocatedPod(py::handle spec, const std::string& podKey) {
@@ -1269,6 +1332,8 @@ class PyHivedCore {
  private:
   HivedCore core_;
   std::vector<py::object> nodeNames_;
+  // node, chain and cell-type names as str objects, shared with every result
+  std::shared_ptr<const NameStrs> nameStrs_;
   // every node name, for schedule_pod(suggested_nodes=None)
   std::set<std::string> allNodeSet_;
   CoreMutex coreMutex_;

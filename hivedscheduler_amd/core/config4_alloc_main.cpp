@@ -1,6 +1,7 @@
 // Heap allocations of one HivedCore::schedule call, per kind of decision, on
 // the flagship benchmark's stream (config 4, see config4_bench_main.cpp), and
-// of what follows a bind: the commit (addAllocatedPod) and the release, by spec
+// of what follows a bind: the commit (addAllocatedPod, handed the decision's own
+// bind info handle as the fused schedule_pod(commit=True) does) and the release, by spec
 // and bind info in even steps and by pod key in odd ones. The global operator
 // new is replaced by a counting one; each count is taken around the one core
 // call, after warm-up, so reusable scratch has its size.
@@ -94,7 +95,7 @@ int main(int argc, char** argv) {
   // with the VC name cut off, so the categories are the same on every build
   std::map<std::string, Tally> tallies;
   for (int step = 0; step < warmup + steps; step++) {
-    std::vector<std::pair<int, BindInfo>> bound;
+    std::vector<std::pair<int, std::shared_ptr<const BindInfo>>> bound;
     for (int i = 0; i < kNumRequests; i++) {
       long before = gAllocations;
       ScheduleResult r = core.schedule(specs[i], keys[i], suggested, Phase::Filtering);
@@ -141,7 +142,7 @@ int main(int argc, char** argv) {
         }
       } else
 #endif
-        core.deleteAllocatedPod(specs[i], info, keys[i]);
+        core.deleteAllocatedPod(specs[i], *info, keys[i]);
       if (step >= warmup) {
         tallies[byKey ? "release (deleteAllocatedPodByKey)" : "release (deleteAllocatedPod)"].add(
             gAllocations - before);

@@ -1,7 +1,8 @@
 // Standalone driver of the flagship benchmark config (no Python): config 4,
 // 64 mixed 1/2/4-GPU requests on a 4-node x 8-MI355X cluster with the VC
 // quotas of bench.py. One step = schedule all 64 requests (a bind is committed
-// at once with addAllocatedPod, as the simulation harness does), then delete
+// at once with addAllocatedPod, handed the decision's own bind info handle as
+// the fused schedule_pod(commit=True) of the simulation harness does), then delete
 // every bound pod: by spec and bind info (deleteAllocatedPod) in even steps, by
 // pod key (deleteAllocatedPodByKey) in odd ones, so both see the same stream.
 // Reports the p50 of HivedCore::schedule per decision kind, of addAllocatedPod
@@ -77,7 +78,7 @@ int main(int argc, char** argv) {
   long binds = 0, waits = 0, preempts = 0;
   for (int step = 0; step < warmup + steps; step++) {
     bool timed = step >= warmup;
-    std::vector<std::pair<int, BindInfo>> bound;
+    std::vector<std::pair<int, std::shared_ptr<const BindInfo>>> bound;
     auto ts = Clock::now();
     for (int i = 0; i < kNumRequests; i++) {
       auto t0 = Clock::now();
@@ -123,7 +124,7 @@ int main(int argc, char** argv) {
         }
       } else
 #endif
-        core.deleteAllocatedPod(specs[i], info, keys[i]);
+        core.deleteAllocatedPod(specs[i], *info, keys[i]);
       double us = usSince(t0);
       if (timed) (byKey ? delKeyS : delS).us.push_back(us);
     }

@@ -22,6 +22,7 @@
 #include <cstddef>
 #include <map>
 #include <memory>
+#include <new>
 #include <optional>
 #include <random>
 #include <set>
@@ -211,6 +212,288 @@ void stableSortSmall(It first, It last, Less less) {
 }
 
 // ---------------------------------------------------------------------------
+// Containers keyed by a pod's leaf-cell count. A group has one to three
+// distinct counts and a node has 8 leaves, so these keep their entries inside
+// the object and touch the heap only beyond that.
+// ---------------------------------------------------------------------------
+
+// int -> V for a handful of keys (a group's leaf-cell counts, the priorities in
+// use under a cell), as a sorted small vector: the first N entries inline, all
+// of them in a heap vector beyond N. Iteration is in ascending key order,
+// exactly as std::map<int, V> gives it; generateResult emits memberBindInfo in
+// that order. It has the part of std::map's interface its users need. Unlike
+// std::map, an insertion or erasure moves the entries behind it: a reference
+// or iterator is good only until the next one.
+template <class V, size_t N = 4>
+class FlatIntMap {
+ public:
+  using value_type = std::pair<int, V>;
+  using iterator = value_type*;
+  using const_iterator = const value_type*;
+
+  FlatIntMap() {}
+  FlatIntMap(const FlatIntMap& o) : spill_(o.spill_) {
+    for (; n_ < o.n_; n_++) new (inl() + n_) value_type(o.inl()[n_]);
+  }
+  FlatIntMap(FlatIntMap&& o) noexcept : spill_(std::move(o.spill_)) {
+    for (; n_ < o.n_; n_++) new (inl() + n_) value_type(std::move(o.inl()[n_]));
+    o.clear();
+  }
+  FlatIntMap& operator=(const FlatIntMap& o) {
+    if (this == &o) return *this;
+    clear();
+    for (; n_ < o.n_; n_++) new (inl() + n_) value_type(o.inl()[n_]);
+    spill_ = o.spill_;
+    return *this;
+  }
+  FlatIntMap& operator=(FlatIntMap&& o) noexcept {
+    if (this == &o) return *this;
+    clear();
+    for (; n_ < o.n_; n_++) new (inl() + n_) value_type(std::move(o.inl()[n_]));
+    spill_ = std::move(o.spill_);
+    o.clear();
+    return *this;
+  }
+  ~FlatIntMap() { clear(); }
+
+  bool empty() const { return size() == 0; }
+  size_t size() const { return spill_.empty() ? n_ : spill_.size(); }
+  iterator begin() { return spill_.empty() ? inl() : spill_.data(); }
+  iterator end() { return begin() + size(); }
+  const_iterator begin() const { return spill_.empty() ? inl() : spill_.data(); }
+  const_iterator end() const { return begin() + size(); }
+
+  iterator find(int k) {
+    iterator it = lowerBound(k);
+    return it != end() && it->first == k ? it : end();
+  }
+  const_iterator find(int k) const { return const_cast<FlatIntMap*>(this)->find(k); }
+  size_t count(int k) const { return find(k) != end() ? 1 : 0; }
+  V& at(int k) {
+    iterator it = find(k);
+    if (it == end()) throw std::out_of_range("FlatIntMap::at");
+    return it->second;
+  }
+  const V& at(int k) const { return const_cast<FlatIntMap*>(this)->at(k); }
+  V& operator[](int k) {
+    iterator it = lowerBound(k);
+    if (it != end() && it->first == k) return it->second;
+    const size_t pos = static_cast<size_t>(it - begin());
+    if (spill_.empty() && n_ < N) {
+      if (pos == n_) {
+        new (inl() + n_) value_type(k, V{});
+      } else {
+        new (inl() + n_) value_type(std::move(inl()[n_ - 1]));
+        for (size_t i = n_ - 1; i > pos; i--) inl()[i] = std::move(inl()[i - 1]);
+        inl()[pos] = value_type(k, V{});
+      }
+      n_++;
+      return inl()[pos].second;
+    }
+    if (spill_.empty()) {
+      spill_.reserve(2 * N);
+      for (size_t i = 0; i < n_; i++) spill_.push_back(std::move(inl()[i]));
+      destroyInline();
+    }
+    return spill_.insert(spill_.begin() + static_cast<std::ptrdiff_t>(pos), value_type(k, V{}))
+        ->second;
+  }
+  size_t erase(int k) {
+    iterator it = find(k);
+    if (it == end()) return 0;
+    if (!spill_.empty()) {
+      spill_.erase(spill_.begin() + (it - spill_.data()));
+      return 1;
+    }
+    for (iterator j = it; j + 1 != end(); ++j) *j = std::move(*(j + 1));
+    inl()[--n_].~value_type();
+    return 1;
+  }
+  void clear() {
+    destroyInline();
+    spill_.clear();
+  }
+
+ private:
+  iterator lowerBound(int k) {
+    iterator it = begin();
+    for (iterator e = end(); it != e && it->first < k; ++it) {
+    }
+    return it;
+  }
+  value_type* inl() { return reinterpret_cast<value_type*>(raw_); }
+  const value_type* inl() const { return reinterpret_cast<const value_type*>(raw_); }
+  void destroyInline() {
+    while (n_ > 0) inl()[--n_].~value_type();
+  }
+  // the first n_ slots hold entries; an empty map has constructed nothing
+  alignas(value_type) unsigned char raw_[N * sizeof(value_type)];
+  size_t n_ = 0;  // entries in raw_; 0 while spill_ holds them
+  std::vector<value_type> spill_;
+};
+
+// The map under the name its main users know it by: keyed by leaf-cell count.
+template <class V, size_t N = 4>
+using FlatLeafMap = FlatIntMap<V, N>;
+
+// The leaf cells of one pod inside a PodCells block.
+template <class P>
+struct CellRow {
+  P* p = nullptr;
+  size_t n = 0;
+  P* begin() const { return p; }
+  P* end() const { return p + n; }
+  size_t size() const { return n; }
+  bool empty() const { return n == 0; }
+  P& operator[](size_t i) const { return p[i]; }
+};
+
+// pods -> leaf cells for one leaf-cell count: a pods x leaves block of cell
+// pointers in one piece, inline up to N pointers (one pod of a whole node),
+// on the heap beyond. pods[pi][li], pods.size(), pods[pi].size() and the
+// nested range-for read as they do on a vector of vectors; every pod of a
+// block has the same number of leaves.
+template <class T, size_t N = 8>
+class PodCells {
+ public:
+  using Row = CellRow<T*>;
+  using ConstRow = CellRow<T* const>;
+  template <class P>
+  class RowIter {
+   public:
+    RowIter(P* base, size_t cols, size_t i) : base_(base), cols_(cols), i_(i) {}
+    CellRow<P>& operator*() const {
+      row_ = CellRow<P>{base_ + i_ * cols_, cols_};
+      return row_;
+    }
+    RowIter& operator++() {
+      i_++;
+      return *this;
+    }
+    bool operator!=(const RowIter& o) const { return i_ != o.i_; }
+    bool operator==(const RowIter& o) const { return i_ == o.i_; }
+
+   private:
+    P* base_;
+    size_t cols_;
+    size_t i_;
+    mutable CellRow<P> row_;
+  };
+
+  PodCells() {}
+  PodCells(const PodCells& o) : heap_(o.heap_), rows_(o.rows_), cols_(o.cols_) { copyInline(o); }
+  PodCells& operator=(const PodCells& o) {
+    if (this == &o) return *this;
+    heap_ = o.heap_;
+    rows_ = o.rows_;
+    cols_ = o.cols_;
+    copyInline(o);
+    return *this;
+  }
+  PodCells(PodCells&& o) noexcept : heap_(std::move(o.heap_)), rows_(o.rows_), cols_(o.cols_) {
+    copyInline(o);
+    o.clear();
+  }
+  PodCells& operator=(PodCells&& o) noexcept {
+    if (this == &o) return *this;
+    heap_ = std::move(o.heap_);
+    rows_ = o.rows_;
+    cols_ = o.cols_;
+    copyInline(o);
+    o.clear();
+    return *this;
+  }
+
+  size_t size() const { return rows_; }
+  bool empty() const { return rows_ == 0; }
+  Row operator[](size_t pod) { return Row{data() + pod * cols_, cols_}; }
+  ConstRow operator[](size_t pod) const { return ConstRow{data() + pod * cols_, cols_}; }
+  RowIter<T*> begin() { return {data(), cols_, 0}; }
+  RowIter<T*> end() { return {data(), cols_, rows_}; }
+  RowIter<T* const> begin() const { return {data(), cols_, 0}; }
+  RowIter<T* const> end() const { return {data(), cols_, rows_}; }
+
+  void clear() {
+    heap_.clear();
+    rows_ = cols_ = 0;
+  }
+  // pods x leaves, every cell null
+  void assign(size_t pods, size_t leaves) {
+    clear();
+    rows_ = pods;
+    cols_ = leaves;
+    if (pods * leaves > N) {
+      heap_.assign(pods * leaves, nullptr);
+    } else {
+      std::fill(inl_, inl_ + pods * leaves, nullptr);
+    }
+  }
+  // One more pod with `leaves` null cells; the caller fills the row handed out.
+  T** appendPod(size_t leaves) {
+    if (rows_ == 0) cols_ = leaves;
+    if (leaves != cols_) throw std::logic_error("PodCells: pods of one block differ in size");
+    const size_t have = rows_ * cols_;
+    if (!heap_.empty() || have + cols_ > N) {
+      if (heap_.empty()) heap_.assign(inl_, inl_ + have);
+      heap_.resize(have + cols_, nullptr);
+    } else {
+      std::fill(inl_ + have, inl_ + have + cols_, nullptr);
+    }
+    rows_++;
+    return data() + have;
+  }
+
+ private:
+  T** data() { return heap_.empty() ? inl_ : heap_.data(); }
+  T* const* data() const { return heap_.empty() ? inl_ : heap_.data(); }
+  // after heap_ / rows_ / cols_ are o's: the cells o keeps inline
+  void copyInline(const PodCells& o) {
+    if (heap_.empty()) std::copy(o.inl_, o.inl_ + rows_ * cols_, inl_);
+  }
+  T* inl_[N];             // the first rows_ * cols_ are cells, the rest is unset
+  std::vector<T*> heap_;  // all cells once they outgrow inl_
+  size_t rows_ = 0;
+  size_t cols_ = 0;
+};
+
+// A vector whose first N elements live inside the object; all of them move to
+// the heap once it grows beyond N. Only what the pod slots of a group need.
+template <class T, size_t N = 1>
+class InlineVec {
+ public:
+  size_t size() const { return heap_.empty() ? n_ : heap_.size(); }
+  bool empty() const { return size() == 0; }
+  T* begin() { return heap_.empty() ? inl_ : heap_.data(); }
+  T* end() { return begin() + size(); }
+  const T* begin() const { return heap_.empty() ? inl_ : heap_.data(); }
+  const T* end() const { return begin() + size(); }
+  T& operator[](size_t i) { return begin()[i]; }
+  const T& operator[](size_t i) const { return begin()[i]; }
+  void resize(size_t n) {
+    if (heap_.empty() && n <= N) {
+      for (size_t i = n; i < n_; i++) inl_[i] = T{};
+      n_ = n;
+      return;
+    }
+    if (heap_.empty()) {
+      heap_.reserve(n);
+      for (size_t i = 0; i < n_; i++) {
+        heap_.push_back(std::move(inl_[i]));
+        inl_[i] = T{};
+      }
+      n_ = 0;
+    }
+    heap_.resize(n);
+  }
+  void clear() { resize(0); }
+
+ private:
+  T inl_[N];
+  size_t n_ = 0;  // elements in inl_; 0 while heap_ holds them
+  std::vector<T> heap_;
+};
+
+// ---------------------------------------------------------------------------
 // Cell model
 // ---------------------------------------------------------------------------
 struct Group;
@@ -230,7 +513,7 @@ struct Cell {
   int priority = kFreePriority;
   bool healthy = true;
   // priority -> used leaf-cell count (rolled up the ancestor path)
-  std::map<int, int> usedLeafAtPriority;
+  FlatIntMap<int> usedLeafAtPriority;  // iterated in ascending priority
   // count of leaves under this cell at kFreePriority, maintained by
   // setCellPriority on leaf free<->used transitions. Together with
   // usedLeafAtPriority this gives the placement engine O(#priorities)
@@ -333,8 +616,15 @@ struct AllocatedPod {
   bool present = false;
   std::string key;   // "ns/name"
   std::string node;
-  BindInfo bindInfo; // full group bind info replicated in every pod
+  // the group's full bind info as the deciding pod saw it; immutable, and
+  // shared with the ScheduleResult it was decided in (see HivedCore::addAllocatedPod)
+  std::shared_ptr<const BindInfo> bindInfo;
 };
+using PodSlots = InlineVec<AllocatedPod, 1>;
+
+// Placement = leafCellNum -> pods -> leaf cells
+template <class CellT>
+using Placement = FlatLeafMap<PodCells<CellT>>;
 
 struct LazyPreemptionStatus {
   std::string preemptor;
@@ -349,14 +639,32 @@ struct Group {
   bool gangReleaseEnable = false;
   int priority = 0;
   GState state = GState::Allocated;
-  std::map<int, int> totalPodNums;  // leafCellNum -> pod count
-  std::map<int, std::vector<AllocatedPod>> allocatedPods;
+  FlatLeafMap<int> totalPodNums;  // leafCellNum -> pod count
+  FlatLeafMap<PodSlots> allocatedPods;
   // leafCellNum -> pods -> leaf cells (entries may be null after reconfig)
-  std::map<int, std::vector<std::vector<PhysicalCell*>>> physPlacement;
+  Placement<PhysicalCell> physPlacement;
   bool hasVirtualPlacement = true;  // false for opportunistic / lazy-preempted
-  std::map<int, std::vector<std::vector<VirtualCell*>>> virtPlacement;
+  Placement<VirtualCell> virtPlacement;
   std::set<std::string> preemptingPods;  // pod keys (Preempting state only)
   std::optional<LazyPreemptionStatus> lazyStatus;
+  // back to the state of a default-constructed Group; the strings keep their
+  // capacity (HivedCore's group pool)
+  void reset() {
+    name.clear();
+    vc.clear();
+    lazyPreemptionEnable = false;
+    ignoreK8sSuggestedNodes = true;
+    gangReleaseEnable = false;
+    priority = 0;
+    state = GState::Allocated;
+    totalPodNums.clear();
+    allocatedPods.clear();
+    physPlacement.clear();
+    hasVirtualPlacement = true;
+    virtPlacement.clear();
+    preemptingPods.clear();
+    lazyStatus.reset();
+  }
 };
 
 // ---------------------------------------------------------------------------
@@ -405,7 +713,7 @@ struct PodSpec {
   bool lazyPreemptionEnable = false;
   bool ignoreK8sSuggestedNodes = true;
   std::string groupName;
-  std::map<int, int> groupPodNums;  // leafCellNum -> pod count
+  FlatLeafMap<int> groupPodNums;  // leafCellNum -> pod count
   // optional: minimum measured HBM per leaf cell (bytes); leaves below are
   // unavailable for this request (MI355X: a GPU reporting < 288 GB is sick)
   long long hbmBytesPerCell = 0;
@@ -415,18 +723,16 @@ enum class Phase { Filtering, Preempting };
 
 struct ScheduleResult {
   enum class Kind { Bind, Preempt, Wait } kind = Kind::Wait;
-  // Bind
-  BindInfo bindInfo;
+  // Bind: built once by the decision and never changed afterwards. The result
+  // owns this handle; a commit that is handed the same handle stores it in the
+  // pod's slot instead of copying, and whoever lets go last frees it.
+  std::shared_ptr<const BindInfo> bindInfo;
   // Preempt: victims on one node (gang semantics: whole victim groups)
   std::string victimNode;
   std::vector<std::string> victimPodKeys;
   // Wait
   std::string waitReason;
 };
-
-// Placement = leafCellNum -> pods -> leaf cells
-template <class CellT>
-using Placement = std::map<int, std::vector<std::vector<CellT*>>>;
 
 // One globally consistent link-clean view of a chain's free capacity:
 // `excluded` = the physical leaves dropped (per-node max independent set of
@@ -460,7 +766,7 @@ struct SchedulingRequest {
   const std::string& vc;
   const std::string& pinnedCellId;
   const std::string& groupName;
-  const std::map<int, int>& podLeafCellNums;
+  const FlatLeafMap<int>& podLeafCellNums;
   // the chain being tried (a key of cellChains_' lists or a cell's own chain)
   const std::string* chain = nullptr;
   // the VC's scheduler, resolved once per request, and the placement engine
@@ -501,11 +807,25 @@ class TopoScheduler {
   // Returns placement or empty with failedReason set. minHbmBytes > 0
   // filters out leaves whose measured HBM capacity falls short.
   // cleanWorld (optional): see SchedulingRequest::cleanWorld.
-  bool Schedule(const std::map<int, int>& podLeafCellNums, int priority,
+  // The engine places generic cells; a view holds cells of one kind, and the
+  // caller names that kind (VirtualCell for a VC's view, PhysicalCell for the
+  // opportunistic one) so that the placement is written typed, once.
+  template <class CellT>
+  bool Schedule(const FlatLeafMap<int>& podLeafCellNums, int priority,
                 const std::set<std::string>& suggestedNodes, bool ignoreSuggestedNodes,
-                Placement<Cell>* out, std::string* failedReason,
-                long long minHbmBytes = 0,
-                const CleanShapeWorld* cleanWorld = nullptr, bool honorOnly = false) const;
+                Placement<CellT>* out, std::string* failedReason, long long minHbmBytes = 0,
+                const CleanShapeWorld* cleanWorld = nullptr, bool honorOnly = false) const {
+    PlacementSink sink{out, [](void* to) { static_cast<Placement<CellT>*>(to)->clear(); },
+                       [](void* to, int leafNum, const std::vector<Cell*>& leaves) {
+                         CellT** row = (*static_cast<Placement<CellT>*>(to))[leafNum].appendPod(
+                             leaves.size());
+                         for (size_t i = 0; i < leaves.size(); i++) {
+                           row[i] = static_cast<CellT*>(leaves[i]);
+                         }
+                       }};
+    return scheduleInto(podLeafCellNums, priority, suggestedNodes, ignoreSuggestedNodes, sink,
+                        failedReason, minHbmBytes, cleanWorld, honorOnly);
+  }
 
  private:
   struct NodeView {
@@ -516,10 +836,21 @@ class TopoScheduler {
     bool healthy = true;
     bool suggested = true;
   };
+  // where a successful attempt writes its placement: one pod's leaves at a
+  // time, filed under their number
+  struct PlacementSink {
+    void* to;
+    void (*clear)(void* to);
+    void (*addPod)(void* to, int leafNum, const std::vector<Cell*>& leaves);
+  };
+  bool scheduleInto(const FlatLeafMap<int>& podLeafCellNums, int priority,
+                    const std::set<std::string>& suggestedNodes, bool ignoreSuggestedNodes,
+                    const PlacementSink& out, std::string* failedReason, long long minHbmBytes,
+                    const CleanShapeWorld* cleanWorld, bool honorOnly) const;
   bool tryScheduleAtPriority(const std::vector<int>& sortedLeafNums, int priority,
                              const std::set<std::string>& suggestedNodes, bool ignoreSuggestedNodes,
                              long long minHbmBytes, bool honorLinks,
-                             const CleanShapeWorld* cleanWorld, Placement<Cell>* out,
+                             const CleanShapeWorld* cleanWorld, const PlacementSink& out,
                              std::string* failedReason) const;
 
   std::vector<Cell*> viewCells_;
@@ -531,6 +862,7 @@ class TopoScheduler {
     std::vector<NodeView> view;
     std::vector<int> sortedLeafNums;
     std::vector<int> pickedNodeIndices;
+    std::vector<Cell*> leaves;  // of the pod being placed
   };
   mutable Scratch scratch_;
 };
@@ -554,6 +886,56 @@ struct IntraVCScheduler {
 struct BindingVertex {
   VirtualCell* cell = nullptr;
   std::vector<BindingVertex*> children;
+};
+
+// The pods a placement would evict, as (node, pod key) pairs: after seal() in
+// ascending node order and, within a node, ascending key order, each pair once.
+// That is the view a std::map<node, std::set<key>> gives: the victim node is
+// picked by its position in node order, and the keys go out in key order. The
+// strings are the victim groups' own (their AllocatedPod slots), which outlive
+// the decision that collects them; the vector keeps its capacity between
+// decisions, and one with no victims touches nothing.
+class VictimList {
+ public:
+  bool empty() const { return pods_.empty(); }
+  void clear() {
+    pods_.clear();
+    nodes_ = 0;
+  }
+  void add(const std::string& node, const std::string& key) { pods_.push_back({&node, &key}); }
+  void seal() {
+    auto less = [](const Entry& a, const Entry& b) {
+      const int c = a.first->compare(*b.first);
+      return c != 0 ? c < 0 : *a.second < *b.second;
+    };
+    auto same = [](const Entry& a, const Entry& b) {
+      return *a.first == *b.first && *a.second == *b.second;
+    };
+    std::sort(pods_.begin(), pods_.end(), less);
+    pods_.erase(std::unique(pods_.begin(), pods_.end(), same), pods_.end());
+    nodes_ = 0;
+    for (size_t i = 0; i < pods_.size(); i++) {
+      if (i == 0 || *pods_[i].first != *pods_[i - 1].first) nodes_++;
+    }
+  }
+  size_t nodeCount() const { return nodes_; }
+  // the index-th node in name order and its pod keys in key order
+  void nodeAt(size_t index, std::string* node, std::vector<std::string>* keys) const {
+    size_t at = 0;
+    size_t i = 0;
+    for (; i < pods_.size(); i++) {
+      if (i > 0 && *pods_[i].first != *pods_[i - 1].first) at++;
+      if (at == index) break;
+    }
+    *node = *pods_[i].first;
+    keys->clear();
+    for (; i < pods_.size() && *pods_[i].first == *node; i++) keys->push_back(*pods_[i].second);
+  }
+
+ private:
+  using Entry = std::pair<const std::string*, const std::string*>;
+  std::vector<Entry> pods_;
+  size_t nodes_ = 0;
 };
 
 // virtual cell -> the physical cell one mapping attempt gives it
@@ -586,7 +968,12 @@ class HivedCore {
   ScheduleResult schedule(const PodSpec& s, const std::string& podKey,
                           const std::set<std::string>& suggestedNodes, Phase phase);
   void deleteUnallocatedPod(const PodSpec& s, const std::string& podKey);
+  // Commits a pod. A bind info from outside (replay, a caller's own record) is
+  // copied once into the pod's slot; the handle of the decision's own result is
+  // stored as it is, so decision, result and slot share one BindInfo.
   void addAllocatedPod(const PodSpec& s, const BindInfo& info, const std::string& podKey);
+  void addAllocatedPod(const PodSpec& s, const std::shared_ptr<const BindInfo>& info,
+                       const std::string& podKey);
   void deleteAllocatedPod(const PodSpec& s, const BindInfo& info, const std::string& podKey);
   // deleteAllocatedPod for the spec and bind info the pod was added with, found
   // through podIndex_ instead of being handed back. Answers false, and changes
@@ -653,20 +1040,20 @@ class HivedCore {
   // --- scheduling internals ---
   ScheduleResult generateResult(const Placement<PhysicalCell>& phys, bool hasVirtual,
                                 const Placement<VirtualCell>& virt,
-                                const std::map<std::string, std::set<std::string>>& victims,
+                                const VictimList& victims,
                                 std::string&& waitReason, int currentLeafNum, int podIndex,
                                 Group* group, const std::string& groupName);
   bool schedulePodFromExistingGroup(Group* g, const PodSpec& s,
                                     const std::set<std::string>& suggestedNodes, Phase phase,
                                     const std::string& podKey, Placement<PhysicalCell>* phys,
                                     bool* hasVirtual, Placement<VirtualCell>* virt,
-                                    std::map<std::string, std::set<std::string>>* victims,
+                                    VictimList* victims,
                                     int* podIndex);
   void schedulePodFromNewGroup(const PodSpec& s, const std::set<std::string>& suggestedNodes,
                                Phase phase, const std::string& podKey,
                                Placement<PhysicalCell>* phys, bool* hasVirtual,
                                Placement<VirtualCell>* virt,
-                               std::map<std::string, std::set<std::string>>* victims,
+                               VictimList* victims,
                                std::string* waitReason);
   bool scheduleNewAffinityGroup(const PodSpec& s, const std::set<std::string>& suggestedNodes,
                                 const std::string& podKey, Placement<PhysicalCell>* phys,
@@ -691,10 +1078,14 @@ class HivedCore {
                                                                const std::string& groupName);
 
   // --- allocated-pod slots and their key index ---
+  void addAllocatedPodShared(const PodSpec& s, const BindInfo& info,
+                             const std::shared_ptr<const BindInfo>* shared,
+                             const std::string& podKey);
   void setPodSlot(Group* g, int leafCellNum, int podIndex, bool releasable,
-                  const std::string& podKey, const BindInfo& info);
+                  const std::string& podKey, std::shared_ptr<const BindInfo> info);
   void clearPodSlot(Group* g, int leafCellNum, int podIndex);
   void eraseGroup(Group* g);
+  Group* insertNewGroup(const PodSpec& s, GState state);
 
   // --- group lifecycle ---
   Group* createAllocatedGroup(const PodSpec& s, const BindInfo& info, const std::string& podKey);
@@ -768,6 +1159,20 @@ class HivedCore {
     }
   };
   MapScratch mapScratch_;
+  VictimList victimScratch_;  // of the decision in progress (schedule never nests)
+
+  // Erased groups, kept with their groups_ map node (the key string and the
+  // Group object) so that the next group costs no allocation. eraseGroup is the
+  // only way in, after every podIndex_ entry of the group is gone, and
+  // insertNewGroup the only way out; Group::reset makes a recycled group equal
+  // to a fresh one. Bounded: a burst of releases frees what exceeds it.
+  using GroupNode = std::map<std::string, std::unique_ptr<Group>>::node_type;
+  // (-DHIVED_GROUP_POOL_MAX=0 builds a core without the pool, to measure it)
+#ifndef HIVED_GROUP_POOL_MAX
+#define HIVED_GROUP_POOL_MAX 64
+#endif
+  static constexpr size_t kGroupPoolMax = HIVED_GROUP_POOL_MAX;
+  std::vector<GroupNode> groupPool_;
 
  public:
   // state (public for inspect/bindings simplicity; external mutation forbidden)

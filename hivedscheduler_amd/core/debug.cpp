@@ -65,7 +65,13 @@ void checkInvariants(const HivedCore& core) {
           }
           if (c->healthy != allHealthy) fail("healthiness roll-up at " + c->address);
           if (anyUsed && c->state != CState::Used) fail("state roll-up (Used) at " + c->address);
-          if (usedSum != c->usedLeafAtPriority) fail("usedLeafAtPriority roll-up at " + c->address);
+          const bool sameCounts =
+              usedSum.size() == c->usedLeafAtPriority.size() &&
+              std::equal(usedSum.begin(), usedSum.end(), c->usedLeafAtPriority.begin(),
+                         [](const auto& a, const auto& b) {
+                           return a.first == b.first && a.second == b.second;
+                         });
+          if (!sameCounts) fail("usedLeafAtPriority roll-up at " + c->address);
         } else if (c->freeLeavesUnder != (c->priority == kFreePriority ? 1 : 0)) {
           fail("leaf freeLeavesUnder at " + c->address);
         }

@@ -83,7 +83,7 @@ int main(int argc, char** argv) {
   lat.reserve(nreq);
   struct LivePod {
     PodSpec spec;
-    BindInfo info;
+    std::shared_ptr<const BindInfo> info;
     std::string key;
   };
   std::vector<LivePod> live;
@@ -107,7 +107,7 @@ int main(int argc, char** argv) {
       live.push_back({s, r.bindInfo, key});
     }
     if ((int)live.size() > nodes * 4) {
-      core.deleteAllocatedPod(live.front().spec, live.front().info, live.front().key);
+      core.deleteAllocatedPod(live.front().spec, *live.front().info, live.front().key);
       live.erase(live.begin());
     }
   }

@@ -748,7 +748,7 @@ bool TopoScheduler::tryScheduleAtPriority(const std::vector<int>& sortedLeafNums
                                           const std::set<std::string>& suggestedNodes,
                                           bool ignoreSuggestedNodes, long long minHbmBytes,
                                           bool honorLinks, const CleanShapeWorld* cleanWorld,
-                                          Placement<Cell>* out,
+                                          const PlacementSink& out,
                                           std::string* failedReason) const {
   // Build and sort the cluster view: healthy > suggested > same-priority used
   // (desc, packing) > higher-priority used (asc, stay away).
@@ -895,11 +895,12 @@ bool TopoScheduler::tryScheduleAtPriority(const std::vector<int>& sortedLeafNums
       }
     }
   }
-  out->clear();
+  out.clear(out.to);
+  std::vector<Cell*>& leaves = scratch_.leaves;
   for (size_t i = 0; i < sortedLeafNums.size(); i++) {
     int q = sortedLeafNums[i];
     Cell* node = cv[pickedNodeIndices[i]].c;
-    std::vector<Cell*> leaves;
+    leaves.clear();
     leaves.reserve(q);
     if (session.world != nullptr && !node->isPhysical()) {
       // world mode on a virtual view: physical-mirroring descent over
@@ -919,16 +920,16 @@ bool TopoScheduler::tryScheduleAtPriority(const std::vector<int>& sortedLeafNums
     } else {
       pickLeaves(node, q, priority, session, leaves);
     }
-    (*out)[q].push_back(std::move(leaves));
+    out.addPod(out.to, q, leaves);
   }
   return true;
 }
 
-bool TopoScheduler::Schedule(const std::map<int, int>& podLeafCellNums, int priority,
-                             const std::set<std::string>& suggestedNodes,
-                             bool ignoreSuggestedNodes, Placement<Cell>* out,
-                             std::string* failedReason, long long minHbmBytes,
-                             const CleanShapeWorld* cleanWorld, bool honorOnly) const {
+bool TopoScheduler::scheduleInto(const FlatLeafMap<int>& podLeafCellNums, int priority,
+                                 const std::set<std::string>& suggestedNodes,
+                                 bool ignoreSuggestedNodes, const PlacementSink& out,
+                                 std::string* failedReason, long long minHbmBytes,
+                                 const CleanShapeWorld* cleanWorld, bool honorOnly) const {
   // The scratch is this scheduler's own and Schedule never re-enters itself:
   // tryScheduleAtPriority and the pick* / avail* helpers it calls call no
   // scheduler, every caller (IntraVCScheduler::schedule, the opportunistic
@@ -979,24 +980,15 @@ bool TopoScheduler::Schedule(const std::map<int, int>& podLeafCellNums, int prio
 bool IntraVCScheduler::schedule(const SchedulingRequest& sr, Placement<VirtualCell>* out,
                                 std::string* failedReason) const {
   // resolved once per chain by the caller (pinned: per request)
+  // a VC's view holds virtual cells only, so the engine writes them as such
   const TopoScheduler* scheduler = sr.topo;
-  Placement<Cell> generic;
   if (scheduler == nullptr ||
       !scheduler->Schedule(sr.podLeafCellNums, sr.priority, *sr.suggestedNodes,
-                           sr.ignoreSuggestedNodes, &generic, failedReason, sr.hbmBytes,
+                           sr.ignoreSuggestedNodes, out, failedReason, sr.hbmBytes,
                            sr.cleanWorld, sr.honorLinksOnly)) {
     if (failedReason->empty()) *failedReason = "no scheduler for request";
     failedReason->append(" when scheduling in VC ").append(sr.vc);
     return false;
-  }
-  out->clear();
-  for (auto& [leafNum, pods] : generic) {
-    for (auto& pod : pods) {
-      std::vector<VirtualCell*> cells;
-      cells.reserve(pod.size());
-      for (Cell* c : pod) cells.push_back(static_cast<VirtualCell*>(c));
-      (*out)[leafNum].push_back(std::move(cells));
-    }
   }
   return true;
 }
