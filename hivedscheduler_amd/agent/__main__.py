@@ -47,6 +47,11 @@ def main() -> None:
                          "attribution) every N sweeps (on deep sweeps); 0 = never")
     ap.add_argument("--simd-probe", action="store_true",
                     help="with --local: also run the SIMD probe")
+    ap.add_argument("--scalar-probe-every", type=int, default=0,
+                    help="scalar probe (exact SALU burn, SGPR march, scalar-load check, "
+                         "per-SIMD attribution) every N sweeps (on deep sweeps); 0 = never")
+    ap.add_argument("--scalar-probe", action="store_true",
+                    help="with --local: also run the scalar probe")
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
@@ -61,7 +66,8 @@ def main() -> None:
                                      min_mfma_tflops=args.min_mfma_tflops,
                                      lds_march=args.lds_march, hbm_march=args.hbm_march,
                                      min_xcd_ratio=args.min_xcd_ratio,
-                                     simd_probe=args.simd_probe)
+                                     simd_probe=args.simd_probe,
+                                     scalar_probe=args.scalar_probe)
         if args.p2p_matrix:
             try:
                 m = p2p_link_matrix()
@@ -83,7 +89,8 @@ def main() -> None:
                             lds_march_every=args.lds_march_every,
                             hbm_march_every=args.hbm_march_every,
                             min_xcd_ratio=args.min_xcd_ratio,
-                            simd_probe_every=args.simd_probe_every)
+                            simd_probe_every=args.simd_probe_every,
+                            scalar_probe_every=args.scalar_probe_every)
     if args.once:
         import json
 

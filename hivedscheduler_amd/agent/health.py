@@ -59,6 +59,7 @@ def collect_node_health(
     hbm_march: bool = False,
     min_xcd_ratio: Optional[float] = None,
     simd_probe: bool = False,
+    scalar_probe: bool = False,
 ) -> dict:
     """One health sweep over all visible GPUs. deep=True also runs the HIP
     kernels (HBM + MFMA); sweep=True adds the 16 GiB HBM stuck-bit pattern
@@ -96,6 +97,13 @@ def collect_node_health(
     leaf bad. The march holds every SIMD's whole register file for about a
     millisecond, during which tenant waves wait.
 
+    scalar_probe=True (with deep) adds the scalar probe (the exact SALU burn,
+    the SGPR march and the scalar-load check): per GPU it records
+    `scalar_probe_ok`, `salu_burn_ok`, `sgpr_march_ok`, `scalar_load_ok` and
+    `scalar_bad_simds` (the SIMDs of any wave that computed, read back or
+    loaded wrong, as xcc, se, sh, cu, simd; a key of its own beside
+    `bad_simds`), and a failed probe marks the leaf bad.
+
     The stuck-bit scan transiently holds up to 16 GiB of HBM; on a GPU
     running tenant jobs this can make the tenant's own allocations fail.
     Keep sweep on the low-frequency cadence and prefer idle GPUs (the
@@ -117,7 +125,7 @@ def collect_node_health(
         from ..ops import gpu_health_report, hbm_slow_xcds
 
         kwargs = _set_flags(burn=burn, lds_march=lds_march, hbm_march=hbm_march,
-                            simd_probe=simd_probe)
+                            simd_probe=simd_probe, scalar_probe=scalar_probe)
         for i in range(n):
             gpu = report["gpus"][str(i)]
             try:
@@ -179,6 +187,18 @@ def collect_node_health(
                         vgpr_march_ok=bool(p["vgpr_march"]["ok"]),
                         bad_simds=[{k: c[k] for k in ("xcc", "se", "sh", "cu", "simd")}
                                    for c in p["bad_simds"]],
+                    )
+                    if not p["ok"] or p["bad_simds"]:
+                        gpu["healthy"] = False
+                if scalar_probe:
+                    p = rep["scalar_probe"]
+                    gpu.update(
+                        scalar_probe_ok=bool(p["ok"]),
+                        salu_burn_ok=bool(p["salu"]["ok"]),
+                        sgpr_march_ok=bool(p["sgpr_march"]["ok"]),
+                        scalar_load_ok=bool(p["scalar_load"]["ok"]),
+                        scalar_bad_simds=[{k: c[k] for k in ("xcc", "se", "sh", "cu", "simd")}
+                                          for c in p["bad_simds"]],
                     )
                     if not p["ok"] or p["bad_simds"]:
                         gpu["healthy"] = False
@@ -256,7 +276,7 @@ class NodeHealthAgent:
                  p2p_matrix_every: int = 30, burn_every: int = 0,
                  min_mfma_tflops: Optional[float] = None, lds_march_every: int = 0,
                  hbm_march_every: int = 0, min_xcd_ratio: Optional[float] = None,
-                 simd_probe_every: int = 0):
+                 simd_probe_every: int = 0, scalar_probe_every: int = 0):
         self.scheduler_url = scheduler_url.rstrip("/")
         self.node_name = node_name or socket.gethostname()
         self.interval_s = interval_s
@@ -287,6 +307,10 @@ class NodeHealthAgent:
         # 0 = never (tens of milliseconds per GPU, and the march takes every
         # SIMD's whole register file for about one of them)
         self.simd_probe_every = simd_probe_every
+        # scalar probe cadence (SALU burn + SGPR march + scalar-load check),
+        # same pattern; 0 = never (tens of milliseconds per GPU, during which
+        # it keeps every CU's scalar unit busy)
+        self.scalar_probe_every = scalar_probe_every
         self._rounds = 0
 
     def post_report(self, report: dict) -> bool:
@@ -342,7 +366,8 @@ class NodeHealthAgent:
         kwargs = _set_flags(burn=deep and self._due(self.burn_every),
                             lds_march=deep and self._due(self.lds_march_every),
                             hbm_march=deep and self._due(self.hbm_march_every),
-                            simd_probe=deep and self._due(self.simd_probe_every))
+                            simd_probe=deep and self._due(self.simd_probe_every),
+                            scalar_probe=deep and self._due(self.scalar_probe_every))
         self._rounds += 1
         if "burn" in kwargs:
             kwargs["min_mfma_tflops"] = self.min_mfma_tflops

@@ -5,7 +5,7 @@ extension is REQUIRED: failure to load raises (no silent eager fallback).
 
 Here: the loader, `gpu_health_report` and the single-tile MFMA checks. Each
 opt-in probe has a module of its own (mfma_burn, lds_march, hbm_march,
-simd_probe) on top of `records`; their public names are re-exported here, and
+simd_probe, scalar_probe) on top of `records`; their public names are re-exported here, and
 their report functions reach the extension through `_ops_on` below.
 """
 from __future__ import annotations
@@ -17,6 +17,12 @@ from .lds_march import (LDS_MARCH_WORDS, lds_march_block_checksum, lds_march_pat
 from .mfma_burn import (BURN_FORMATS, _burn_integers, burn_chain_limit, burn_operands,  # noqa: F401
                         mfma_burn_report, summarize_burn)
 from .records import decode_hw_simd, decode_hw_word  # noqa: F401
+from .scalar_probe import (SALU_CHAINS, SALU_SECTIONS, SGPR_MARCH_FIRST_REG,  # noqa: F401
+                           SGPR_MARCH_INJECT_REG, SGPR_MARCH_REGS, salu_burn_checksum,
+                           salu_burn_expected, salu_burn_report, salu_ctl_arms,
+                           scalar_load_pattern, scalar_load_report, scalar_probe_report,
+                           sgpr_march_pattern, sgpr_march_report, sgpr_march_wave_sum,
+                           summarize_salu_burn, summarize_scalar_load, summarize_sgpr_march)
 from .simd_probe import (VALU_EXACT_SECTIONS, VALU_SECTIONS, VGPR_MARCH_FIRST_REG,  # noqa: F401
                          VGPR_MARCH_INJECT_AGPR, VGPR_MARCH_INJECT_VGPR, VGPR_MARCH_REGS,
                          simd_probe_report, summarize_valu_burn, summarize_vgpr_march,
@@ -48,7 +54,8 @@ def _ops_on(device: int):
 
 def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
                       bw_samples: int = 1, burn: bool = False, lds_march: bool = False,
-                      hbm_march: bool = False, simd_probe: bool = False) -> dict:
+                      hbm_march: bool = False, simd_probe: bool = False,
+                      scalar_probe: bool = False) -> dict:
     """Run the health-probe kernels on one GPU and return measured facts.
 
     Feeds leaf-cell healthiness: HBM bandwidth deficit, MFMA mismatch, or
@@ -81,6 +88,12 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     burn per section, tens of milliseconds, and the register-file march,
     about a millisecond during which it holds every SIMD's whole register
     file) as report["simd_probe"] and ANDs its verdict into `healthy`. Off by
+    default, and the report is then unchanged.
+
+    scalar_probe=True adds the scalar probe (`scalar_probe_report`: the exact
+    SALU burn per section, tens of milliseconds, the SGPR march over the 70
+    registers of every wave and the scalar-load check in five widths) as
+    report["scalar_probe"] and ANDs its verdict into `healthy`. Off by
     default, and the report is then unchanged.
     """
     import torch
@@ -149,6 +162,9 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     if simd_probe:
         report["simd_probe"] = simd_probe_report(device)
         report["healthy"] = bool(report["healthy"] and report["simd_probe"]["ok"])
+    if scalar_probe:
+        report["scalar_probe"] = scalar_probe_report(device)
+        report["healthy"] = bool(report["healthy"] and report["scalar_probe"]["ok"])
     return report
 
 

@@ -16,6 +16,13 @@
 //                kernel; the SIMD of any wave that was wrong
 //  - vgpr_march: 480 of the 512 vector registers per lane of every SIMD, both
 //                bit polarities; the SIMD, register and bits of any mismatch
+//  - salu_burn:  sustained, timed scalar-ALU issue per section (32-bit, 64-bit,
+//                SCC and control flow, EXEC masks), verified bitwise in the
+//                kernel; the SIMD of any wave that was wrong
+//  - sgpr_march: s32..s101 of every wave, both bit polarities, values unique
+//                across waves; the SIMD, register and bits of any mismatch
+//  - scalar_load_check: a pattern and its complement read through the scalar
+//                data cache in all five load widths, compared on the SALU
 //  - hbm_march:  a bounded span of HBM, both bit polarities, 16 B per lane,
 //                values unique across the sweep; the offset, bits and direction
 //                of any mismatch, and a bandwidth per XCD from device clocks
@@ -1427,6 +1434,827 @@ std::tuple<torch::Tensor, double, long> vgpr_march(long blocks, long rounds, lon
 }
 
 // ---------------------------------------------------------------------------
+// Scalar probe, part 1. SALU burn: a bounded, timed, exactly verifiable run of
+// sustained scalar-ALU issue, built like the VALU burn above. A CU has ONE
+// scalar unit, shared by its four SIMDs; every kernel computes its
+// wave-uniform addresses, loop counts, branch conditions and EXEC masks on it.
+//
+// Sections s32, s64 and ctl: each wave carries SALU_CHAINS = 8 independent
+// states in SGPRs, seeded by valu_seed_state(seed, section, chain index), so
+// every wave computes the same eight values. Each round re-seeds them, applies
+// `chain` dependent steps to each and compares them on the SALU against
+// expected[0..8), which the host mirror (ops.salu_burn_expected) computes. The
+// steps are inline asm on "s" operands: in plain C++ the compiler chooses
+// between SALU and VALU and folds constants. The state derives from kernel
+// arguments and constants only, so it is wave-uniform for the compiler; the
+// wave index is made so with readfirstlane. A 64-bit operand cannot be taken
+// apart inside an asm string, so a step that needs the halves of one (the
+// add/addc pair of s64, the s_cselect_b64 of ctl) is several statements with
+// plain register-pair packing between them. What a step is made of:
+//   s32   s_mul_i32, s_mul_hi_u32, s_mul_hi_i32, the carry chain s_add_u32 /
+//         s_addc_u32 / s_sub_u32 / s_subb_u32, s_lshl/lshr_b32, s_ashr_i32,
+//         s_bfe_u32/i32, s_bcnt1_i32_b32, s_ff1_i32_b32, s_flbit_i32_b32,
+//         s_brev_b32, s_lshl{1,2,3,4}_add_u32, s_sext_i32_i8/i16,
+//         s_absdiff_i32, s_min/max_{i,u}32, s_pack_{ll,lh,hh}_b32_b16,
+//         s_bitset0/1_b32, s_andn2/orn2/nand/nor/xnor_b32
+//   s64   s_lshl/lshr_b64, s_ashr_i64, s_bfe_u64/i64, a 64-bit add from
+//         s_add_u32 + s_addc_u32, s_and/or/xor/andn2/nand/nor/xnor_b64,
+//         s_not_b64, s_brev_b64, s_wqm_b64, s_bcnt1_i32_b64, s_ff1_i32_b64,
+//         s_flbit_i32_b64, s_cmp_eq_u64 / s_cmp_lg_u64 into s_cselect_b32
+//   ctl   SCC and control flow: s_movk_i32, s_mulk_i32, s_addk_i32, the twelve
+//         s_cmp_{eq,lg,gt,ge,lt,le}_{i32,u32}, s_bitcmp0/1_b32 and the twelve
+//         s_cmpk_*, each outcome shifted into a word with s_addc_u32 d, d, d;
+//         s_cselect_b32/b64 and s_cmov_b32; then a data-dependent
+//         s_cbranch_scc0 between two different updates and an s_cbranch_scc1
+//         around a third (the mirror asserts that all four ways are taken)
+// s_absdiff_i32 gets sign-extended 16- and 8-bit operands, so its difference
+// cannot overflow; the bit-field extracts use constant fields inside the word.
+// SCC is read only after a compare or an add/sub whose carry is defined.
+//
+// Section mask is where the scalar unit meets the vector unit, in plain C++
+// (the compiler owns the VALU-writes-SGPR wait states): the state is per lane
+// as in the VALU burn (expected[0..64)). A step ballots a state bit (v_cmp
+// into an SGPR pair), takes the popcount and find-first of the mask on the
+// SALU, updates the lanes inside and outside the mask by different formulas
+// (EXEC saved, narrowed, inverted, restored) and feeds lane 0's value back
+// through v_readfirstlane.
+//
+// Lane 0 of each wave writes one record of eight int32 (store_record8):
+//   [0] placement word (hw_word)
+//   [1] mismatched chain-rounds (lane-rounds for mask)
+//   [2] first bad round (-1 if none)
+//   [3] lowest bad chain (lane) in that round (-1 if none)
+//   [4] [5] xor over chains (lanes) and rounds of the state, low and high word
+//   [6] [7] 0 (reserved)
+// As in the VALU burn the checksum cancels over an even number of rounds.
+//
+// inject_* (default -1 = off): in wave inject_wave, at round inject_round,
+// chain (lane) inject_chain has bit inject_bit xored into its state before the
+// compare. Registers only.
+//
+// The scalar unit only READS memory in this probe (expected[], the pattern of
+// part 3); everything it computes leaves the wave through store_record8, a
+// vector store.
+// ---------------------------------------------------------------------------
+enum { SALU_S32 = 0, SALU_S64 = 1, SALU_CTL = 2, SALU_MASK = 3 };
+constexpr int SALU_CHAINS = 8;
+
+__device__ __forceinline__ unsigned long long u64_of(unsigned lo, unsigned hi) {
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// A scalar load of N dwords and its wait, one asm statement with an early-clobber
+// destination: scalar loads return out of order, and the compiler knows nothing
+// of a load issued from asm. Part 3 below is built on these; the burn reads
+// `expected` with one.
+typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+typedef __attribute__((ext_vector_type(8))) unsigned u32x8;
+typedef __attribute__((ext_vector_type(16))) unsigned u32x16;
+
+
+// N dwords at byte offset byte_off (a multiple of 4*N), loaded and waited for
+template <int N> struct ScalarLoad;
+#define HVD_SCALAR_LOAD(N, T, MNEMONIC)                                                    \
+  template <> struct ScalarLoad<N> {                                                       \
+    typedef T vec;                                                                         \
+    static __device__ __forceinline__ vec load(const int* p, unsigned byte_off) {          \
+      vec v;                                                                               \
+      asm volatile(MNEMONIC " %0, %1, %2\n\ts_waitcnt lgkmcnt(0)"                          \
+                   : "=&s"(v)                                                              \
+                   : "s"(p), "s"(byte_off)                                                 \
+                   : "memory");                                                            \
+      return v;                                                                            \
+    }                                                                                      \
+  };
+HVD_SCALAR_LOAD(2, u32x2, "s_load_dwordx2")
+HVD_SCALAR_LOAD(4, u32x4, "s_load_dwordx4")
+HVD_SCALAR_LOAD(8, u32x8, "s_load_dwordx8")
+HVD_SCALAR_LOAD(16, u32x16, "s_load_dwordx16")
+#undef HVD_SCALAR_LOAD
+template <> struct ScalarLoad<1> {
+  static __device__ __forceinline__ unsigned load(const int* p, unsigned byte_off) {
+    unsigned v;
+    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(v)
+                 : "s"(p), "s"(byte_off)
+                 : "memory");
+    return v;
+  }
+};
+
+template <int SEC> struct SaluStep;
+
+template <> struct SaluStep<SALU_S32> {
+  typedef unsigned state;
+  static __device__ __forceinline__ state step(state s) {
+    unsigned a, b, c, d, e, f;
+    asm volatile(
+        "s_mul_i32 %[a], %[s], 0x9E3779B1\n\t"
+        "s_mul_hi_u32 %[b], %[s], 0x85EBCA6B\n\t"
+        "s_mul_hi_i32 %[c], %[s], 0xC2B2AE35\n\t"
+        "s_add_u32 %[a], %[a], %[b]\n\t"
+        "s_addc_u32 %[b], %[b], %[c]\n\t"
+        "s_sub_u32 %[c], %[c], %[a]\n\t"
+        "s_subb_u32 %[a], %[a], %[b]\n\t"
+        "s_addc_u32 %[c], %[c], %[s]\n\t"
+        "s_lshl_b32 %[d], %[a], %[b]\n\t"
+        "s_lshr_b32 %[e], %[c], %[a]\n\t"
+        "s_xor_b32 %[d], %[d], %[e]\n\t"
+        "s_ashr_i32 %[e], %[b], %[c]\n\t"
+        "s_add_u32 %[d], %[d], %[e]\n\t"
+        "s_bfe_u32 %[e], %[a], 0xB0007\n\t"
+        "s_xor_b32 %[d], %[d], %[e]\n\t"
+        "s_bfe_i32 %[e], %[c], 0xD0005\n\t"
+        "s_add_u32 %[d], %[d], %[e]\n\t"
+        "s_bcnt1_i32_b32 %[e], %[b]\n\t"
+        "s_lshl1_add_u32 %[d], %[e], %[d]\n\t"
+        "s_ff1_i32_b32 %[e], %[c]\n\t"
+        "s_lshl2_add_u32 %[d], %[e], %[d]\n\t"
+        "s_flbit_i32_b32 %[e], %[a]\n\t"
+        "s_lshl3_add_u32 %[d], %[e], %[d]\n\t"
+        "s_brev_b32 %[e], %[b]\n\t"
+        "s_lshl4_add_u32 %[d], %[e], %[d]\n\t"
+        "s_xor_b32 %[d], %[d], %[e]\n\t"
+        "s_sext_i32_i16 %[e], %[a]\n\t"
+        "s_sext_i32_i8 %[f], %[c]\n\t"
+        "s_absdiff_i32 %[e], %[e], %[f]\n\t"
+        "s_add_u32 %[d], %[d], %[e]\n\t"
+        "s_min_i32 %[e], %[a], %[b]\n\t"
+        "s_max_i32 %[f], %[a], %[c]\n\t"
+        "s_xor_b32 %[e], %[e], %[f]\n\t"
+        "s_min_u32 %[f], %[b], %[c]\n\t"
+        "s_add_u32 %[e], %[e], %[f]\n\t"
+        "s_max_u32 %[f], %[a], %[d]\n\t"
+        "s_xor_b32 %[e], %[e], %[f]\n\t"
+        "s_add_u32 %[d], %[d], %[e]\n\t"
+        "s_pack_ll_b32_b16 %[e], %[a], %[b]\n\t"
+        "s_pack_lh_b32_b16 %[f], %[b], %[c]\n\t"
+        "s_xor_b32 %[e], %[e], %[f]\n\t"
+        "s_pack_hh_b32_b16 %[f], %[c], %[a]\n\t"
+        "s_add_u32 %[e], %[e], %[f]\n\t"
+        "s_xor_b32 %[d], %[d], %[e]\n\t"
+        "s_mov_b32 %[e], %[c]\n\t"
+        "s_bitset0_b32 %[e], %[a]\n\t"
+        "s_bitset1_b32 %[e], %[b]\n\t"
+        "s_add_u32 %[d], %[d], %[e]\n\t"
+        "s_andn2_b32 %[e], %[a], %[b]\n\t"
+        "s_orn2_b32 %[f], %[b], %[c]\n\t"
+        "s_xor_b32 %[e], %[e], %[f]\n\t"
+        "s_nand_b32 %[f], %[c], %[a]\n\t"
+        "s_add_u32 %[e], %[e], %[f]\n\t"
+        "s_nor_b32 %[f], %[a], %[d]\n\t"
+        "s_xor_b32 %[e], %[e], %[f]\n\t"
+        "s_xnor_b32 %[f], %[b], %[d]\n\t"
+        "s_add_u32 %[e], %[e], %[f]\n\t"
+        "s_xor_b32 %[d], %[d], %[e]\n\t"
+        "s_add_u32 %[s], %[d], 0x7F4A7C15\n\t"
+        : [s] "+s"(s), [a] "=&s"(a), [b] "=&s"(b), [c] "=&s"(c), [d] "=&s"(d), [e] "=&s"(e),
+          [f] "=&s"(f)
+        :
+        : "scc");
+    return s;
+  }
+};
+
+template <> struct SaluStep<SALU_S64> {
+  typedef unsigned long long state;
+  static __device__ __forceinline__ state step(state s) {
+    unsigned long long A, B, C, D, E, F;
+    asm volatile(
+        "s_lshl_b64 %[A], %[s], 13\n\t"
+        "s_lshr_b64 %[B], %[s], 7\n\t"
+        "s_xor_b64 %[A], %[A], %[B]\n\t"
+        "s_ashr_i64 %[B], %[s], 17\n\t"
+        "s_xor_b64 %[A], %[A], %[B]\n\t"
+        "s_bfe_u64 %[B], %[s], 0x280009\n\t"
+        "s_bfe_i64 %[C], %[A], 0x1D0011\n\t"
+        : [A] "=&s"(A), [B] "=&s"(B), [C] "=&s"(C)
+        : [s] "s"(s)
+        : "scc");
+    // A += B, the 64-bit add of two register pairs
+    unsigned alo = (unsigned)A, ahi = (unsigned)(A >> 32);
+    asm volatile(
+        "s_add_u32 %[alo], %[alo], %[blo]\n\t"
+        "s_addc_u32 %[ahi], %[ahi], %[bhi]\n\t"
+        : [alo] "+s"(alo), [ahi] "+s"(ahi)
+        : [blo] "s"((unsigned)B), [bhi] "s"((unsigned)(B >> 32))
+        : "scc");
+    A = u64_of(alo, ahi);
+    unsigned e, f, g, h;
+    asm volatile(
+        "s_and_b64 %[D], %[A], %[C]\n\t"
+        "s_or_b64 %[E], %[B], %[C]\n\t"
+        "s_xor_b64 %[D], %[D], %[E]\n\t"
+        "s_andn2_b64 %[E], %[A], %[B]\n\t"
+        "s_xor_b64 %[D], %[D], %[E]\n\t"
+        "s_nand_b64 %[E], %[s], %[C]\n\t"
+        "s_xor_b64 %[D], %[D], %[E]\n\t"
+        "s_nor_b64 %[E], %[A], %[s]\n\t"
+        "s_xor_b64 %[D], %[D], %[E]\n\t"
+        "s_xnor_b64 %[E], %[B], %[s]\n\t"
+        "s_xor_b64 %[D], %[D], %[E]\n\t"
+        "s_not_b64 %[E], %[C]\n\t"
+        "s_brev_b64 %[E], %[E]\n\t"
+        "s_xor_b64 %[D], %[D], %[E]\n\t"
+        "s_wqm_b64 %[E], %[B]\n\t"
+        "s_xor_b64 %[D], %[D], %[E]\n\t"
+        "s_bcnt1_i32_b64 %[e], %[A]\n\t"
+        "s_ff1_i32_b64 %[f], %[D]\n\t"
+        "s_flbit_i32_b64 %[g], %[C]\n\t"
+        "s_bfe_u64 %[E], %[s], 0x10000\n\t"
+        "s_bfe_u64 %[F], %[A], 0x10003\n\t"
+        "s_cmp_eq_u64 %[E], %[F]\n\t"
+        "s_cselect_b32 %[h], %[e], %[f]\n\t"
+        "s_bfe_u64 %[F], %[B], 0x10005\n\t"
+        "s_cmp_lg_u64 %[E], %[F]\n\t"
+        "s_cselect_b32 %[g], %[g], %[e]\n\t"
+        "s_lshl_b32 %[e], %[e], 8\n\t"
+        "s_xor_b32 %[e], %[e], %[f]\n\t"
+        : [D] "=&s"(D), [E] "=&s"(E), [F] "=&s"(F), [e] "=&s"(e), [f] "=&s"(f), [g] "=&s"(g),
+          [h] "=&s"(h)
+        : [s] "s"(s), [A] "s"(A), [B] "s"(B), [C] "s"(C)
+        : "scc");
+    unsigned dlo = (unsigned)D, dhi = (unsigned)(D >> 32);
+    asm volatile(
+        "s_add_u32 %[dlo], %[dlo], %[h]\n\t"
+        "s_addc_u32 %[dhi], %[dhi], %[g]\n\t"
+        "s_xor_b32 %[dhi], %[dhi], %[e]\n\t"
+        "s_add_u32 %[dlo], %[dlo], 0x7F4A7C15\n\t"
+        "s_addc_u32 %[dhi], %[dhi], 0x9E3779B9\n\t"
+        : [dlo] "+s"(dlo), [dhi] "+s"(dhi)
+        : [h] "s"(h), [g] "s"(g), [e] "s"(e)
+        : "scc");
+    return u64_of(dlo, dhi);
+  }
+};
+
+template <> struct SaluStep<SALU_CTL> {
+  typedef unsigned state;
+  static __device__ __forceinline__ state step(state s) {
+    unsigned a, b;
+    asm volatile(
+        "s_mov_b32 %[a], %[s]\n\t"
+        "s_mulk_i32 %[a], 0x6b43\n\t"
+        "s_addk_i32 %[a], 0x7c15\n\t"
+        "s_lshr_b32 %[b], %[s], 15\n\t"
+        "s_xor_b32 %[b], %[b], %[a]\n\t"
+        : [a] "=&s"(a), [b] "=&s"(b)
+        : [s] "s"(s)
+        : "scc");
+    const unsigned long long P = u64_of(b, a), Q = u64_of(s, b);
+    unsigned long long R;
+    unsigned n, c, d, e, f, g, h;
+    // every compare's outcome goes into d as one bit: d = d + d + SCC
+#define SALU_CTL_BIT "s_addc_u32 %[d], %[d], %[d]\n\t"
+    asm volatile(
+        "s_and_b32 %[c], %[a], 3\n\t"
+        "s_and_b32 %[e], %[b], 3\n\t"
+        "s_lshr_b32 %[g], %[a], 16\n\t"
+        "s_lshr_b32 %[h], %[b], 16\n\t"
+        "s_movk_i32 %[d], 0x1b\n\t"
+        "s_movk_i32 %[f], -12059\n\t"
+        "s_cmp_eq_i32 %[c], %[e]\n\t"
+        "s_cselect_b32 %[n], %[a], %[b]\n\t" SALU_CTL_BIT
+        "s_cmp_lg_i32 %[c], 2\n\t"
+        "s_cmov_b32 %[f], %[h]\n\t" SALU_CTL_BIT
+        "s_cmp_gt_i32 %[a], %[b]\n\t"
+        "s_cselect_b64 %[R], %[P], %[Q]\n\t" SALU_CTL_BIT
+        "s_cmp_ge_i32 %[b], %[s]\n\t" SALU_CTL_BIT
+        "s_cmp_lt_i32 %[a], %[s]\n\t" SALU_CTL_BIT
+        "s_cmp_le_i32 %[s], %[b]\n\t" SALU_CTL_BIT
+        "s_cmp_eq_u32 %[e], 1\n\t" SALU_CTL_BIT
+        "s_cmp_lg_u32 %[c], %[e]\n\t" SALU_CTL_BIT
+        "s_cmp_gt_u32 %[a], %[b]\n\t" SALU_CTL_BIT
+        "s_cmp_ge_u32 %[b], %[s]\n\t" SALU_CTL_BIT
+        "s_cmp_lt_u32 %[s], %[a]\n\t" SALU_CTL_BIT
+        "s_cmp_le_u32 %[h], %[g]\n\t" SALU_CTL_BIT
+        "s_bitcmp0_b32 %[a], %[b]\n\t" SALU_CTL_BIT
+        "s_bitcmp1_b32 %[b], %[a]\n\t" SALU_CTL_BIT
+        "s_cmpk_eq_i32 %[c], 1\n\t" SALU_CTL_BIT
+        "s_cmpk_lg_i32 %[e], 2\n\t" SALU_CTL_BIT
+        "s_cmpk_gt_i32 %[a], 0x1234\n\t" SALU_CTL_BIT
+        "s_cmpk_ge_i32 %[b], -4660\n\t" SALU_CTL_BIT
+        "s_cmpk_lt_i32 %[a], -28672\n\t" SALU_CTL_BIT
+        "s_cmpk_le_i32 %[b], 0x7000\n\t" SALU_CTL_BIT
+        "s_cmpk_eq_u32 %[e], 3\n\t" SALU_CTL_BIT
+        "s_cmpk_lg_u32 %[c], 0\n\t" SALU_CTL_BIT
+        "s_cmpk_gt_u32 %[g], 0x8000\n\t" SALU_CTL_BIT
+        "s_cmpk_ge_u32 %[h], 0x4000\n\t" SALU_CTL_BIT
+        "s_cmpk_lt_u32 %[g], 0xc000\n\t" SALU_CTL_BIT
+        "s_cmpk_le_u32 %[h], 0x2000\n\t" SALU_CTL_BIT
+        "s_xor_b32 %[n], %[n], %[f]\n\t"
+        // two different updates, chosen by a state bit
+        "s_bitcmp1_b32 %[s], 7\n\t"
+        "s_cbranch_scc0 hvd_ctl_else_%=\n\t"
+        "s_mul_i32 %[n], %[n], 0x9E3779B1\n\t"
+        "s_add_u32 %[n], %[n], %[d]\n\t"
+        "s_branch hvd_ctl_join_%=\n"
+        "hvd_ctl_else_%=:\n\t"
+        "s_sub_u32 %[n], %[n], %[d]\n\t"
+        "s_xor_b32 %[n], %[n], %[a]\n"
+        "hvd_ctl_join_%=:\n\t"
+        // a third, skipped when the new value is below b
+        "s_cmp_lt_u32 %[n], %[b]\n\t"
+        "s_cbranch_scc1 hvd_ctl_skip_%=\n\t"
+        "s_not_b32 %[n], %[n]\n\t"
+        "s_add_u32 %[n], %[n], %[h]\n"
+        "hvd_ctl_skip_%=:\n\t"
+        : [n] "=&s"(n), [c] "=&s"(c), [d] "=&s"(d), [e] "=&s"(e), [f] "=&s"(f), [g] "=&s"(g),
+          [h] "=&s"(h), [R] "=&s"(R)
+        : [s] "s"(s), [a] "s"(a), [b] "s"(b), [P] "s"(P), [Q] "s"(Q)
+        : "scc");
+#undef SALU_CTL_BIT
+    asm volatile(
+        "s_xor_b32 %[n], %[n], %[rlo]\n\t"
+        "s_add_u32 %[n], %[n], %[rhi]\n\t"
+        : [n] "+s"(n)
+        : [rlo] "s"((unsigned)R), [rhi] "s"((unsigned)(R >> 32))
+        : "scc");
+    return n;
+  }
+};
+
+// one step of the mask section for this lane; c is the step index
+__device__ __forceinline__ unsigned salu_mask_step(unsigned s, int lane, int c) {
+  const unsigned long long m = __ballot((s >> (c & 31)) & 1u);
+  const unsigned pc = (unsigned)__popcll(m);
+  const unsigned ff = (unsigned)__ffsll((long long)m);  // 0 for an empty mask, else 1 + index
+  // the empty asm keeps the two arms a real branch on EXEC: without it the
+  // compiler turns them into a select
+  if ((m >> lane) & 1) {
+    s = s * 0x9E3779B1u + pc;
+    asm volatile("" : "+v"(s));
+  } else {
+    s = (s ^ (s >> 15)) * 0x85EBCA6Bu + ff;
+    asm volatile("" : "+v"(s));
+  }
+  const unsigned first = (unsigned)__builtin_amdgcn_readfirstlane((int)s);
+  return s + (first ^ (unsigned)m ^ (unsigned)(m >> 32));
+}
+
+// the wave index as a value the compiler knows to be wave-uniform
+__device__ __forceinline__ int uniform_wave_index() {
+  return (int)blockIdx.x * (int)(blockDim.x >> 6) +
+         __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+}
+
+template <int SEC>
+__global__ void __launch_bounds__(256)
+salu_burn_kernel(const long long* __restrict__ expected, int4* __restrict__ records,
+                 unsigned seed, int chain, int rounds, int inject_wave, int inject_round,
+                 int inject_chain, int inject_bit) {
+  typedef SaluStep<SEC> S;
+  typedef typename S::state state;
+  const int wave = uniform_wave_index();
+  const unsigned place = hw_word();
+
+  const state flip =
+      wave == inject_wave ? (state)1 << (inject_bit & (int)(8 * sizeof(state) - 1)) : (state)0;
+  int mismatched = 0, first_round = -1, first_chain = -1;
+  state checksum = 0;
+  for (int round = 0; round < rounds; round++) {
+    // Opaque to the optimiser: every round really recomputes its chains. The
+    // seeds are derived again each round and the expected values loaded after
+    // the chain loop, instead of both held in 32 more SGPRs across it (with
+    // them the s64 section spilled)
+    unsigned sd = seed;
+    asm volatile("" : "+s"(sd));
+    state s[SALU_CHAINS];
+#pragma unroll
+    for (int k = 0; k < SALU_CHAINS; k++) s[k] = (state)valu_seed_state(sd, SEC, k);
+    for (int c = 0; c < chain; c++) {
+#pragma unroll
+      for (int k = 0; k < SALU_CHAINS; k++) s[k] = S::step(s[k]);
+    }
+    // expected[0..8) is 16 dwords: one scalar load. The compare is asm too, so
+    // that it stays on the SALU; from the highest chain down, so that `low`
+    // ends as the lowest bad one
+    const u32x16 w = ScalarLoad<16>::load(reinterpret_cast<const int*>(expected), 0u);
+    // masks, not selects: integer arithmetic on wave-uniform values stays on the SALU
+    const state flip_now = flip & ((state)0 - (state)(round == inject_round));
+    int bad = 0, low = -1;
+#pragma unroll
+    for (int k = SALU_CHAINS - 1; k >= 0; k--) {
+      s[k] ^= flip_now & ((state)0 - (state)(k == inject_chain));
+      checksum ^= s[k];
+      const state want = (state)u64_of(w[2 * k], w[2 * k + 1]);
+      if constexpr (sizeof(state) == 8) {
+        asm volatile("s_cmp_lg_u64 %[got], %[want]\n\t"
+                     "s_cselect_b32 %[low], %[k], %[low]\n\t"
+                     "s_addc_u32 %[bad], %[bad], 0"
+                     : [bad] "+s"(bad), [low] "+s"(low)
+                     : [got] "s"(s[k]), [want] "s"(want), [k] "s"(k)
+                     : "scc");
+      } else {
+        asm volatile("s_cmp_lg_u32 %[got], %[want]\n\t"
+                     "s_cselect_b32 %[low], %[k], %[low]\n\t"
+                     "s_addc_u32 %[bad], %[bad], 0"
+                     : [bad] "+s"(bad), [low] "+s"(low)
+                     : [got] "s"(s[k]), [want] "s"(want), [k] "s"(k)
+                     : "scc");
+      }
+    }
+    mismatched += bad;
+    if (bad && first_round < 0) {
+      first_round = round;
+      first_chain = low;
+    }
+  }
+  if ((threadIdx.x & 63) == 0)
+    store_record8(records, wave, (int)place, mismatched, first_round, first_chain,
+                  (int)(unsigned)checksum, (int)(unsigned)((unsigned long long)checksum >> 32), 0,
+                  0);
+}
+
+__global__ void __launch_bounds__(256)
+salu_mask_burn_kernel(const long long* __restrict__ expected, int4* __restrict__ records,
+                      unsigned seed, int chain, int rounds, int inject_wave, int inject_round,
+                      int inject_lane, int inject_bit) {
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const unsigned place = hw_word();
+
+  const unsigned seeded = (unsigned)valu_seed_state(seed, SALU_MASK, lane);
+  const unsigned want = (unsigned)expected[lane];
+  const unsigned flip = (wave == inject_wave && lane == inject_lane) ? 1u << (inject_bit & 31) : 0u;
+  int mismatched = 0, first_round = -1, first_lane = -1;
+  unsigned checksum = 0;
+  for (int round = 0; round < rounds; round++) {
+    unsigned s = seeded;
+    asm volatile("" : "+v"(s));
+    for (int c = 0; c < chain; c++) s = salu_mask_step(s, lane, c);
+    if (round == inject_round) s ^= flip;
+    checksum ^= s;
+    const unsigned long long bad = __ballot(s != want);  // wave-uniform
+    if (bad) {
+      mismatched += __popcll(bad);
+      if (first_round < 0) {
+        first_round = round;
+        first_lane = __ffsll((long long)bad) - 1;
+      }
+    }
+  }
+  checksum = wave_xor(checksum);
+  if (lane == 0)
+    store_record8(records, wave, (int)place, mismatched, first_round, first_lane, (int)checksum, 0,
+                  0, 0);
+}
+
+// ---------------------------------------------------------------------------
+// Scalar probe, part 2. SGPR march: a timed write/read-verify of the scalar
+// registers a wave is given, in both bit polarities, built like the VGPR march
+// above. A pass is ONE asm statement: it writes s32..s101 in ascending order,
+// xors the injection mask into s77, then reads all of them back in ascending
+// order and compares on the SALU. The statement names every register it
+// marches as a clobber; s0..s31 stay the compiler's, for the kernel's own
+// values and the statement's operands.
+//
+// Unlike the VGPR march this kernel CANNOT own the file. The SGPR file has 800
+// entries per SIMD and a wave gets its allocation, not the file: the kernel
+// verifies the 70 registers each wave was given, and the host sizes the grid
+// so that the waves resident on a SIMD together hold most of the file.
+//
+// Pattern: in round r register R of global wave w holds
+//   p(r, R, w) = ((w*128 + R) * 0x9E3779B1 mod 2^32) ^ rs,
+//   rs = fmix32(seed + r*0x9E3779B9),
+// then its complement in the round's second pass. The multiply by an odd
+// constant is a bijection, so the values are distinct across the registers of
+// a wave and across all waves of a launch (w < 2^25): co-resident waves hold
+// different data, and an allocation that aliases another's reads back wrong.
+//
+// Lane 0 of each wave writes one record of eight int32 (store_record8):
+//   [0] placement word (hw_word)
+//   [1] mismatched registers over all passes
+//   [2] first bad global pass, round*2 + polarity (-1 if none)
+//   [3] lowest mismatching register in that pass (-1 if none)
+//   [4] dropped mask: OR of (want & ~got)   [5] raised mask: OR of (got & ~want)
+//   [6] sum mod 2^32 of every value read in the pattern passes
+//   [7] registers marched per pass (70)
+//
+// inject_* (default -1 = off): in wave inject_wave, at global pass
+// inject_pass, the mask xored into s77 between the write and the read phase
+// holds bit inject_bit; everywhere else it is zero. Registers only.
+// ---------------------------------------------------------------------------
+constexpr int SGPR_MARCH_FIRST = 32;    // s0..s31 stay the compiler's
+constexpr int SGPR_MARCH_MARCHED = 70;  // s32..s101
+constexpr int SGPR_MARCH_INJECT = 77;
+
+#define SGPR_MARCH_CLOBBERS                                                               \
+  "s32", "s33", "s34", "s35", "s36", "s37", "s38", "s39", HVD_C10("s", 4), HVD_C50("s", 5, 6, 7, \
+                                                                                   8, 9),  \
+      "s100", "s101"
+
+__global__ void __launch_bounds__(256)
+sgpr_march_kernel(int4* __restrict__ records, int rounds, unsigned seed, int inject_wave,
+                  int inject_bit, int inject_pass) {
+  const int wave = uniform_wave_index();
+  const unsigned place = hw_word();
+
+  const unsigned base = (unsigned)wave * 128u * 0x9E3779B1u;
+  const unsigned flip = wave == inject_wave ? 1u << (inject_bit & 31) : 0u;
+  unsigned mism = 0, dropped = 0, raised = 0, sum = 0;
+  int first_pass = -1;
+  unsigned first_reg = 0xFFFFFFFFu;
+#pragma nounroll
+  for (int pass = 0; pass < 2 * rounds; pass++) {
+    const unsigned rs = fmix32(seed + (unsigned)(pass >> 1) * 0x9E3779B9u);
+    // plain integer arithmetic, which stays on the SALU: selects of these
+    // wave-uniform values have been seen to land in VGPRs
+    const unsigned smask = (unsigned)(pass & 1) - 1u;  // all ones in pattern passes: sum those
+    const unsigned xr = rs ^ ~smask;                   // the complement in the second pass
+    const unsigned m = flip & (0u - (unsigned)(pass == inject_pass));
+    unsigned first = 0xFFFFFFFFu, t0, t1, t2;
+    asm volatile(
+        // write phase
+        ".set hvd_r, 32\n\t"
+        ".rept 70\n\t"
+        "s_add_u32 s[hvd_r], %[base], (hvd_r*0x9E3779B1)&0xffffffff\n\t"
+        "s_xor_b32 s[hvd_r], s[hvd_r], %[xr]\n\t"
+        ".set hvd_r, hvd_r+1\n\t"
+        ".endr\n\t"
+        // injection: the mask is zero except in one wave and pass
+        "s_xor_b32 s77, s77, %[m]\n\t"
+        // read phase: t0 = want, t1 = diff
+        ".set hvd_r, 32\n\t"
+        ".rept 70\n\t"
+        "s_add_u32 %[t0], %[base], (hvd_r*0x9E3779B1)&0xffffffff\n\t"
+        "s_xor_b32 %[t0], %[t0], %[xr]\n\t"
+        "s_and_b32 %[t2], s[hvd_r], %[smask]\n\t"
+        "s_add_u32 %[sum], %[sum], %[t2]\n\t"
+        "s_xor_b32 %[t1], %[t0], s[hvd_r]\n\t"
+        "s_and_b32 %[t2], %[t0], %[t1]\n\t"
+        "s_or_b32 %[dropped], %[dropped], %[t2]\n\t"
+        "s_and_b32 %[t2], s[hvd_r], %[t1]\n\t"
+        "s_or_b32 %[raised], %[raised], %[t2]\n\t"
+        "s_cmp_lg_u32 %[t1], 0\n\t"
+        "s_cselect_b32 %[t2], hvd_r, -1\n\t"
+        "s_addc_u32 %[mism], %[mism], 0\n\t"
+        "s_min_u32 %[first], %[first], %[t2]\n\t"
+        ".set hvd_r, hvd_r+1\n\t"
+        ".endr\n\t"
+        : [mism] "+s"(mism), [dropped] "+s"(dropped), [raised] "+s"(raised), [sum] "+s"(sum),
+          [first] "+s"(first), [t0] "=&s"(t0), [t1] "=&s"(t1), [t2] "=&s"(t2)
+        : [base] "s"(base), [xr] "s"(xr), [smask] "s"(smask), [m] "s"(m)
+        : "scc", SGPR_MARCH_CLOBBERS);
+    const bool first_here = first != 0xFFFFFFFFu && first_pass < 0;
+    first_pass = first_here ? pass : first_pass;
+    first_reg = first_here ? first : first_reg;
+  }
+  if ((threadIdx.x & 63) == 0)
+    store_record8(records, wave, (int)place, (int)mism, first_pass, (int)first_reg, (int)dropped,
+                  (int)raised, (int)sum, SGPR_MARCH_MARCHED);
+}
+
+// ---------------------------------------------------------------------------
+// Scalar probe, part 3. Scalar-load check: every wave reads a whole uint32
+// pattern [2, W] (row 1 the complement of row 0) through the scalar data cache
+// with s_load_dword, x2, x4, x8 and x16, one width per round, rotating, at
+// offsets aligned to the load's own size, and compares every word on the SALU
+// against the value recomputed from (seed, row, index):
+//   row 0 word i = fmix32(seed ^ (i * 0x85EBCA6B)).
+// The load and its s_waitcnt lgkmcnt(0) are one asm statement with an
+// early-clobber destination: scalar loads return out of order, and the
+// compiler knows nothing of a load issued from asm.
+//
+// This verifies the data bits of the scalar load path in both polarities and
+// that all five widths return the right words. It does NOT march the scalar
+// cache's cells: nothing lets a kernel choose them.
+//
+// Lane 0 of each wave writes one record of eight int32 (store_record8):
+//   [0] placement word (hw_word)
+//   [1] mismatched words over all rounds
+//   [2] first bad round (-1 if none)
+//   [3] lowest bad word in that round, row*W + index (-1 if none)
+//   [4] dropped mask   [5] raised mask
+//   [6] sum mod 2^32 of the row-0 words read
+//   [7] words read per round (2*W)
+// There is no injection: a test flips a bit in the tensor it uploads.
+// ---------------------------------------------------------------------------
+struct ScalarLoadState {
+  unsigned mismatched, first_word, dropped, raised, sum;
+};
+
+// Compare one loaded word on the SALU. j is its index within its row, idx its
+// index in the buffer (row*W + j), inv all ones in row 1 (the complement) and
+// smask all ones in row 0 (the row that is summed). One asm statement, so that
+// the recomputed value, the compare and the bookkeeping stay scalar
+// instructions: written in C++ the compiler moved them to the vector ALU.
+// t = want, u = diff, w = scratch
+__device__ __forceinline__ void scalar_load_compare(ScalarLoadState& s, unsigned got, unsigned seed,
+                                                    unsigned j, unsigned idx, unsigned inv,
+                                                    unsigned smask) {
+  unsigned t, u, w;
+  asm volatile(
+      "s_mul_i32 %[t], %[j], 0x85EBCA6B\n\t"
+      "s_xor_b32 %[t], %[t], %[seed]\n\t"
+      // fmix32
+      "s_lshr_b32 %[u], %[t], 16\n\t"
+      "s_xor_b32 %[t], %[t], %[u]\n\t"
+      "s_mul_i32 %[t], %[t], 0x85EBCA6B\n\t"
+      "s_lshr_b32 %[u], %[t], 13\n\t"
+      "s_xor_b32 %[t], %[t], %[u]\n\t"
+      "s_mul_i32 %[t], %[t], 0xC2B2AE35\n\t"
+      "s_lshr_b32 %[u], %[t], 16\n\t"
+      "s_xor_b32 %[t], %[t], %[u]\n\t"
+      "s_xor_b32 %[t], %[t], %[inv]\n\t"
+      "s_and_b32 %[w], %[got], %[smask]\n\t"
+      "s_add_u32 %[sum], %[sum], %[w]\n\t"
+      "s_and_b32 %[w], %[t], %[got]\n\t"
+      "s_xor_b32 %[w], %[w], %[t]\n\t"  // want & ~got
+      "s_or_b32 %[dropped], %[dropped], %[w]\n\t"
+      "s_and_b32 %[w], %[t], %[got]\n\t"
+      "s_xor_b32 %[w], %[w], %[got]\n\t"  // got & ~want
+      "s_or_b32 %[raised], %[raised], %[w]\n\t"
+      "s_xor_b32 %[u], %[t], %[got]\n\t"  // SCC = mismatch
+      "s_cselect_b32 %[w], %[idx], -1\n\t"
+      "s_addc_u32 %[mism], %[mism], 0\n\t"
+      "s_min_u32 %[first], %[first], %[w]\n\t"
+      : [mism] "+s"(s.mismatched), [first] "+s"(s.first_word), [dropped] "+s"(s.dropped),
+        [raised] "+s"(s.raised), [sum] "+s"(s.sum), [t] "=&s"(t), [u] "=&s"(u), [w] "=&s"(w)
+      : [got] "s"(got), [seed] "s"(seed), [j] "s"(j), [idx] "s"(idx), [inv] "s"(inv),
+        [smask] "s"(smask)
+      : "scc");
+}
+
+// one row of the buffer (words dwords, a multiple of 16) through loads of N
+// dwords. The row is a template argument so that inv and smask are constants:
+// derived from a compare of the loop index they landed in VGPRs
+template <int N, int ROW>
+__device__ __forceinline__ void scalar_load_row(ScalarLoadState& s, const int* p, unsigned seed,
+                                                unsigned words) {
+  constexpr unsigned inv = ROW ? 0xFFFFFFFFu : 0u;
+  const unsigned row_base = ROW ? words : 0u;
+  for (unsigned j = 0; j < words; j += N) {
+    const unsigned idx = row_base + j;
+    if constexpr (N == 1) {
+      scalar_load_compare(s, ScalarLoad<1>::load(p, idx * 4), seed, j, idx, inv, ~inv);
+    } else {
+      const typename ScalarLoad<N>::vec v = ScalarLoad<N>::load(p, idx * 4);
+#pragma unroll
+      for (int k = 0; k < N; k++) scalar_load_compare(s, v[k], seed, j + k, idx + k, inv, ~inv);
+    }
+  }
+}
+
+// one round: the whole buffer, row 0 then row 1
+template <int N>
+__device__ __forceinline__ void scalar_load_round(ScalarLoadState& s, const int* p, unsigned seed,
+                                                  unsigned words) {
+  scalar_load_row<N, 0>(s, p, seed, words);
+  scalar_load_row<N, 1>(s, p, seed, words);
+}
+
+__global__ void __launch_bounds__(256)
+scalar_load_kernel(const int* __restrict__ pattern, int4* __restrict__ records, unsigned seed,
+                   int words, int rounds) {
+  const int wave = uniform_wave_index();
+  const unsigned place = hw_word();
+  ScalarLoadState total = {0u, 0xFFFFFFFFu, 0u, 0u, 0u};
+  int first_round = -1;
+  for (int round = 0; round < rounds; round++) {
+    ScalarLoadState s = {0u, 0xFFFFFFFFu, 0u, 0u, 0u};
+    switch (round % 5) {
+      case 0: scalar_load_round<1>(s, pattern, seed, (unsigned)words); break;
+      case 1: scalar_load_round<2>(s, pattern, seed, (unsigned)words); break;
+      case 2: scalar_load_round<4>(s, pattern, seed, (unsigned)words); break;
+      case 3: scalar_load_round<8>(s, pattern, seed, (unsigned)words); break;
+      default: scalar_load_round<16>(s, pattern, seed, (unsigned)words); break;
+    }
+    total.mismatched += s.mismatched;
+    total.dropped |= s.dropped;
+    total.raised |= s.raised;
+    total.sum += s.sum;
+    if (s.mismatched && first_round < 0) {
+      first_round = round;
+      total.first_word = s.first_word;
+    }
+  }
+  if ((threadIdx.x & 63) == 0)
+    store_record8(records, wave, (int)place, (int)total.mismatched, first_round,
+                  (int)total.first_word, (int)total.dropped, (int)total.raised, (int)total.sum,
+                  2 * words);
+}
+
+// expected: int64 on the current device, the states a wave must reach after
+// `chain` steps (ops.salu_burn_expected): SALU_CHAINS values for sections s32,
+// s64 and ctl, 64 (one per lane) for mask. One untimed warm-up launch, then
+// one timed launch (warm_then_timed_ms).
+// Returns (records [waves,8] int32, elapsed_ms of the timed launch).
+std::tuple<torch::Tensor, double> salu_burn(torch::Tensor expected, const std::string& section,
+                                            long seed, long blocks, long chain, long rounds,
+                                            long inject_wave, long inject_round,
+                                            long inject_chain, long inject_bit) {
+  int sec = section == "s32" ? SALU_S32 : section == "s64" ? SALU_S64 : section == "ctl" ? SALU_CTL
+            : section == "mask" ? SALU_MASK : -1;
+  TORCH_CHECK(sec >= 0, "section must be one of s32, s64, ctl, mask; got ", section);
+  TORCH_CHECK(blocks >= 1 && blocks <= (1L << 20), "blocks must be in [1, 2^20]");
+  TORCH_CHECK(chain >= 1 && rounds >= 1, "chain and rounds must be >= 1");
+  // bounded run: at most 2^18 steps per chain per wave. At eight waves per
+  // SIMD a step of all eight chains of the slowest section (ctl) measures
+  // ~8.4 us (BENCHMARKS.md "Scalar probe"), ~2.2 s for 2^18 of them at the
+  // default grid
+  TORCH_CHECK(chain <= (1L << 18) && rounds <= (1L << 18) && chain * rounds <= (1L << 18),
+              "chain*rounds must be <= 2^18");
+  const long units = sec == SALU_MASK ? 64 : SALU_CHAINS;
+  const long state_bits = sec == SALU_S64 ? 64 : 32;
+  TORCH_CHECK(inject_wave >= -1 && inject_wave < blocks * 4 && inject_round >= -1 &&
+                  inject_round < rounds && inject_chain >= -1 && inject_chain < units &&
+                  inject_bit >= -1 && inject_bit < state_bits,
+              "inject_wave/inject_round/inject_chain/inject_bit out of range");
+  TORCH_CHECK(inject_wave < 0 || (inject_round >= 0 && inject_chain >= 0 && inject_bit >= 0),
+              "an injection needs inject_round, inject_chain and inject_bit");
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  TORCH_CHECK(expected.is_cuda() && expected.get_device() == dev,
+              "expected must be on the current GPU");
+  TORCH_CHECK(expected.dtype() == torch::kInt64 && expected.numel() == units,
+              "expected must hold ", units, " int64 values for section ", section);
+  expected = expected.contiguous();
+  const long long* want = reinterpret_cast<const long long*>(expected.data_ptr<int64_t>());
+  auto records = zero_records(blocks * 4, 8);
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  const double ms = warm_then_timed_ms(stream, [&]() {
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, stream, want,
+                         reinterpret_cast<int4*>(records.data_ptr<int>()), (unsigned)seed,
+                         (int)chain, (int)rounds, (int)inject_wave, (int)inject_round,
+                         (int)inject_chain, (int)inject_bit);
+    };
+    if (sec == SALU_MASK) {
+      launch(salu_mask_burn_kernel);
+    } else {
+      dispatch_int<3>(sec, [&](auto sec_c) { launch(salu_burn_kernel<decltype(sec_c)::value>); });
+    }
+  });
+  return std::make_tuple(records, ms);
+}
+
+// One untimed warm-up launch, then one timed launch (warm_then_timed_ms).
+// Returns (records [blocks*4, 8] int32, elapsed_ms of the timed launch, waves
+// per SIMD as the occupancy query reports them: reported, never asserted, for
+// the query over-reports for SGPR-heavy 256-thread kernels).
+std::tuple<torch::Tensor, double, long> sgpr_march(long blocks, long rounds, long seed,
+                                                   long inject_wave, long inject_bit,
+                                                   long inject_pass) {
+  // the pattern is unique across waves while w*128 + R < 2^32: w < 2^25
+  TORCH_CHECK(blocks >= 1 && blocks <= (1L << 20), "blocks must be in [1, 2^20]");
+  TORCH_CHECK(rounds >= 1, "rounds must be >= 1");
+  // bounded run: a round (two passes) measures ~3.7 us per workgroup on a CU
+  // (BENCHMARKS.md "Scalar probe"); on 256 CUs that puts 2^27 block-rounds at
+  // ~2 s
+  TORCH_CHECK(rounds <= (1L << 27) && blocks * rounds <= (1L << 27),
+              "blocks*rounds must be <= 2^27");
+  TORCH_CHECK(inject_wave >= -1 && inject_wave < blocks * 4, "inject_wave out of range");
+  TORCH_CHECK(inject_bit >= 0 && inject_bit < 32, "inject_bit out of range");
+  TORCH_CHECK(inject_pass >= -1 && inject_pass < rounds * 2, "inject_pass out of range");
+  int per_cu = 0;
+  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sgpr_march_kernel, 256, 0));
+  auto records = zero_records(blocks * 4, 8);
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  const double ms = warm_then_timed_ms(stream, [&]() {
+    hipLaunchKernelGGL(sgpr_march_kernel, dim3(blocks), dim3(256), 0, stream,
+                       reinterpret_cast<int4*>(records.data_ptr<int>()), (int)rounds,
+                       (unsigned)seed, (int)inject_wave, (int)inject_bit, (int)inject_pass);
+  });
+  // a 256-thread workgroup is one wave on each of the four SIMDs
+  return std::make_tuple(records, ms, (long)per_cu);
+}
+
+// pattern: int32 [2, W] on the current device (ops.scalar_load_pattern viewed
+// as int32), W a multiple of 16 in [16, 4096]. One untimed warm-up launch,
+// then one timed launch (warm_then_timed_ms).
+// Returns (records [blocks*4, 8] int32, elapsed_ms of the timed launch).
+std::tuple<torch::Tensor, double> scalar_load_check(torch::Tensor pattern, long seed, long blocks,
+                                                    long rounds) {
+  TORCH_CHECK(blocks >= 1 && blocks <= (1L << 20), "blocks must be in [1, 2^20]");
+  TORCH_CHECK(rounds >= 1, "rounds must be >= 1");
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  TORCH_CHECK(pattern.is_cuda() && pattern.get_device() == dev,
+              "pattern must be on the current GPU");
+  TORCH_CHECK(pattern.dtype() == torch::kInt32, "pattern must be int32");
+  TORCH_CHECK(pattern.dim() == 2 && pattern.size(0) == 2, "pattern must be [2, W]");
+  const long words = pattern.size(1);
+  TORCH_CHECK(words >= 16 && words <= 4096 && words % 16 == 0,
+              "W must be a multiple of 16 in [16, 4096]; got ", words);
+  TORCH_CHECK(pattern.is_contiguous(), "pattern must be contiguous");
+  // bounded run: 2048 workgroups x 5 rounds x 1024 words measure ~3.7 ms
+  // (BENCHMARKS.md "Scalar probe"), ~0.35 ns per workgroup-round-word: ~1.5 s
+  // for 2^32 of them
+  TORCH_CHECK(rounds <= (1L << 24) && blocks * rounds * words <= (1L << 32),
+              "blocks*rounds*W must be <= 2^32");
+  auto records = zero_records(blocks * 4, 8);
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  const double ms = warm_then_timed_ms(stream, [&]() {
+    hipLaunchKernelGGL(scalar_load_kernel, dim3(blocks), dim3(256), 0, stream,
+                       pattern.data_ptr<int>(), reinterpret_cast<int4*>(records.data_ptr<int>()),
+                       (unsigned)seed, (int)words, (int)rounds);
+  });
+  return std::make_tuple(records, ms);
+}
+
+// ---------------------------------------------------------------------------
 // xGMI p2p bandwidth between two devices (one direction).
 // ---------------------------------------------------------------------------
 double p2p_gbps(int src_dev, int dst_dev, long size_mb, long iters) {
@@ -1938,6 +2766,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("inject_bit") = 0, py::arg("inject_pass") = -1,
         "Register-file march (480 of the 512 VGPR+AGPR entries per lane of every SIMD): both "
         "polarities, timed; returns (per-wave records [blocks*4,8], ms, workgroups per CU)");
+  m.def("salu_burn", &salu_burn, py::arg("expected"), py::arg("section"), py::arg("seed") = 1,
+        py::arg("blocks") = 2048, py::arg("chain") = 64, py::arg("rounds") = 33,
+        py::arg("inject_wave") = -1, py::arg("inject_round") = -1, py::arg("inject_chain") = -1,
+        py::arg("inject_bit") = -1,
+        "Sustained scalar-ALU burn (section s32|s64|ctl|mask): rounds x chain dependent steps on "
+        "eight states per wave (64 lanes for mask), verified bitwise against expected; returns "
+        "(per-wave records [waves,8], ms)");
+  m.def("sgpr_march", &sgpr_march, py::arg("blocks"), py::arg("rounds"), py::arg("seed"),
+        py::arg("inject_wave") = -1, py::arg("inject_bit") = 0, py::arg("inject_pass") = -1,
+        "SGPR march (s32..s101 of every wave): both polarities, timed; returns (per-wave records "
+        "[blocks*4,8], ms, waves per SIMD by the occupancy query)");
+  m.def("scalar_load_check", &scalar_load_check, py::arg("pattern"), py::arg("seed"),
+        py::arg("blocks"), py::arg("rounds"),
+        "Scalar-load check: every wave reads pattern [2,W] with s_load_dword, x2, x4, x8 and x16 "
+        "and compares on the SALU; returns (per-wave records [blocks*4,8], ms)");
   m.def("cu_coverage", &cu_coverage, py::arg("blocks") = 4096,
         "Per-wave (XCC_ID<<16 | HW_ID) placement words for CU-coverage checks");
   m.def("device_info", &device_info, py::arg("dev") = 0);
