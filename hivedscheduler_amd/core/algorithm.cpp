@@ -185,28 +185,27 @@ ScheduleResult HivedCore::schedule(const PodSpec& s, const std::string& podKey,
   int podIndex = 0;
   bool havePlacement = false;
 
-  auto it = groups_.find(s.groupName);
-  bool groupExists = it != groups_.end();
-  // a group can come into being below only in the Preempting phase
-  // (createPreemptingGroup), so a Filtering miss needs no second lookup
-  bool mayHaveGroup = groupExists || phase == Phase::Preempting;
-  if (groupExists) {
-    havePlacement = schedulePodFromExistingGroup(it->second.get(), s, suggestedNodes, phase,
-                                                 podKey, &phys, &hasVirtual, &virt, &victims,
-                                                 &podIndex);
-    // the group may have been a preempting group deleted just above
-    groupExists = groups_.find(s.groupName) != groups_.end();
+  // The one lookup of the group by name. From here on the group is followed
+  // by pointer: it stays while schedulePodFromExistingGroup answers true, and
+  // a new one can come into being only in schedulePodFromNewGroup, which
+  // hands it back.
+  Group* g = nullptr;
+  if (auto it = groups_.find(s.groupName); it != groups_.end()) g = it->second.get();
+  if (g != nullptr) {
+    havePlacement = schedulePodFromExistingGroup(g, s, suggestedNodes, phase, podKey, &phys,
+                                                 &hasVirtual, &virt, &victims, &podIndex);
+    if (!havePlacement) {
+      // it was a preempting group and has just been deleted: look again
+      auto it = groups_.find(s.groupName);
+      g = it == groups_.end() ? nullptr : it->second.get();
+    }
   }
-  if (!groupExists) {
-    schedulePodFromNewGroup(s, suggestedNodes, phase, podKey, &phys, &hasVirtual, &virt, &victims,
-                            &waitReason);
+  if (g == nullptr) {
+    g = schedulePodFromNewGroup(s, suggestedNodes, phase, podKey, &phys, &hasVirtual, &virt,
+                                &victims, &waitReason);
     havePlacement = !phys.empty();
   }
   (void)havePlacement;
-  Group* g = nullptr;
-  if (mayHaveGroup) {
-    if (auto git = groups_.find(s.groupName); git != groups_.end()) g = git->second.get();
-  }
   return generateResult(phys, hasVirtual, virt, victims, std::move(waitReason), s.leafCellNumber,
                         podIndex, g, s.groupName);
 }
@@ -268,7 +267,7 @@ ScheduleResult HivedCore::generateResult(const Placement<PhysicalCell>& phys, bo
           if (vIt != virt.end() && pi < vIt->second.size() &&
               li < static_cast<int>(vIt->second[pi].size()) && vIt->second[pi][li] != nullptr) {
             VirtualCell* v = vIt->second[pi][li];
-            pl.preassignedTypes[li] = cellTypes_[v->chain][v->preassigned->level];
+            pl.preassignedTypes[li] = v->cs->levelType[v->preassigned->level];
           }
         }
       }
@@ -327,15 +326,15 @@ bool HivedCore::schedulePodFromExistingGroup(
   return true;
 }
 
-void HivedCore::schedulePodFromNewGroup(const PodSpec& s,
-                                        const std::set<std::string>& suggestedNodes, Phase phase,
-                                        const std::string& podKey, Placement<PhysicalCell>* phys,
-                                        bool* hasVirtual, Placement<VirtualCell>* virt,
-                                        VictimList* victims,
-                                        std::string* waitReason) {
+// Answers the preempting group it created, if it created one.
+Group* HivedCore::schedulePodFromNewGroup(const PodSpec& s,
+                                          const std::set<std::string>& suggestedNodes, Phase phase,
+                                          const std::string& podKey, Placement<PhysicalCell>* phys,
+                                          bool* hasVirtual, Placement<VirtualCell>* virt,
+                                          VictimList* victims, std::string* waitReason) {
   if (!scheduleNewAffinityGroup(s, suggestedNodes, podKey, phys, hasVirtual, virt, waitReason)) {
     phys->clear();
-    return;
+    return nullptr;
   }
   OverlappingPreemptors overlapping = collectPreemptionVictims(*phys, victims);
   if (phase == Phase::Preempting) {
@@ -345,9 +344,10 @@ void HivedCore::schedulePodFromNewGroup(const PodSpec& s,
     }
     if (!victims->empty()) {
       // reserve cells immediately so equal-priority groups cannot contend
-      createPreemptingGroup(s, *phys, *virt, podKey);
+      return createPreemptingGroup(s, *phys, *virt, podKey);
     }
   }
+  return nullptr;
 }
 
 bool HivedCore::scheduleNewAffinityGroup(const PodSpec& s,
@@ -361,7 +361,9 @@ bool HivedCore::scheduleNewAffinityGroup(const PodSpec& s,
   sr.hbmBytes = s.hbmBytesPerCell;
   validateSchedulingRequest(sr, podKey);  // also resolves sr.vcScheduler
   if (!sr.pinnedCellId.empty()) {
-    sr.chain = &pinnedPhysical_[s.vc][s.pinnedCellId]->chain;
+    // validated above: the VC has this pinned cell, and its cells know their chain
+    const ChainCellList& pinnedCells = sr.vcScheduler->pinned.find(sr.pinnedCellId)->second;
+    sr.chain = pinnedCells.at(pinnedCells.top())[0]->cs;
     auto it = sr.vcScheduler->pinnedSchedulers.find(sr.pinnedCellId);
     sr.topo = it == sr.vcScheduler->pinnedSchedulers.end() ? nullptr : &it->second;
     return handleSchedulingRequest(sr, phys, hasVirtual, virt, failedReason);
@@ -385,24 +387,24 @@ bool HivedCore::scheduleNewAffinityGroup(const PodSpec& s,
 }
 
 bool HivedCore::scheduleForLeafCellType(SchedulingRequest& sr, const std::string& leafCellType,
-                                        const std::vector<std::string>& chains,
+                                        const std::vector<ChainState*>& chains,
                                         const std::string& podKey, bool typeSpecified,
                                         Placement<PhysicalCell>* phys, bool* hasVirtual,
                                         Placement<VirtualCell>* virt, std::string* failedReason) {
   bool vcHasType = false;
-  for (const std::string& chain : chains) {
-    // one lookup per chain: the placement engine every attempt on it uses.
-    // A VC has an engine for exactly the chains it has cells of
+  for (ChainState* chain : chains) {
+    // the placement engine every attempt on this chain uses. A VC has an
+    // engine for exactly the chains it has non-pinned cells of
     // (nonPinnedSchedulers is built from nonPinnedFull, key for key).
     if (sr.priority < kMinGuaranteedPriority) {
-      sr.topo = &opportunisticSchedulers_.at(chain);
+      sr.topo = &chain->opportunistic;
     } else {
-      auto it = sr.vcScheduler->nonPinnedSchedulers.find(chain);
-      if (it == sr.vcScheduler->nonPinnedSchedulers.end()) continue;
-      sr.topo = &it->second;
+      const VCChainState* vcc = sr.vcScheduler->byChain[chain->index];
+      if (vcc == nullptr || vcc->topo == nullptr) continue;
+      sr.topo = vcc->topo;
     }
     vcHasType = true;
-    sr.chain = &chain;
+    sr.chain = chain;
     if (handleSchedulingRequest(sr, phys, hasVirtual, virt, failedReason)) return true;
   }
   if (typeSpecified && sr.priority >= kMinGuaranteedPriority && !vcHasType) {
@@ -460,7 +462,7 @@ bool HivedCore::scheduleGuaranteedGroup(SchedulingRequest& sr, Placement<Physica
   // the chain's cells and whether any of its links is degraded, looked up
   // once: nothing below changes a link (bad links change only through
   // setXgmiLinkHealthy, a top-level operation of its own)
-  const ChainCellList& fullCells = fullCellList_[*sr.chain];
+  const ChainCellList& fullCells = sr.chain->full;
   const bool badLinks = chainHasBadLinks(fullCells);
 
   // One full placement attempt: intra-VC schedule -> lazy preemption ->
@@ -543,8 +545,8 @@ bool HivedCore::scheduleGuaranteedGroup(SchedulingRequest& sr, Placement<Physica
       if (!firstTry) bindings = seedBindings;  // drop partial picks from a failed attempt
       firstTry = false;
       // working copies, assigned into the scratch's own storage
-      ms.freeList = freeCellList_[*sr.chain];
-      ms.freeCellNum = allVCFreeCellNum_[*sr.chain];
+      ms.freeList = sr.chain->free;
+      ms.freeCellNum = sr.chain->allVCFree;
       return mapVirtualPlacementToPhysical(preassigned, ms.nonPreassigned, ms.nonPreassignedUsed,
                                            ms.freeList, ms.freeCellNum, *sr.suggestedNodes,
                                            sr.ignoreSuggestedNodes, bindings, sr.hbmBytes,
@@ -601,7 +603,7 @@ bool HivedCore::scheduleGuaranteedGroup(SchedulingRequest& sr, Placement<Physica
       std::vector<CleanShapeWorld> computed;
       const std::vector<CleanShapeWorld>* worldsPtr;
       if (filter == nullptr) {
-        WorldCacheEntry& entry = worldCache_[{*sr.chain, tier}];
+        WorldCacheEntry& entry = sr.chain->worldCache[tier];
         if (entry.epoch != gWorldEpochCounter) {
           entry.worlds = computeCleanShapeWorlds(fullCells, nullptr, 4, tier);
           entry.epoch = gWorldEpochCounter;
@@ -614,7 +616,7 @@ bool HivedCore::scheduleGuaranteedGroup(SchedulingRequest& sr, Placement<Physica
       for (const auto& w : *worldsPtr) {
         sr.cleanWorld = &w;
         if (mapDebugRelease()) {
-          fprintf(stderr, "[world] chain=%s tier=%d excl=%zu:", sr.chain->c_str(), tier,
+          fprintf(stderr, "[world] chain=%s tier=%d excl=%zu:", sr.chain->name.c_str(), tier,
                   w.excluded.size());
           for (auto& [l, v] : w.caps) fprintf(stderr, " L%d=%d", l, v);
           fprintf(stderr, "\n");
@@ -827,6 +829,9 @@ Group* HivedCore::insertNewGroup(const PodSpec& s, GState state) {
 Group* HivedCore::createAllocatedGroup(const PodSpec& s, const BindInfo& info,
                                        const std::string& podKey) {
   Group* g = insertNewGroup(s, GState::Allocated);
+  // the pod's VC, found once for all of its leaves (null: no such VC)
+  const IntraVCScheduler* vcs = nullptr;
+  if (auto vcIt = vcSchedulers_.find(s.vc); vcIt != vcSchedulers_.end()) vcs = &vcIt->second;
   bool shouldLazyPreempt = false;
   for (auto& mbi : info.memberBindInfo) {
     if (mbi.empty()) continue;
@@ -838,11 +843,18 @@ Group* HivedCore::createAllocatedGroup(const PodSpec& s, const BindInfo& info,
       g->allocatedPods[leafCellNumber].resize(mbi.size());
     }
     for (size_t podIndex = 0; podIndex < mbi.size(); podIndex++) {
+      // the placement's node, found once for all of its leaves
+      const std::vector<PhysicalCell*>* nodeLeaves = nullptr;
+      if (auto nodeIt = nodeLeafCellsStorage_.find(mbi[podIndex].node);
+          nodeIt != nodeLeafCellsStorage_.end()) {
+        nodeLeaves = &nodeIt->second;
+      }
       for (size_t li = 0; li < mbi[podIndex].leafIndices.size(); li++) {
         bool lazyPreempt = false;
         bool isOpportunistic = false;
-        auto [p, v] = findAllocatedLeafCell(static_cast<int>(li), mbi[podIndex], info.chain, s, g,
-                                            podKey, &lazyPreempt, &isOpportunistic);
+        auto [p, v] = findAllocatedLeafCell(static_cast<int>(li), mbi[podIndex], info.chain, s,
+                                            vcs, nodeLeaves, g, podKey, &lazyPreempt,
+                                            &isOpportunistic);
         if (p == nullptr) {
           // leaf cell address no longer in the spec: ignore this cell
           continue;
@@ -908,9 +920,9 @@ void HivedCore::deleteAllocatedGroup(Group* g, const std::string& podKey) {
   eraseGroup(g);
 }
 
-void HivedCore::createPreemptingGroup(const PodSpec& s, const Placement<PhysicalCell>& phys,
-                                      const Placement<VirtualCell>& virt,
-                                      const std::string& podKey) {
+Group* HivedCore::createPreemptingGroup(const PodSpec& s, const Placement<PhysicalCell>& phys,
+                                        const Placement<VirtualCell>& virt,
+                                        const std::string& podKey) {
   Group* g = insertNewGroup(s, GState::Preempting);
   g->physPlacement = phys;
   g->virtPlacement = virt;
@@ -936,6 +948,7 @@ void HivedCore::createPreemptingGroup(const PodSpec& s, const Placement<Physical
     }
   }
   g->preemptingPods.insert(podKey);
+  return g;
 }
 
 void HivedCore::deletePreemptingGroup(Group* g, const std::string& podKey) {
@@ -1056,7 +1069,8 @@ void HivedCore::revertLazyPreempt(Group* g, const Placement<VirtualCell>& virt) 
 
 std::pair<PhysicalCell*, VirtualCell*> HivedCore::findAllocatedLeafCell(
     int index, const PodPlacementInfo& placement, const std::string& chain, const PodSpec& s,
-    Group* group, const std::string& podKey, bool* lazyPreempt, bool* isOpportunistic) {
+    const IntraVCScheduler* vcs, const std::vector<PhysicalCell*>* nodeLeaves, Group* group,
+    const std::string& podKey, bool* lazyPreempt, bool* isOpportunistic) {
   (void)podKey;
   *lazyPreempt = false;
   *isOpportunistic = false;
@@ -1067,16 +1081,15 @@ std::pair<PhysicalCell*, VirtualCell*> HivedCore::findAllocatedLeafCell(
   // name used in two chains) leave the choice to that search.
   PhysicalCell* p = nullptr;
   int matches = 0;
-  if (auto nodeIt = nodeLeafCellsStorage_.find(placement.node);
-      nodeIt != nodeLeafCellsStorage_.end()) {
-    for (PhysicalCell* leaf : nodeIt->second) {
+  if (nodeLeaves != nullptr) {  // the leaves of placement.node, found by the caller
+    for (PhysicalCell* leaf : *nodeLeaves) {
       if (leaf->leafIndices[0] == leafIndex) {
         p = leaf;
         matches++;
       }
     }
   }
-  if (matches > 1) p = findPhysicalLeafCell(fullCellList_, chain, placement.node, leafIndex);
+  if (matches > 1) p = findPhysicalLeafCell(chainStates_, chain, placement.node, leafIndex);
   if (p == nullptr) return {nullptr, nullptr};
   if (placement.preassignedTypes.empty()) {
     *lazyPreempt = true;
@@ -1093,11 +1106,8 @@ std::pair<PhysicalCell*, VirtualCell*> HivedCore::findAllocatedLeafCell(
     return {p, nullptr};
   }
   int preassignedLevel = -1;
-  auto typesIt = cellTypes_.find(p->chain);
-  if (typesIt != cellTypes_.end()) {
-    for (auto& [l, t] : typesIt->second) {
-      if (t == preassignedType) preassignedLevel = l;
-    }
+  for (int l = kLowestLevel; l <= p->cs->top; l++) {
+    if (p->cs->levelType[l] == preassignedType) preassignedLevel = l;
   }
   if (preassignedLevel > 0) {
     // Ownership-conflict check (reconfiguration/recovery semantics,
@@ -1136,17 +1146,15 @@ std::pair<PhysicalCell*, VirtualCell*> HivedCore::findAllocatedLeafCell(
   std::string message;
   if (preassignedLevel < 0) {
     message = "preassigned cell type " + preassignedType + " not found in chain " + p->chain;
-  } else if (!vcSchedulers_.count(s.vc)) {
+  } else if (vcs == nullptr) {
     message = "VC " + s.vc + " not found";
   } else {
-    IntraVCScheduler& vcs = vcSchedulers_[s.vc];
     const ChainCellList* vccl = nullptr;
     if (!s.pinnedCellId.empty()) {
-      auto it = vcs.pinned.find(s.pinnedCellId);
-      if (it != vcs.pinned.end()) vccl = &it->second;
-    } else {
-      auto it = vcs.nonPinnedPreassigned.find(p->chain);
-      if (it != vcs.nonPinnedPreassigned.end()) vccl = &it->second;
+      auto it = vcs->pinned.find(s.pinnedCellId);
+      if (it != vcs->pinned.end()) vccl = &it->second;
+    } else if (const VCChainState* vcc = vcs->byChain[p->cs->index]) {
+      vccl = vcc->preassigned;
     }
     if (vccl == nullptr) {
       message = "VC " + s.vc + " has no cell for chain " + p->chain;
@@ -1180,7 +1188,7 @@ std::pair<bool, std::string> HivedCore::allocateLeafCell(PhysicalCell* p, Virtua
     VirtualCell* pac = v->preassigned;
     if (pac->phys != nullptr && pac->phys->virt == pac &&
         pac->phys->priority < kMinGuaranteedPriority &&
-        vcDoomedBadCells_[vc][p->chain].contains(pac->phys, pac->phys->level)) {
+        pac->vcChain->doomed.contains(pac->phys, pac->phys->level)) {
       // The preassigned cell was doomed onto a bad physical cell AFTER this
       // placement was computed against a different physical target (the doom
       // machinery can fire mid-commit, e.g. inside an overlapping
@@ -1197,9 +1205,9 @@ std::pair<bool, std::string> HivedCore::allocateLeafCell(PhysicalCell* p, Virtua
         PhysicalCell* doomed = pac->phys;
         pac->phys = nullptr;
         doomed->virt = nullptr;
-        vcDoomedBadCells_[vc][p->chain].remove(doomed, doomed->level);
-        allVCDoomedBadCellNum_[p->chain][doomed->level]--;
-        releasePreassignedCell(doomed, vc, true);
+        pac->vcChain->doomed.remove(doomed, doomed->level);
+        p->cs->allVCDoomedBadCellNum[doomed->level]--;
+        releasePreassignedCell(doomed, pac->vcChain, true);
       }
     }
     bool preassignedNewlyBound = pac->phys == nullptr;
@@ -1220,7 +1228,7 @@ std::pair<bool, std::string> HivedCore::allocateLeafCell(PhysicalCell* p, Virtua
       // authoritative membership: anc, or an unbound ancestor of it, must be
       // DIRECTLY in the free list (inFreeCellList's split-flag shortcut
       // reports stale true for an allocated-but-unbound cell)
-      auto& fl = freeCellList_[p->chain];
+      const ChainCellList& fl = p->cs->free;
       for (PhysicalCell* a = anc; a != nullptr && a->virt == nullptr;
            a = static_cast<PhysicalCell*>(a->parent)) {
         if (a->level <= fl.top() && fl.contains(a, a->level)) {
@@ -1234,7 +1242,7 @@ std::pair<bool, std::string> HivedCore::allocateLeafCell(PhysicalCell* p, Virtua
       bindCell(p, v);
     }
     if (preassignedNewlyBound && preassignedProducible) {
-      std::tie(safetyOk, reason) = allocatePreassignedCell(pac->phys, vc, false);
+      std::tie(safetyOk, reason) = allocatePreassignedCell(pac->phys, pac->vcChain, false);
     }
   } else {
     setCellPriority(p, kOpportunisticPriority);
@@ -1254,7 +1262,7 @@ void HivedCore::releaseLeafCell(PhysicalCell* p, const std::string& vc) {
     p->otVC.clear();
   } else {
     VirtualCell* v = p->virt;
-    const std::string& owner = v->vc;
+    VCChainState* owner = v->vcChain;
     updateUsedLeafCellNumAtPriority(v, v->priority, false);
     setCellPriority(v, kFreePriority);
     PhysicalCell* preassignedPhysical = v->preassigned->phys;
@@ -1264,8 +1272,7 @@ void HivedCore::releaseLeafCell(PhysicalCell* p, const std::string& vc) {
     }
     if (preassignedPhysical != nullptr && !preassignedPhysical->pinned &&
         v->preassigned->priority < kMinGuaranteedPriority &&
-        !vcDoomedBadCells_[owner][preassignedPhysical->chain].contains(
-            preassignedPhysical, preassignedPhysical->level)) {
+        !owner->doomed.contains(preassignedPhysical, preassignedPhysical->level)) {
       releasePreassignedCell(preassignedPhysical, owner, false);
     } else if (mapDebugRelease()) {
       fprintf(stderr, "[rel] keep preassigned %s: phys=%d pinned=%d prio=%d doomed=%d (leaf %s)\n",
@@ -1273,8 +1280,7 @@ void HivedCore::releaseLeafCell(PhysicalCell* p, const std::string& vc) {
               preassignedPhysical != nullptr && preassignedPhysical->pinned,
               v->preassigned->priority,
               preassignedPhysical != nullptr &&
-                  vcDoomedBadCells_[owner][preassignedPhysical->chain].contains(
-                      preassignedPhysical, preassignedPhysical->level),
+                  owner->doomed.contains(preassignedPhysical, preassignedPhysical->level),
               p->address.c_str());
     }
   }

@@ -17,6 +17,11 @@ static bool mapDebug() {
 
 namespace {
 
+// The mapper's lists of physical cells (usable candidates, picks): a handful
+// each, built at every level of the recursion, so they live on the frame that
+// builds them and reach for the heap only beyond 16 cells.
+using PhysList = SmallVec<PhysicalCell*, 16>;
+
 // Refcounted claims with an undo journal: physical leaves (and their
 // ancestors) claimed by picks of THIS mapping round. The journal makes
 // backtracking EXACT — abandoned branches are fully unclaimed. That matters
@@ -28,7 +33,7 @@ namespace {
 // quad still saw its abandoned quad's claims).
 struct ClaimSet {
   SmallPtrMap<PhysicalCell, int, 32> refs;
-  std::vector<PhysicalCell*> log;  // claimed leaves, in order
+  SmallVec<PhysicalCell*, 32> log;  // claimed leaves, in order
 
   bool count(PhysicalCell* c) const { return refs.count(c) > 0; }
   size_t checkpoint() const { return log.size(); }
@@ -100,8 +105,7 @@ bool leafLinkConflict(const AllocCtx& ctx, PhysicalCell* leaf) {
 // Fills `usable` (emptied first); leaves it empty when fewer than numNeeded
 // cells are usable.
 void getUsablePhysicalCells(const std::vector<Cell*>& candidates, int numNeeded,
-                            const AllocCtx& ctx, int demandLeaves,
-                            std::vector<PhysicalCell*>& usable) {
+                            const AllocCtx& ctx, int demandLeaves, PhysList& usable) {
   usable.clear();
   for (Cell* cc : candidates) {
     auto* c = static_cast<PhysicalCell*>(cc);
@@ -189,7 +193,7 @@ void getUsablePhysicalCells(const std::vector<Cell*>& candidates, int numNeeded,
 // recursing into children to preserve the intra-cell topology.
 bool mapVirtualCellsToPhysical(BindingVertex* const* cellsIn, size_t numCells,
                                const std::vector<Cell*>& candidatesIn, const AllocCtx& ctx,
-                               bool returnPicked, std::vector<PhysicalCell*>* picked) {
+                               bool returnPicked, PhysList* picked) {
   // Multi-leaf vertices map first (demand descending) so they get the
   // link-clean candidates and single-leaf vertices take the leftovers
   // (incl. degraded pairs, which suit them fine).
@@ -204,7 +208,7 @@ bool mapVirtualCellsToPhysical(BindingVertex* const* cellsIn, size_t numCells,
       return vertexLeafDemand(a) > vertexLeafDemand(b);
     });
   }
-  std::vector<PhysicalCell*> candidates;
+  PhysList candidates;  // this depth's own
   getUsablePhysicalCells(candidatesIn, static_cast<int>(cells.size()), ctx, maxDemand, candidates);
   if (candidates.empty() && numCells != 0) return false;
   int n = static_cast<int>(cells.size());
@@ -274,7 +278,7 @@ bool buddyAlloc(BindingVertex* cell, ChainCellList& freeList, int currentLevel,
     fprintf(stderr, "\n");
   }
   if (currentLevel == cell->cell->level) {
-    std::vector<PhysicalCell*> picked;
+    PhysList picked;
     if (mapVirtualCellsToPhysical(&cell, 1, freeList.at(currentLevel), ctx, true, &picked)) {
       for (PhysicalCell* c : picked) freeList.remove(c, currentLevel);
       if (mapDebug())
@@ -284,7 +288,7 @@ bool buddyAlloc(BindingVertex* cell, ChainCellList& freeList, int currentLevel,
     if (mapDebug()) fprintf(stderr, "[map]  -> no usable candidate at own level\n");
     return false;
   }
-  std::vector<PhysicalCell*> freeCells;
+  PhysList freeCells;  // this level's own
   getUsablePhysicalCells(freeList.at(currentLevel), 1, ctx, vertexLeafDemand(cell), freeCells);
   if (freeCells.empty()) return false;
   for (PhysicalCell* c : freeCells) {
@@ -306,15 +310,14 @@ bool buddyAlloc(BindingVertex* cell, ChainCellList& freeList, int currentLevel,
 // free cells beyond the buddy path, but only as many as safety allows
 // (splittable = free cells minus cells the VCs still need reserved).
 bool safeRelaxedBuddyAlloc(BindingVertex* cell, ChainCellList& freeList,
-                           std::map<int, int>& freeCellNum, int currentLevel,
+                           const std::vector<int>& freeCellNum, int currentLevel,
                            const AllocCtx& ctx) {
   if (mapDebug()) fprintf(stderr, "[map] safeRelaxed for virt level=%d\n", currentLevel);
   int top = freeList.top();
   std::map<int, int> splittableNum;
   Cell* splittableCell = nullptr;
   for (int i = top; i > currentLevel; i--) {
-    splittableNum[i] =
-        static_cast<int>(freeList.at(i).size()) - (freeCellNum.count(i) ? freeCellNum[i] : 0);
+    splittableNum[i] = static_cast<int>(freeList.at(i).size()) - freeCellNum[i];
     if (i < top && splittableCell != nullptr) {
       splittableNum[i] += splittableNum[i + 1] * static_cast<int>(splittableCell->children.size());
     }
@@ -349,7 +352,7 @@ bool safeRelaxedBuddyAlloc(BindingVertex* cell, ChainCellList& freeList,
     // prepend the split cells so they are tried first
     auto& cur = freeList.at(currentLevel);
     cur.insert(cur.begin(), splitList.begin(), splitList.end());
-    std::vector<PhysicalCell*> picked;
+    PhysList picked;
     if (mapVirtualCellsToPhysical(&cell, 1, cur, ctx, true, &picked)) {
       for (PhysicalCell* c : picked) freeList.remove(c, currentLevel);
       if (mapDebug())
@@ -373,7 +376,7 @@ int getLowestFreeCellLevel(const ChainCellList& freeList, int l) {
 bool HivedCore::mapVirtualPlacementToPhysical(
     const std::vector<BindingVertex*>& preassigned,
     const std::vector<std::vector<BindingVertex*>>& nonPreassigned, size_t nonPreassignedCount,
-    ChainCellList& freeList, std::map<int, int>& freeCellNum,
+    ChainCellList& freeList, std::vector<int>& freeCellNum,
     const std::set<std::string>& suggestedNodes, bool ignoreSuggestedNodes, CellBindings& bindings,
     long long minHbmBytes, bool honorLinks, const CleanShapeWorld* world) {
   ClaimSet claimed;
@@ -415,23 +418,19 @@ bool HivedCore::mapVirtualPlacementToPhysical(
   // across multiple higher-level free cells and stranded another VC's
   // guarantee. Rejecting here turns that into a correct "wait".
   if (!preassigned.empty()) {
-    const std::string& chain = preassigned[0]->cell->chain;
-    auto avfIt = allVCFreeCellNum_.find(chain);
-    if (avfIt != allVCFreeCellNum_.end()) {
-      int top = freeList.top();
-      int producible = 0;
-      for (int l = top; l >= kLowestLevel; l--) {
-        if (l < top && !fullCellList_[chain].at(l + 1).empty()) {
-          producible *= static_cast<int>(fullCellList_[chain].at(l + 1)[0]->children.size());
-        }
-        producible += static_cast<int>(freeList.at(l).size());
-        auto needIt = avfIt->second.find(l);
-        int need = needIt == avfIt->second.end() ? 0 : needIt->second;
-        for (BindingVertex* c : preassigned) {
-          if (c->cell->level == l) need--;  // this placement's new preassigned bindings
-        }
-        if (producible < need) return false;
+    const ChainState* chain = preassigned[0]->cell->cs;
+    int top = freeList.top();
+    int producible = 0;
+    for (int l = top; l >= kLowestLevel; l--) {
+      if (l < top && !chain->full.at(l + 1).empty()) {
+        producible *= static_cast<int>(chain->full.at(l + 1)[0]->children.size());
       }
+      producible += static_cast<int>(freeList.at(l).size());
+      int need = chain->allVCFree[l];
+      for (BindingVertex* c : preassigned) {
+        if (c->cell->level == l) need--;  // this placement's new preassigned bindings
+      }
+      if (producible < need) return false;
     }
   }
   return true;
@@ -442,7 +441,7 @@ bool HivedCore::mapVirtualPlacementToPhysical(
 // Remove a cell from the free list, splitting unsplit ancestors on the way up.
 // Returns the highest level at which a cell was removed.
 int HivedCore::removeCellFromFreeList(PhysicalCell* c) {
-  ChainCellList& freeList = freeCellList_[c->chain];
+  ChainCellList& freeList = c->cs->free;
   bool terminate = false;
   for (;;) {
     int l = c->level;
@@ -466,7 +465,7 @@ int HivedCore::removeCellFromFreeList(PhysicalCell* c) {
 // Add a cell back to the free list, merging buddies into the parent while all
 // of them are free. Returns the highest level at which a cell was added.
 int HivedCore::addCellToFreeList(PhysicalCell* c) {
-  ChainCellList& freeList = freeCellList_[c->chain];
+  ChainCellList& freeList = c->cs->free;
   bool terminate = false;
   for (;;) {
     int l = c->level;
@@ -501,29 +500,29 @@ int HivedCore::addCellToFreeList(PhysicalCell* c) {
 // --- preassigned-cell allocation + safety & doomed-bad accounting -----------
 
 std::pair<bool, std::string> HivedCore::allocatePreassignedCell(PhysicalCell* c,
-                                                                const std::string& vcn,
+                                                                VCChainState* vcc,
                                                                 bool doomedBad) {
   bool safetyOk = true;
   std::string reason;
-  const std::string& chain = c->chain;
+  ChainState* chain = c->cs;
   int level = c->level;
-  vcFreeCellNum_[vcn][chain][level]--;
-  allVCFreeCellNum_[chain][level]--;
-  totalLeftCellNum_[chain][level]--;
+  vcc->free[level]--;
+  chain->allVCFree[level]--;
+  chain->totalLeft[level]--;
   int splitLevelUpTo = removeCellFromFreeList(c);
 
   Cell* parent = c->parent;
   for (int l = level + 1; l <= splitLevelUpTo; l++) {
-    totalLeftCellNum_[chain][l]--;
-    if (totalLeftCellNum_[chain][l] < allVCFreeCellNum_[chain][l]) {
+    chain->totalLeft[l]--;
+    if (chain->totalLeft[l] < chain->allVCFree[l]) {
       safetyOk = false;
-      reason = "Adding pod would lead to broken safety: cell type " + cellTypes_[chain][l] + ", " +
-               std::to_string(totalLeftCellNum_[chain][l]) + " left, " +
-               std::to_string(allVCFreeCellNum_[chain][l]) + " free cells in all VCs";
+      reason = "Adding pod would lead to broken safety: cell type " + chain->levelType[l] + ", " +
+               std::to_string(chain->totalLeft[l]) + " left, " +
+               std::to_string(chain->allVCFree[l]) + " free cells in all VCs";
     }
     if (!static_cast<PhysicalCell*>(parent)->healthy) {
       // parent bad: healthy-free count unchanged; just drop it from bad frees
-      badFreeCells_[chain].remove(parent, l);
+      chain->badFree.remove(parent, l);
     } else {
       // parent healthy: healthy-free count decreased; maybe doom VC cells
       tryBindDoomedBadCell(chain, l);
@@ -538,32 +537,32 @@ std::pair<bool, std::string> HivedCore::allocatePreassignedCell(PhysicalCell* c,
   }
   int numToReduce = static_cast<int>(c->children.size());
   for (int l = level - 1; l >= kLowestLevel; l--) {
-    totalLeftCellNum_[chain][l] -= numToReduce;
-    if (totalLeftCellNum_[chain][l] < allVCFreeCellNum_[chain][l]) {
+    chain->totalLeft[l] -= numToReduce;
+    if (chain->totalLeft[l] < chain->allVCFree[l]) {
       safetyOk = false;
-      reason = "Adding pod would lead to broken safety: cell type " + cellTypes_[chain][l] + ", " +
-               std::to_string(totalLeftCellNum_[chain][l]) + " left, " +
-               std::to_string(allVCFreeCellNum_[chain][l]) + " free cells in all VCs";
+      reason = "Adding pod would lead to broken safety: cell type " + chain->levelType[l] + ", " +
+               std::to_string(chain->totalLeft[l]) + " left, " +
+               std::to_string(chain->allVCFree[l]) + " free cells in all VCs";
     }
     if (!doomedBad) tryBindDoomedBadCell(chain, l);
-    numToReduce *= static_cast<int>(fullCellList_[chain].at(l)[0]->children.size());
+    numToReduce *= static_cast<int>(chain->full.at(l)[0]->children.size());
   }
   return {safetyOk, reason};
 }
 
-void HivedCore::releasePreassignedCell(PhysicalCell* c, const std::string& vcn, bool doomedBad) {
-  const std::string& chain = c->chain;
+void HivedCore::releasePreassignedCell(PhysicalCell* c, VCChainState* vcc, bool doomedBad) {
+  ChainState* chain = c->cs;
   int level = c->level;
-  vcFreeCellNum_[vcn][chain][level]++;
-  allVCFreeCellNum_[chain][level]++;
-  totalLeftCellNum_[chain][level]++;
+  vcc->free[level]++;
+  chain->allVCFree[level]++;
+  chain->totalLeft[level]++;
   int mergeLevelUpTo = addCellToFreeList(c);
 
   Cell* parent = c->parent;
   for (int l = level + 1; l <= mergeLevelUpTo; l++) {
-    totalLeftCellNum_[chain][l]++;
+    chain->totalLeft[l]++;
     if (!static_cast<PhysicalCell*>(parent)->healthy) {
-      badFreeCells_[chain].add(parent, l);
+      chain->badFree.add(parent, l);
     } else {
       tryUnbindDoomedBadCell(chain, l);
     }
@@ -577,17 +576,17 @@ void HivedCore::releasePreassignedCell(PhysicalCell* c, const std::string& vcn, 
   }
   int numToAdd = static_cast<int>(c->children.size());
   for (int l = level - 1; l >= kLowestLevel; l--) {
-    totalLeftCellNum_[chain][l] += numToAdd;
+    chain->totalLeft[l] += numToAdd;
     if (!doomedBad) tryUnbindDoomedBadCell(chain, l);
-    numToAdd *= static_cast<int>(fullCellList_[chain].at(l)[0]->children.size());
+    numToAdd *= static_cast<int>(chain->full.at(l)[0]->children.size());
   }
 }
 
 // A bad free cell being allocated: bind each bad child to a virtual cell so
 // the VC scheduler sees the failure.
 void HivedCore::allocateBadCell(PhysicalCell* c) {
-  if (badFreeCells_[c->chain].contains(c, c->level)) {
-    badFreeCells_[c->chain].remove(c, c->level);
+  if (c->cs->badFree.contains(c, c->level)) {
+    c->cs->badFree.remove(c, c->level);
   }
   if (c->virt == nullptr) {
     VirtualCell* vc = getUnboundVirtualCell(static_cast<PhysicalCell*>(c->parent)->virt->children);
@@ -601,7 +600,7 @@ void HivedCore::allocateBadCell(PhysicalCell* c) {
 }
 
 void HivedCore::releaseBadCell(PhysicalCell* c) {
-  badFreeCells_[c->chain].add(c, c->level);
+  c->cs->badFree.add(c, c->level);
   if (VirtualCell* vc = c->virt) {
     c->virt = nullptr;
     vc->phys = nullptr;
@@ -755,12 +754,12 @@ void HivedCore::setHealthyCell(PhysicalCell* c) {
       c->virt = nullptr;
       vc->phys = nullptr;
       if (vc->parent == nullptr) {
-        auto& doomed = vcDoomedBadCells_[vc->vc][c->chain];
+        auto& doomed = vc->vcChain->doomed;
         if (c->level <= doomed.top() && doomed.contains(c, c->level)) {
           // a doomed bad cell healing: undo the doom's accounting
           doomed.remove(c, c->level);
-          allVCDoomedBadCellNum_[c->chain][c->level]--;
-          releasePreassignedCell(c, vc->vc, true);
+          c->cs->allVCDoomedBadCellNum[c->level]--;
+          releasePreassignedCell(c, vc->vcChain, true);
         }
         // else: an allocated-bad preassigned whose pods already left — its
         // accounting was released at pod-delete time while the binding was
@@ -768,12 +767,12 @@ void HivedCore::setHealthyCell(PhysicalCell* c) {
         // threw on the registry remove and double-released the accounting)
       }
     } else if (!c->pinned && vc->parent == nullptr &&
-               vcDoomedBadCells_[vc->vc][c->chain].contains(c, c->level)) {
+               vc->vcChain->doomed.contains(c, c->level)) {
       // a doomed bad cell now healthy AND in real use: it is no longer
       // "doomed" — it transitions to a normally-allocated preassigned cell
       // (keeps its binding; releaseLeafCell will release it when free)
-      vcDoomedBadCells_[vc->vc][c->chain].remove(c, c->level);
-      allVCDoomedBadCellNum_[c->chain][c->level]--;
+      vc->vcChain->doomed.remove(c, c->level);
+      c->cs->allVCDoomedBadCellNum[c->level]--;
     }
   }
   if (c->parent == nullptr) return;
@@ -784,21 +783,21 @@ void HivedCore::setHealthyCell(PhysicalCell* c) {
 }
 
 void HivedCore::addBadFreeCell(PhysicalCell* c) {
-  const std::string& chain = c->chain;
+  ChainState* chain = c->cs;
   int level = c->level;
-  badFreeCells_[chain].add(c, level);
-  if (allVCFreeCellNum_[chain][level] >
-      totalLeftCellNum_[chain][level] - static_cast<int>(badFreeCells_[chain].at(level).size())) {
+  chain->badFree.add(c, level);
+  if (chain->allVCFree[level] >
+      chain->totalLeft[level] - static_cast<int>(chain->badFree.at(level).size())) {
     tryBindDoomedBadCell(chain, level);
   }
 }
 
 void HivedCore::removeBadFreeCell(PhysicalCell* c) {
-  badFreeCells_[c->chain].remove(c, c->level);
-  tryUnbindDoomedBadCell(c->chain, c->level);
+  c->cs->badFree.remove(c, c->level);
+  tryUnbindDoomedBadCell(c->cs, c->level);
 }
 
-// Dooming allocates the bad physical cell out of the free list. badFreeCells_
+// Dooming allocates the bad physical cell out of the free list. badFree
 // contains SUBSUMED cells (free via an unsplit ancestor), and allocating one
 // of those splits every unsplit ancestor — removing a cell from totalLeft at
 // each split level — and removes the candidate's producible children below.
@@ -806,21 +805,21 @@ void HivedCore::removeBadFreeCell(PhysicalCell* c) {
 // VC's quad-level guarantee (totalLeft < allVCFree). A candidate is only
 // eligible if no level's guarantee would break.
 bool HivedCore::doomAllocationIsSafe(PhysicalCell* pc) {
-  const std::string& chain = pc->chain;
+  const ChainState* chain = pc->cs;
   PhysicalCell* a = pc;
   while (a->parent != nullptr && !static_cast<PhysicalCell*>(a->parent)->split) {
     a = static_cast<PhysicalCell*>(a->parent);
-    if (totalLeftCellNum_[chain][a->level] - 1 < allVCFreeCellNum_[chain][a->level]) return false;
+    if (chain->totalLeft[a->level] - 1 < chain->allVCFree[a->level]) return false;
   }
   int numToReduce = static_cast<int>(pc->children.size());
   for (int l = pc->level - 1; l >= kLowestLevel && numToReduce > 0; l--) {
-    if (totalLeftCellNum_[chain][l] - numToReduce < allVCFreeCellNum_[chain][l]) return false;
-    numToReduce *= static_cast<int>(fullCellList_[chain].at(l)[0]->children.size());
+    if (chain->totalLeft[l] - numToReduce < chain->allVCFree[l]) return false;
+    numToReduce *= static_cast<int>(chain->full.at(l)[0]->children.size());
   }
   return true;
 }
 
-void HivedCore::tryBindDoomedBadCell(const std::string& chain, int level) {
+void HivedCore::tryBindDoomedBadCell(ChainState* chain, int level) {
   if (inOperation_) {
     pendingDoomChecks_.emplace_back(chain, level);
     return;
@@ -828,7 +827,7 @@ void HivedCore::tryBindDoomedBadCell(const std::string& chain, int level) {
   doBindDoomedBadCell(chain, level);
 }
 
-void HivedCore::tryUnbindDoomedBadCell(const std::string& chain, int level) {
+void HivedCore::tryUnbindDoomedBadCell(ChainState* chain, int level) {
   if (inOperation_) {
     pendingDoomChecks_.emplace_back(chain, level);
     return;
@@ -837,11 +836,20 @@ void HivedCore::tryUnbindDoomedBadCell(const std::string& chain, int level) {
 }
 
 void HivedCore::drainDoomChecks() {
+  // First in, first out, by a moving head: a check that a running check
+  // triggers queues up behind the ones still waiting, and the queue is
+  // emptied in one piece at the end. On the way out through an exception the
+  // checks already taken (done) leave the queue and the rest stay pending.
+  auto& queue = pendingDoomChecks_;
+  size_t head = 0;
+  auto dropTaken = [&] { queue.erase(queue.begin(), queue.begin() + static_cast<std::ptrdiff_t>(head)); };
   int guard = 0;
-  while (!pendingDoomChecks_.empty()) {
-    if (++guard > 100000) throw HivedError::Internal("doom-check drain did not converge");
-    auto [chain, level] = pendingDoomChecks_.front();
-    pendingDoomChecks_.erase(pendingDoomChecks_.begin());
+  while (head < queue.size()) {
+    if (++guard > 100000) {
+      dropTaken();
+      throw HivedError::Internal("doom-check drain did not converge");
+    }
+    auto [chain, level] = queue[head++];  // a copy: the checks below may grow the queue
     // execute with the operation flag set so nested triggers re-queue
     inOperation_ = true;
     try {
@@ -849,25 +857,28 @@ void HivedCore::drainDoomChecks() {
       doBindDoomedBadCell(chain, level);
     } catch (...) {
       inOperation_ = false;
+      dropTaken();
       throw;
     }
     inOperation_ = false;
   }
+  queue.clear();
 }
 
 // If healthy free cells < a VC's free cells at some level, some of the VC's
 // cells are inevitably bad: bind bad physical cells to free virtual cells so
 // users and the intra-VC scheduler can see them.
-void HivedCore::doBindDoomedBadCell(const std::string& chain, int level) {
-  for (auto& [vcName, vcFreeNum] : vcFreeCellNum_) {
-    auto chainIt = vcFreeNum.find(chain);
-    if (chainIt == vcFreeNum.end()) continue;
-    while (chainIt->second[level] >
-           totalLeftCellNum_[chain][level] -
-               static_cast<int>(badFreeCells_[chain].at(level).size())) {
-      if (badFreeCells_[chain].at(level).empty()) return;
+void HivedCore::doBindDoomedBadCell(ChainState* chain, int level) {
+  // Only a bad free cell of this level can be doomed, and the loop below gives
+  // up as soon as it needs one and finds none. Read now, when the check runs:
+  // the list may have changed since the check was queued.
+  if (chain->badFree.at(level).empty()) return;
+  for (VCChainState* vcc : chain->vcs) {
+    while (vcc->free[level] >
+           chain->totalLeft[level] - static_cast<int>(chain->badFree.at(level).size())) {
+      if (chain->badFree.at(level).empty()) return;
       PhysicalCell* pc = nullptr;
-      for (Cell* cand : badFreeCells_[chain].at(level)) {
+      for (Cell* cand : chain->badFree.at(level)) {
         // Only cells DIRECTLY in the free list at this level are eligible:
         // a subsumed candidate (free via an unsplit ancestor) would require
         // splitting that ancestor, and tryBindDoomedBadCell can fire
@@ -876,8 +887,7 @@ void HivedCore::doBindDoomedBadCell(const std::string& chain, int level) {
         // (fuzz-found crash: "cell not found in list when removing").
         // The ancestor itself is bad and listed at ITS level, so node-level
         // dooming still covers the VC's higher-level quota.
-        if (!freeCellList_[chain].at(level).empty() &&
-            freeCellList_[chain].contains(cand, level) &&
+        if (!chain->free.at(level).empty() && chain->free.contains(cand, level) &&
             doomAllocationIsSafe(static_cast<PhysicalCell*>(cand))) {
           pc = static_cast<PhysicalCell*>(cand);
           break;
@@ -886,32 +896,31 @@ void HivedCore::doBindDoomedBadCell(const std::string& chain, int level) {
       if (pc == nullptr) return;  // no directly-free, safety-preserving candidate
       if (mapDebug())
         fprintf(stderr, "[doom] bind %s level=%d for vc=%s\n", pc->address.c_str(), level,
-                vcName.c_str());
-      auto& pre = vcSchedulers_[vcName].nonPinnedPreassigned;
-      auto preIt = pre.find(chain);
+                vcc->vc.c_str());
       VirtualCell* vc = nullptr;
-      if (preIt != pre.end() && level <= preIt->second.top()) {
-        vc = getUnboundVirtualCell(preIt->second.at(level));
+      if (vcc->preassigned != nullptr && level <= vcc->preassigned->top()) {
+        vc = getUnboundVirtualCell(vcc->preassigned->at(level));
       }
       if (vc == nullptr) return;  // no more free preassigned cells to doom
       pc->virt = vc;
       vc->phys = pc;
-      vcDoomedBadCells_[vcName][chain].add(pc, level);
-      allVCDoomedBadCellNum_[chain][level]++;
-      allocatePreassignedCell(pc, vcName, true);
+      vcc->doomed.add(pc, level);
+      chain->allVCDoomedBadCellNum[level]++;
+      allocatePreassignedCell(pc, vcc, true);
     }
   }
 }
 
-void HivedCore::doUnbindDoomedBadCell(const std::string& chain, int level) {
-  for (auto& [vcName, vcFreeNum] : vcFreeCellNum_) {
-    auto chainIt = vcFreeNum.find(chain);
-    if (chainIt == vcFreeNum.end()) continue;
-    auto& doomed = vcDoomedBadCells_[vcName][chain];
-    if (level > doomed.top()) continue;
-    while (chainIt->second[level] <
-           totalLeftCellNum_[chain][level] -
-               static_cast<int>(badFreeCells_[chain].at(level).size())) {
+void HivedCore::doUnbindDoomedBadCell(ChainState* chain, int level) {
+  // Nothing is doomed at this level in any VC (the count moves with every add
+  // to and removal from a VC's doomed list): nothing to lift. Read now, when
+  // the check runs, as above.
+  if (chain->allVCDoomedBadCellNum[level] == 0) return;
+  for (VCChainState* vcc : chain->vcs) {
+    ChainCellList& doomed = vcc->doomed;
+    if (doomed.at(level).empty()) continue;
+    while (vcc->free[level] <
+           chain->totalLeft[level] - static_cast<int>(chain->badFree.at(level).size())) {
       // release only doomed cells whose binding exists purely because they
       // are bad (not in real use by a group scheduled onto healthy leaves)
       PhysicalCell* pc = nullptr;
@@ -924,12 +933,12 @@ void HivedCore::doUnbindDoomedBadCell(const std::string& chain, int level) {
       if (pc == nullptr) break;
       if (mapDebug())
         fprintf(stderr, "[doom] unbind %s level=%d vc=%s\n", pc->address.c_str(), level,
-                vcName.c_str());
+                vcc->vc.c_str());
       pc->virt->phys = nullptr;
       pc->virt = nullptr;
       doomed.remove(pc, level);
-      allVCDoomedBadCellNum_[chain][level]--;
-      releasePreassignedCell(pc, vcName, true);
+      chain->allVCDoomedBadCellNum[level]--;
+      releasePreassignedCell(pc, vcc, true);
     }
   }
 }

@@ -1221,8 +1221,9 @@ class PyHivedCore {
 
   py::list getPhysicalClusterStatus() {
     py::list out;
-    for (auto& [chain, ccl] : core_.fullCellList_) {
+    for (auto& [chain, st] : core_.chainStates_) {
       (void)chain;
+      const ChainCellList& ccl = st.full;
       int top = ccl.top();
       for (Cell* c : ccl.at(top)) {
         out.append(physicalCellStatus(static_cast<PhysicalCell*>(c)));
@@ -1261,9 +1262,9 @@ class PyHivedCore {
       }
     }
     // opportunistic cells used by this VC, exposed as fake virtual cells
-    for (auto& [chain, ccl] : core_.fullCellList_) {
+    for (auto& [chain, st] : core_.chainStates_) {
       (void)chain;
-      for (Cell* c : ccl.at(kLowestLevel)) {
+      for (Cell* c : st.full.at(kLowestLevel)) {
         auto* pc = static_cast<PhysicalCell*>(c);
         if (pc->otVC == vcName) {
           py::dict d;
@@ -1287,41 +1288,22 @@ class PyHivedCore {
     // safety-accounting introspection for tests/debugging: per chain+level
     // totalLeft / allVCFree / per-VC free / bad-free count
     py::dict d;
-    for (auto& [chain, perLevel] : core_.totalLeftCellNum_) {
+    for (auto& [chain, st] : core_.chainStates_) {
       py::dict cd;
-      for (auto& [level, left] : perLevel) {
+      for (int level = kLowestLevel; level <= st.top; level++) {
         py::dict ld;
-        ld["totalLeft"] = left;
-        int avf = 0;
-        auto ai = core_.allVCFreeCellNum_.find(chain);
-        if (ai != core_.allVCFreeCellNum_.end()) {
-          auto li = ai->second.find(level);
-          if (li != ai->second.end()) avf = li->second;
-        }
-        ld["allVCFree"] = avf;
+        ld["totalLeft"] = st.totalLeft[level];
+        ld["allVCFree"] = st.allVCFree[level];
         py::dict vd;
-        for (auto& [vcn, perChain] : core_.vcFreeCellNum_) {
-          auto ci = perChain.find(chain);
-          if (ci == perChain.end()) continue;
-          auto li = ci->second.find(level);
-          if (li != ci->second.end() && li->second != 0) vd[py::str(vcn)] = li->second;
+        for (const VCChainState* vcc : st.vcs) {  // in VC-name order
+          if (vcc->free[level] != 0) vd[py::str(vcc->vc)] = vcc->free[level];
         }
         ld["vcFree"] = vd;
-        auto fi = core_.freeCellList_.find(chain);
-        if (fi != core_.freeCellList_.end() && level <= fi->second.top()) {
-          py::list fl;
-          for (auto* fc : fi->second.at(level)) fl.append(fc->address);
-          ld["freeList"] = fl;
-        }
-        auto di = core_.allVCDoomedBadCellNum_.find(chain);
-        if (di != core_.allVCDoomedBadCellNum_.end()) {
-          auto li2 = di->second.find(level);
-          if (li2 != di->second.end() && li2->second != 0) ld["doomed"] = li2->second;
-        }
-        auto bi = core_.badFreeCells_.find(chain);
-        if (bi != core_.badFreeCells_.end() && level <= bi->second.top()) {
-          ld["badFree"] = static_cast<int>(bi->second.at(level).size());
-        }
+        py::list fl;
+        for (auto* fc : st.free.at(level)) fl.append(fc->address);
+        ld["freeList"] = fl;
+        if (st.allVCDoomedBadCellNum[level] != 0) ld["doomed"] = st.allVCDoomedBadCellNum[level];
+        ld["badFree"] = static_cast<int>(st.badFree.at(level).size());
         cd[py::int_(level)] = ld;
       }
       d[py::str(chain)] = cd;

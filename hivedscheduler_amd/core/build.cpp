@@ -61,12 +61,14 @@ struct BuildContext {
   BuildContext(HivedCore* h_, const ClusterSpec& s) : h(h_), spec(s) {}
 
   PhysicalCell* buildPhysicalCell(const PhysCellSpec& cs, const ChainMeta& meta,
-                                  const std::string& chain, int level,
+                                  ChainState* chainState, int level,
                                   const std::string& parentAddr, const std::string& nodeName) {
+    const std::string& chain = chainState->name;
     auto cell = std::make_unique<PhysicalCell>();
     PhysicalCell* c = cell.get();
     h->cellStore_.push_back(std::move(cell));
     c->chain = chain;
+    c->cs = chainState;
     c->level = level;
     c->typeName = meta.typeAt(level);
     c->isNodeLevel = meta.isNodeAt(level);
@@ -116,7 +118,7 @@ struct BuildContext {
       }
       for (const auto& childSpec : cs.children) {
         PhysicalCell* child =
-            buildPhysicalCell(childSpec, meta, chain, level - 1, c->address, ownNodeName);
+            buildPhysicalCell(childSpec, meta, chainState, level - 1, c->address, ownNodeName);
         child->parent = c;
         c->children.push_back(child);
         c->totalLeaf += child->totalLeaf;
@@ -128,19 +130,20 @@ struct BuildContext {
         for (int gi : child->leafIndices) c->leafIndices.push_back(gi);
       }
     }
-    h->fullCellList_[chain].add(c, level);
+    chainState->full.add(c, level);
     return c;
   }
 
-  VirtualCell* buildVirtualCell(const std::string& vc, const std::string& chain,
-                                const ChainMeta& meta, int level, VirtualCell* preassigned,
-                                const std::string& addr, const std::string& pinnedId,
-                                ChainCellList& fullList) {
+  VirtualCell* buildVirtualCell(VCChainState* vcChain, const ChainMeta& meta, int level,
+                                VirtualCell* preassigned, const std::string& addr,
+                                const std::string& pinnedId, ChainCellList& fullList) {
     auto cell = std::make_unique<VirtualCell>();
     VirtualCell* c = cell.get();
     h->cellStore_.push_back(std::move(cell));
-    c->vc = vc;
-    c->chain = chain;
+    c->vc = vcChain->vc;
+    c->chain = vcChain->chain->name;
+    c->cs = vcChain->chain;
+    c->vcChain = vcChain;
     c->level = level;
     c->typeName = meta.typeAt(level);
     c->isNodeLevel = meta.isNodeAt(level);
@@ -154,7 +157,7 @@ struct BuildContext {
     } else {
       int childNum = childCountAt(spec.cellTypes, c->typeName);
       for (int i = 0; i < childNum; i++) {
-        VirtualCell* child = buildVirtualCell(vc, chain, meta, level - 1, c->preassigned,
+        VirtualCell* child = buildVirtualCell(vcChain, meta, level - 1, c->preassigned,
                                               addr + "/" + std::to_string(i), pinnedId, fullList);
         child->parent = c;
         c->children.push_back(child);
@@ -166,25 +169,54 @@ struct BuildContext {
     return c;
   }
 
+  // the VC's record on a chain, made on first use
+  VCChainState* vcChainState(const std::string& vcName, ChainState* chainState) {
+    auto& perChain = h->vcChainStates_[vcName];
+    auto it = perChain.find(chainState->name);
+    if (it != perChain.end()) return &it->second;
+    VCChainState& vcc = perChain[chainState->name];
+    vcc.vc = vcName;
+    vcc.chain = chainState;
+    vcc.free.assign(chainState->top + 1, 0);
+    vcc.doomed.init(chainState->top);
+    h->vcSchedulers_[vcName].byChain[chainState->index] = &vcc;
+    return &vcc;
+  }
+
   void build() {
     // --- physical cluster ---
     for (const auto& cs : spec.physicalCells) {
       const std::string& chain = cs.type;
       if (!chainMeta.count(chain)) chainMeta.emplace(chain, buildChainMeta(spec.cellTypes, chain));
       const ChainMeta& meta = chainMeta.at(chain);
-      if (!h->fullCellList_.count(chain)) {
-        h->fullCellList_[chain].init(meta.topLevel());
-        h->freeCellList_[chain].init(meta.topLevel());
-        for (int l = 1; l <= meta.topLevel(); l++) {
-          h->cellTypes_[chain][l] = meta.typeAt(l);
-        }
+      if (!h->chainStates_.count(chain)) {
+        ChainState& st = h->chainStates_[chain];
+        st.name = chain;
+        st.top = meta.topLevel();
+        st.full.init(st.top);
+        st.free.init(st.top);
+        st.badFree.init(st.top);
+        st.levelType.assign(st.top + 1, std::string());
+        for (int l = 1; l <= st.top; l++) st.levelType[l] = meta.typeAt(l);
+        st.totalLeft.assign(st.top + 1, 0);
+        st.allVCFree.assign(st.top + 1, 0);
+        st.allVCDoomedBadCellNum.assign(st.top + 1, 0);
       }
-      PhysicalCell* top = buildPhysicalCell(cs, meta, chain, meta.topLevel(), "", "");
-      h->freeCellList_[chain].add(top, meta.topLevel());
+      ChainState* st = &h->chainStates_.at(chain);
+      PhysicalCell* top = buildPhysicalCell(cs, meta, st, meta.topLevel(), "", "");
+      st->free.add(top, meta.topLevel());
+    }
+    {
+      int index = 0;
+      for (auto& [chain, st] : h->chainStates_) {
+        (void)chain;
+        st.index = index++;
+      }
     }
     for (auto& [chain, meta] : chainMeta) {
-      if (!h->fullCellList_.count(chain)) continue;
-      h->cellChains_[meta.types.back()].push_back(chain);
+      auto stIt = h->chainStates_.find(chain);
+      if (stIt == h->chainStates_.end()) continue;
+      h->cellChains_[meta.types.back()].push_back(&stIt->second);
       int leafNum = 1;
       for (int l = 1; l <= meta.topLevel(); l++) {
         h->leafCellNums_[chain][l] = leafNum;
@@ -197,6 +229,7 @@ struct BuildContext {
     // --- virtual clusters ---
     for (const auto& [vcName, vcSpec] : spec.virtualClusters) {
       IntraVCScheduler& vcs = h->vcSchedulers_[vcName];
+      vcs.byChain.assign(h->chainStates_.size(), nullptr);
       int cellCounter = 0;
       for (const auto& vcell : vcSpec.virtualCells) {
         // resolve hierarchical type path "CHAIN.CHILD..." -> (chain, level)
@@ -214,7 +247,7 @@ struct BuildContext {
         }
         const std::string& chain = parts[0];
         auto metaIt = chainMeta.find(chain);
-        if (metaIt == chainMeta.end() || !h->fullCellList_.count(chain)) {
+        if (metaIt == chainMeta.end() || !h->chainStates_.count(chain)) {
           throw HivedError::BadRequest("VC " + vcName + " virtual cell type " + path +
                                        ": chain " + chain + " does not exist in physical cluster");
         }
@@ -230,13 +263,15 @@ struct BuildContext {
           vcs.nonPinnedFull[chain].init(meta.topLevel());
           vcs.nonPinnedPreassigned[chain].init(meta.topLevel());
         }
+        VCChainState* vcc = vcChainState(vcName, &h->chainStates_.at(chain));
+        vcc->preassigned = &vcs.nonPinnedPreassigned[chain];
         for (int i = 0; i < vcell.number; i++) {
           std::string addr = vcName + "/" + chain + "/" + std::to_string(cellCounter++);
-          VirtualCell* pre = buildVirtualCell(vcName, chain, meta, level, nullptr, addr, "",
-                                              vcs.nonPinnedFull[chain]);
+          VirtualCell* pre =
+              buildVirtualCell(vcc, meta, level, nullptr, addr, "", vcs.nonPinnedFull[chain]);
           vcs.nonPinnedPreassigned[chain].add(pre, level);
         }
-        h->vcFreeCellNum_[vcName][chain][level] += vcell.number;
+        vcc->free[level] += vcell.number;
       }
       // pinned cells: statically bound, scheduled by their own scheduler
       for (const auto& pinnedId : vcSpec.pinnedIds) {
@@ -255,21 +290,23 @@ struct BuildContext {
         ChainCellList& pinnedList = vcs.pinned[pinnedId];
         pinnedList.init(pc->level);
         std::string addr = vcName + "/" + pinnedId;
-        buildVirtualCell(vcName, pc->chain, meta, pc->level, nullptr, addr, pinnedId, pinnedList);
+        VCChainState* vcc = vcChainState(vcName, pc->cs);
+        buildVirtualCell(vcc, meta, pc->level, nullptr, addr, pinnedId, pinnedList);
         h->pinnedPhysical_[vcName][pinnedId] = pc;
-        h->vcFreeCellNum_[vcName][pc->chain][pc->level] += 1;
+        vcc->free[pc->level] += 1;
       }
       for (auto& [chain, ccl] : vcs.nonPinnedFull) {
-        vcs.nonPinnedSchedulers.emplace(chain,
-                                        TopoScheduler(ccl, h->leafCellNums_[chain], true));
+        auto entered = vcs.nonPinnedSchedulers.emplace(
+            chain, TopoScheduler(ccl, h->leafCellNums_[chain], true));
+        vcs.byChain[h->chainStates_.at(chain).index]->topo = &entered.first->second;
       }
       for (auto& [pid, ccl] : vcs.pinned) {
         const std::string& chain = ccl.at(kLowestLevel)[0]->chain;
         vcs.pinnedSchedulers.emplace(pid, TopoScheduler(ccl, h->leafCellNums_[chain], true));
       }
     }
-    for (auto& [chain, ccl] : h->fullCellList_) {
-      h->opportunisticSchedulers_.emplace(chain, TopoScheduler(ccl, h->leafCellNums_[chain], false));
+    for (auto& [chain, st] : h->chainStates_) {
+      st.opportunistic = TopoScheduler(st.full, h->leafCellNums_[chain], false);
     }
   }
 };
@@ -289,41 +326,34 @@ void HivedCore::buildFromSpec(const ClusterSpec& spec) {
 // Validates VC quota against the physical cluster and initializes the
 // accounting maps (parity: hived_algorithm.go:369-409).
 void HivedCore::initCellNums() {
-  // Every physical chain gets accounting structures, even with no VC quota.
-  for (auto& [chain, ccl] : fullCellList_) {
-    int top = ccl.top();
-    badFreeCells_[chain].init(top);
-    totalLeftCellNum_[chain][top] = static_cast<int>(ccl.at(top).size());
-    for (int l = top; l >= kLowestLevel; l--) {
-      allVCDoomedBadCellNum_[chain][l] = 0;
-      allVCFreeCellNum_[chain][l] += 0;
-      if (l > kLowestLevel) {
-        int childNum = static_cast<int>(ccl.at(l)[0]->children.size());
-        totalLeftCellNum_[chain][l - 1] = totalLeftCellNum_[chain][l] * childNum;
-      }
+  // Every physical chain has its accounting, even with no VC quota.
+  for (auto& [chain, st] : chainStates_) {
+    (void)chain;
+    const ChainCellList& ccl = st.full;
+    int top = st.top;
+    st.totalLeft[top] = static_cast<int>(ccl.at(top).size());
+    for (int l = top; l > kLowestLevel; l--) {
+      int childNum = static_cast<int>(ccl.at(l)[0]->children.size());
+      st.totalLeft[l - 1] = st.totalLeft[l] * childNum;
     }
   }
-  for (auto& [vc, perChain] : vcFreeCellNum_) {
-    vcDoomedBadCells_[vc] = {};
-    for (auto& [chain, perLevel] : perChain) {
-      if (!fullCellList_.count(chain)) {
-        throw HivedError::BadRequest("Illegal initial VC assignment: chain " + chain +
-                                     " does not exist in physical cluster");
-      }
-      vcDoomedBadCells_[vc][chain].init(fullCellList_[chain].top());
-      for (auto& [level, num] : perLevel) {
-        allVCFreeCellNum_[chain][level] += num;
-      }
-    }
+  // a chain's VCs in VC-name order: the order the doom checks visit them in
+  for (auto& [vc, perChain] : vcChainStates_) {
     (void)vc;
+    for (auto& [chain, vcc] : perChain) {
+      (void)chain;
+      ChainState* st = vcc.chain;
+      st->vcs.push_back(&vcc);
+      for (int l = kLowestLevel; l <= st->top; l++) st->allVCFree[l] += vcc.free[l];
+    }
   }
   // Validate: the VCs' free cells fit into the physical cluster at every level.
-  for (auto& [chain, chainFreeCellNum] : allVCFreeCellNum_) {
-    ChainCellList& ccl = fullCellList_.at(chain);
-    int top = ccl.top();
+  for (auto& [chain, st] : chainStates_) {
+    const ChainCellList& ccl = st.full;
+    int top = st.top;
     int available = static_cast<int>(ccl.at(top).size());
     for (int l = top; l >= kLowestLevel; l--) {
-      int need = chainFreeCellNum.count(l) ? chainFreeCellNum[l] : 0;
+      int need = st.allVCFree[l];
       int left = available - need;
       if (left < 0) {
         throw HivedError::BadRequest(
@@ -343,7 +373,7 @@ void HivedCore::initCellNums() {
 void HivedCore::initPinnedCells() {
   for (auto& [vcName, perId] : pinnedPhysical_) {
     for (auto& [pid, pc] : perId) {
-      allocatePreassignedCell(pc, vcName, false);
+      allocatePreassignedCell(pc, &vcChainStates_.at(vcName).at(pc->chain), false);
       ChainCellList& vlist = vcSchedulers_[vcName].pinned[pid];
       auto* pinnedVirtual = static_cast<VirtualCell*>(vlist.at(vlist.top())[0]);
       bindCell(pc, pinnedVirtual);
@@ -375,14 +405,16 @@ std::vector<std::string> HivedCore::allNodes() const {
 
 std::vector<std::string> HivedCore::chains() const {
   std::vector<std::string> out;
-  for (auto& [chain, ccl] : fullCellList_) out.push_back(chain);
+  for (auto& [chain, st] : chainStates_) out.push_back(chain);
   return out;
 }
 
 std::map<int, std::string> HivedCore::chainLevelTypes(const std::string& chain) const {
-  auto it = cellTypes_.find(chain);
-  if (it == cellTypes_.end()) return {};
-  return it->second;
+  std::map<int, std::string> out;
+  auto it = chainStates_.find(chain);
+  if (it == chainStates_.end()) return out;
+  for (int l = kLowestLevel; l <= it->second.top; l++) out[l] = it->second.levelType[l];
+  return out;
 }
 
 }  // namespace hived

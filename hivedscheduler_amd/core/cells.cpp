@@ -188,12 +188,12 @@ void setCellState(PhysicalCell* c, CState s) {
   }
 }
 
-static PhysicalCell* findPhysicalLeafCellInChain(std::map<std::string, ChainCellList>& fullCellList,
+static PhysicalCell* findPhysicalLeafCellInChain(const std::map<std::string, ChainState>& chains,
                                                  const std::string& chain, const std::string& node,
                                                  int leafIndex) {
-  auto it = fullCellList.find(chain);
-  if (it == fullCellList.end()) return nullptr;
-  for (Cell* c : it->second.at(kLowestLevel)) {
+  auto it = chains.find(chain);
+  if (it == chains.end()) return nullptr;
+  for (Cell* c : it->second.full.at(kLowestLevel)) {
     auto* pc = static_cast<PhysicalCell*>(c);
     if (!pc->nodes.empty() && pc->nodes[0] == node && !pc->leafIndices.empty() &&
         pc->leafIndices[0] == leafIndex) {
@@ -203,14 +203,14 @@ static PhysicalCell* findPhysicalLeafCellInChain(std::map<std::string, ChainCell
   return nullptr;
 }
 
-PhysicalCell* findPhysicalLeafCell(std::map<std::string, ChainCellList>& fullCellList,
+PhysicalCell* findPhysicalLeafCell(const std::map<std::string, ChainState>& chains,
                                    const std::string& chain, const std::string& node,
                                    int leafIndex) {
-  if (PhysicalCell* c = findPhysicalLeafCellInChain(fullCellList, chain, node, leafIndex)) return c;
-  for (auto& [other, ccl] : fullCellList) {
-    (void)ccl;
+  if (PhysicalCell* c = findPhysicalLeafCellInChain(chains, chain, node, leafIndex)) return c;
+  for (auto& [other, st] : chains) {
+    (void)st;
     if (other == chain) continue;
-    if (PhysicalCell* c = findPhysicalLeafCellInChain(fullCellList, other, node, leafIndex)) return c;
+    if (PhysicalCell* c = findPhysicalLeafCellInChain(chains, other, node, leafIndex)) return c;
   }
   return nullptr;
 }

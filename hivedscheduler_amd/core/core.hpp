@@ -194,6 +194,47 @@ class SmallBuf {
   size_t n_;
 };
 
+// A list of a trivially copyable T that grows by push_back: the first N values
+// live inside the object, all of them on the heap once it outgrows N. For the
+// mapper's candidate lists, which hold a handful of cells and are built anew
+// at every level of its recursion (one list per depth, each on its own frame).
+template <class T, size_t N = 16>
+class SmallVec {
+ public:
+  SmallVec() {}
+  SmallVec(const SmallVec&) = delete;
+  SmallVec& operator=(const SmallVec&) = delete;
+  size_t size() const { return n_; }
+  bool empty() const { return n_ == 0; }
+  T* begin() { return p_; }
+  T* end() { return p_ + n_; }
+  const T* begin() const { return p_; }
+  const T* end() const { return p_ + n_; }
+  T& operator[](size_t i) { return p_[i]; }
+  const T& operator[](size_t i) const { return p_[i]; }
+  T& back() { return p_[n_ - 1]; }
+  void clear() { n_ = 0; }
+  void pop_back() { n_--; }
+  void push_back(const T& v) {
+    if (n_ == cap_) grow();
+    p_[n_++] = v;
+  }
+
+ private:
+  void grow() {
+    std::vector<T> bigger(2 * cap_);
+    std::copy(p_, p_ + n_, bigger.begin());
+    heap_.swap(bigger);
+    p_ = heap_.data();
+    cap_ = heap_.size();
+  }
+  T inl_[N];
+  std::vector<T> heap_;
+  T* p_ = inl_;
+  size_t n_ = 0;
+  size_t cap_ = N;
+};
+
 // Stable sort without std::stable_sort's heap-allocated merge buffer while
 // the range is short (an insertion sort, which is stable too, so both give
 // the same order).
@@ -499,9 +540,12 @@ class InlineVec {
 struct Group;
 struct PhysicalCell;
 struct VirtualCell;
+struct ChainState;
+struct VCChainState;
 
 struct Cell {
   std::string chain;        // top-level cell type name identifying the chain
+  ChainState* cs = nullptr; // that chain's record (see ChainState)
   int level = 0;            // 1 = leaf
   int totalLeaf = 0;        // number of leaf cells contained
   std::string address;      // unique address
@@ -522,8 +566,10 @@ struct Cell {
   // 100% of flat samples before this cache).
   int freeLeavesUnder = 0;
 
+  explicit Cell(bool physical_) : physical(physical_) {}
   virtual ~Cell() = default;
-  virtual bool isPhysical() const = 0;
+  const bool physical;  // a PhysicalCell, else a VirtualCell
+  bool isPhysical() const { return physical; }
   int usedAt(int p) const {
     auto it = usedLeafAtPriority.find(p);
     return it == usedLeafAtPriority.end() ? 0 : it->second;
@@ -554,7 +600,7 @@ struct PhysicalCell : Cell {
   int badLinksUnder = 0;
   // leaf cells only: peer leaves connected by a currently-degraded link
   std::vector<PhysicalCell*> badLinkPeers;
-  bool isPhysical() const override { return true; }
+  PhysicalCell() : Cell(true) {}
 };
 
 // One xGMI link's measured state (node-local, endpoints are GPU indices).
@@ -570,7 +616,9 @@ struct VirtualCell : Cell {
   VirtualCell* preassigned = nullptr;  // root ancestor in the VC forest
   PhysicalCell* phys = nullptr;        // bound physical cell
   std::string pinnedId;                // non-empty if in a pinned pool
-  bool isPhysical() const override { return false; }
+  // the record of this cell's VC on this cell's chain (see VCChainState)
+  VCChainState* vcChain = nullptr;
+  VirtualCell() : Cell(false) {}
 };
 
 // Level-indexed cell lists for one chain (index 1..top).
@@ -767,8 +815,8 @@ struct SchedulingRequest {
   const std::string& pinnedCellId;
   const std::string& groupName;
   const FlatLeafMap<int>& podLeafCellNums;
-  // the chain being tried (a key of cellChains_' lists or a cell's own chain)
-  const std::string* chain = nullptr;
+  // the chain being tried
+  ChainState* chain = nullptr;
   // the VC's scheduler, resolved once per request, and the placement engine
   // of the chain (or pinned cell) being tried, resolved once per chain: the
   // attempts themselves look nothing up by name
@@ -868,9 +916,60 @@ class TopoScheduler {
 };
 
 // ---------------------------------------------------------------------------
+// Chain state
+// ---------------------------------------------------------------------------
+// Clean-shape worlds of one (chain, tier), validated against
+// gWorldEpochCounter (bumped by every mutation that can change a world: leaf
+// priorities, bindings, health, links). Wait-storms — the common case under
+// contention: many failed filters with no allocation in between — reuse cached
+// worlds instead of recomputing them per Schedule.
+struct WorldCacheEntry {
+  unsigned long long epoch = 0;
+  std::vector<CleanShapeWorld> worlds;
+};
+
+// Everything the core keeps per chain, in one record that every cell of the
+// chain points to (Cell::cs): the hot path reaches it from the cell in hand
+// and looks nothing up by the chain's name. Built once by the cluster-spec
+// compiler; HivedCore::chainStates_ owns the records and is the name-ordered
+// index the cold paths (status, debug, health setters) iterate. The per-level
+// vectors are indexed by level, 1..top; [0] is unused.
+struct ChainState {
+  std::string name;
+  int index = 0;  // dense, in name order (IntraVCScheduler::byChain)
+  int top = 0;
+  ChainCellList full;     // every physical cell
+  ChainCellList free;     // the buddy free list
+  ChainCellList badFree;  // bad cells that are free (directly or via an unsplit ancestor)
+  std::vector<std::string> levelType;  // cell type name
+  std::vector<int> totalLeft;          // cells the free list can still produce
+  std::vector<int> allVCFree;          // free preassigned cells, all VCs together
+  std::vector<int> allVCDoomedBadCellNum;
+  // the VCs with quota (or a pinned cell) in this chain, in VC-name order
+  std::vector<VCChainState*> vcs;
+  TopoScheduler opportunistic;  // placement engine over the physical cells
+  std::map<int, WorldCacheEntry> worldCache;  // by tier
+};
+
+// One VC's share of one chain. Reached from the VC's scheduler
+// (IntraVCScheduler::byChain) and from every virtual cell (VirtualCell::vcChain).
+struct VCChainState {
+  std::string vc;
+  ChainState* chain = nullptr;
+  std::vector<int> free;  // free preassigned cells by level
+  ChainCellList doomed;   // bad physical cells bound to this VC's free cells
+  // the VC's preassigned cells and its placement engine on this chain; null
+  // where the VC has only a pinned cell there
+  const ChainCellList* preassigned = nullptr;
+  const TopoScheduler* topo = nullptr;
+};
+
+// ---------------------------------------------------------------------------
 // Intra-VC scheduler
 // ---------------------------------------------------------------------------
 struct IntraVCScheduler {
+  // by ChainState::index; null for a chain this VC has nothing in
+  std::vector<VCChainState*> byChain;
   std::map<std::string, ChainCellList> nonPinnedFull;         // chain -> all virtual cells
   std::map<std::string, ChainCellList> nonPinnedPreassigned;  // chain -> preassigned cells
   std::map<std::string, ChainCellList> pinned;                // pinnedId -> subtree cells
@@ -928,8 +1027,11 @@ class VictimList {
       if (at == index) break;
     }
     *node = *pods_[i].first;
+    size_t last = i;
+    while (last < pods_.size() && *pods_[last].first == *node) last++;
     keys->clear();
-    for (; i < pods_.size() && *pods_[i].first == *node; i++) keys->push_back(*pods_[i].second);
+    keys->reserve(last - i);  // one allocation, whatever the number of keys
+    for (; i < last; i++) keys->push_back(*pods_[i].second);
   }
 
  private:
@@ -983,8 +1085,6 @@ class HivedCore {
 
   // -- inspect --
   const std::map<std::string, std::unique_ptr<Group>>& groups() const { return groups_; }
-  const std::map<std::string, ChainCellList>& fullCellList() const { return fullCellList_; }
-  const std::map<std::string, ChainCellList>& freeCellList() const { return freeCellList_; }
   const std::map<std::string, IntraVCScheduler>& vcSchedulers() const { return vcSchedulers_; }
   std::vector<std::string> chains() const;
   std::map<int, std::string> chainLevelTypes(const std::string& chain) const;
@@ -1010,10 +1110,10 @@ class HivedCore {
   // and can consume cells an in-flight placement depends on (fuzz-found
   // corruption). tryBind/tryUnbind queue when an operation is active; the
   // bodies run from drainDoomChecks() once state is consistent.
-  void tryBindDoomedBadCell(const std::string& chain, int level);
-  void tryUnbindDoomedBadCell(const std::string& chain, int level);
-  void doBindDoomedBadCell(const std::string& chain, int level);
-  void doUnbindDoomedBadCell(const std::string& chain, int level);
+  void tryBindDoomedBadCell(ChainState* chain, int level);
+  void tryUnbindDoomedBadCell(ChainState* chain, int level);
+  void doBindDoomedBadCell(ChainState* chain, int level);
+  void doUnbindDoomedBadCell(ChainState* chain, int level);
   void drainDoomChecks();
 
   class OpGuard {
@@ -1049,18 +1149,18 @@ class HivedCore {
                                     bool* hasVirtual, Placement<VirtualCell>* virt,
                                     VictimList* victims,
                                     int* podIndex);
-  void schedulePodFromNewGroup(const PodSpec& s, const std::set<std::string>& suggestedNodes,
-                               Phase phase, const std::string& podKey,
-                               Placement<PhysicalCell>* phys, bool* hasVirtual,
-                               Placement<VirtualCell>* virt,
-                               VictimList* victims,
-                               std::string* waitReason);
+  Group* schedulePodFromNewGroup(const PodSpec& s, const std::set<std::string>& suggestedNodes,
+                                 Phase phase, const std::string& podKey,
+                                 Placement<PhysicalCell>* phys, bool* hasVirtual,
+                                 Placement<VirtualCell>* virt,
+                                 VictimList* victims,
+                                 std::string* waitReason);
   bool scheduleNewAffinityGroup(const PodSpec& s, const std::set<std::string>& suggestedNodes,
                                 const std::string& podKey, Placement<PhysicalCell>* phys,
                                 bool* hasVirtual, Placement<VirtualCell>* virt,
                                 std::string* failedReason);
   bool scheduleForLeafCellType(SchedulingRequest& sr, const std::string& leafCellType,
-                               const std::vector<std::string>& chains,
+                               const std::vector<ChainState*>& chains,
                                const std::string& podKey, bool typeSpecified,
                                Placement<PhysicalCell>* phys, bool* hasVirtual,
                                Placement<VirtualCell>* virt, std::string* failedReason);
@@ -1090,8 +1190,8 @@ class HivedCore {
   // --- group lifecycle ---
   Group* createAllocatedGroup(const PodSpec& s, const BindInfo& info, const std::string& podKey);
   void deleteAllocatedGroup(Group* g, const std::string& podKey);
-  void createPreemptingGroup(const PodSpec& s, const Placement<PhysicalCell>& phys,
-                             const Placement<VirtualCell>& virt, const std::string& podKey);
+  Group* createPreemptingGroup(const PodSpec& s, const Placement<PhysicalCell>& phys,
+                               const Placement<VirtualCell>& virt, const std::string& podKey);
   void deletePreemptingGroup(Group* g, const std::string& podKey);
   void allocatePreemptingGroup(Group* g, const std::string& podKey);
   Placement<VirtualCell> lazyPreemptGroup(Group* victim, const std::string& preemptor);
@@ -1101,13 +1201,14 @@ class HivedCore {
   // --- leaf-cell allocate/release + safety accounting ---
   std::pair<PhysicalCell*, VirtualCell*> findAllocatedLeafCell(
       int index, const PodPlacementInfo& placement, const std::string& chain, const PodSpec& s,
-      Group* group, const std::string& podKey, bool* lazyPreempt, bool* isOpportunistic);
+      const IntraVCScheduler* vcs, const std::vector<PhysicalCell*>* nodeLeaves, Group* group,
+      const std::string& podKey, bool* lazyPreempt, bool* isOpportunistic);
   std::pair<bool, std::string> allocateLeafCell(PhysicalCell* p, VirtualCell* v, int priority,
                                                 const std::string& vc);
   void releaseLeafCell(PhysicalCell* p, const std::string& vc);
-  std::pair<bool, std::string> allocatePreassignedCell(PhysicalCell* c, const std::string& vc,
+  std::pair<bool, std::string> allocatePreassignedCell(PhysicalCell* c, VCChainState* vc,
                                                        bool doomedBad);
-  void releasePreassignedCell(PhysicalCell* c, const std::string& vc, bool doomedBad);
+  void releasePreassignedCell(PhysicalCell* c, VCChainState* vc, bool doomedBad);
   void allocateBadCell(PhysicalCell* c);
   void releaseBadCell(PhysicalCell* c);
   int removeCellFromFreeList(PhysicalCell* c);
@@ -1115,12 +1216,12 @@ class HivedCore {
 
   // --- mapping virtual -> physical (buddy allocation) ---
   // freeList / freeCellNum: the caller's working copies of the chain's free
-  // list and allVCFreeCellNum_ entry; both are consumed. Of nonPreassigned the
+  // list and allVCFree counts; both are consumed. Of nonPreassigned the
   // first nonPreassignedCount groups count.
   bool mapVirtualPlacementToPhysical(const std::vector<BindingVertex*>& preassigned,
                                      const std::vector<std::vector<BindingVertex*>>& nonPreassigned,
                                      size_t nonPreassignedCount, ChainCellList& freeList,
-                                     std::map<int, int>& freeCellNum,
+                                     std::vector<int>& freeCellNum,
                                      const std::set<std::string>& suggestedNodes,
                                      bool ignoreSuggestedNodes, CellBindings& bindings,
                                      long long minHbmBytes = 0, bool honorLinks = false,
@@ -1138,7 +1239,7 @@ class HivedCore {
     size_t nonPreassignedUsed = 0;
     std::vector<VirtualCell*> path;
     ChainCellList freeList;
-    std::map<int, int> freeCellNum;
+    std::vector<int> freeCellNum;  // by level
     void reset() {
       verticesUsed = 0;
       preassigned.clear();
@@ -1176,12 +1277,16 @@ class HivedCore {
 
  public:
   // state (public for inspect/bindings simplicity; external mutation forbidden)
-  std::map<std::string, ChainCellList> fullCellList_;
-  std::map<std::string, ChainCellList> freeCellList_;
+  // chain name -> the chain's record; std::map nodes never move, so the
+  // pointers the cells hold stay good. Iterated (in name order) by the cold
+  // paths only.
+  std::map<std::string, ChainState> chainStates_;
+  // vc -> chain -> that VC's record on that chain, for the VCs with quota or
+  // a pinned cell there
+  std::map<std::string, std::map<std::string, VCChainState>> vcChainStates_;
   bool inOperation_ = false;
-  std::vector<std::pair<std::string, int>> pendingDoomChecks_;
+  std::vector<std::pair<ChainState*, int>> pendingDoomChecks_;  // (chain, level), FIFO
   std::map<std::string, IntraVCScheduler> vcSchedulers_;
-  std::map<std::string, TopoScheduler> opportunisticSchedulers_;
   std::map<std::string, std::unique_ptr<Group>> groups_;
   // pod key -> the allocatedPods slot that holds it. Kept by setPodSlot /
   // clearPodSlot / eraseGroup, the only writers of a slot's `present`, so it
@@ -1197,22 +1302,13 @@ class HivedCore {
   };
   std::unordered_map<std::string, PodSlotRef> podIndex_;
 
-  // vc -> chain -> level -> free preassigned cell count
-  std::map<std::string, std::map<std::string, std::map<int, int>>> vcFreeCellNum_;
-  std::map<std::string, std::map<int, int>> allVCFreeCellNum_;
-  std::map<std::string, std::map<int, int>> totalLeftCellNum_;
-
-  std::map<std::string, ChainCellList> badFreeCells_;
-  std::map<std::string, std::map<std::string, ChainCellList>> vcDoomedBadCells_;
-  std::map<std::string, std::map<int, int>> allVCDoomedBadCellNum_;
-
   std::set<std::string> badNodes_;
   // leaves individually marked bad (GPU/xGMI level), independent of node health
   std::set<PhysicalCell*> badLeafMarks_;
   // node -> (minIdx, maxIdx) -> link record (first-class xGMI link state)
   std::map<std::string, std::map<std::pair<int, int>, XgmiLink>> xgmiLinks_;
-  std::map<std::string, std::vector<std::string>> cellChains_;        // leaf type -> chains
-  std::map<std::string, std::map<int, std::string>> cellTypes_;      // chain -> level -> type
+  // leaf type -> chains, in chain-name order
+  std::map<std::string, std::vector<ChainState*>> cellChains_;
   std::map<std::string, std::map<int, int>> leafCellNums_;           // chain -> level -> leaf num
   // pinned: vc -> pinnedId -> physical cell
   std::map<std::string, std::map<std::string, PhysicalCell*>> pinnedPhysical_;
@@ -1225,16 +1321,6 @@ class HivedCore {
   // node name -> leaf cells on that node (for health propagation)
   std::map<std::string, std::vector<PhysicalCell*>> nodeLeafCellsStorage_;
   long long scheduleCount_ = 0;
-  // Clean-shape-world cache, validated against gWorldEpochCounter (bumped
-  // by every mutation that can change a world: leaf priorities, bindings,
-  // health, links). Wait-storms — the common case under contention: many
-  // failed filters with no allocation in between — reuse cached worlds
-  // instead of recomputing them per Schedule.
-  struct WorldCacheEntry {
-    unsigned long long epoch = 0;
-    std::vector<CleanShapeWorld> worlds;
-  };
-  std::map<std::pair<std::string, int>, WorldCacheEntry> worldCache_;
 };
 
 // helpers shared across translation units
@@ -1249,7 +1335,7 @@ VirtualCell* mapPhysicalCellToVirtual(PhysicalCell* c, const ChainCellList& vccl
                                       int preassignedLevel, int p, std::string* message);
 bool inFreeCellList(PhysicalCell* c);
 void setCellState(PhysicalCell* c, CState s);
-PhysicalCell* findPhysicalLeafCell(std::map<std::string, ChainCellList>& fullCellList,
+PhysicalCell* findPhysicalLeafCell(const std::map<std::string, ChainState>& chains,
                                    const std::string& chain, const std::string& node,
                                    int leafIndex);
 Cell* ancestorNoHigherThanNode(Cell* c);

@@ -36,10 +36,12 @@ int countFreeListSubtree(const ChainCellList& freeList, int level) {
 
 void checkInvariants(const HivedCore& core) {
   // ---- per-cell roll-ups over every physical chain ----
-  for (auto& [chain, ccl] : core.fullCellList_) {
+  for (auto& [chain, st] : core.chainStates_) {
+    const ChainCellList& ccl = st.full;
     for (int l = ccl.top(); l >= kLowestLevel; l--) {
       for (Cell* cc : ccl.at(l)) {
         auto* c = static_cast<PhysicalCell*>(cc);
+        if (c->cs != &st) fail("cell " + c->address + " does not point to its chain " + chain);
         if (!c->children.empty()) {
           int maxPrio = kFreePriority;
           bool allHealthy = true;
@@ -107,8 +109,9 @@ void checkInvariants(const HivedCore& core) {
         for (Cell* c = x; c != nullptr; c = c->parent) expect[c]++;
       }
     }
-    for (auto& [chain, ccl] : core.fullCellList_) {
+    for (auto& [chain, st] : core.chainStates_) {
       (void)chain;
+      const ChainCellList& ccl = st.full;
       for (int l = ccl.top(); l >= kLowestLevel; l--) {
         for (Cell* cc : ccl.at(l)) {
           auto* c = static_cast<PhysicalCell*>(cc);
@@ -122,7 +125,8 @@ void checkInvariants(const HivedCore& core) {
     }
   }
   // ---- free list consistency + accounting ----
-  for (auto& [chain, freeList] : core.freeCellList_) {
+  for (auto& [chain, st] : core.chainStates_) {
+    const ChainCellList& freeList = st.free;
     for (int l = freeList.top(); l >= kLowestLevel; l--) {
       for (Cell* cc : freeList.at(l)) {
         auto* c = static_cast<PhysicalCell*>(cc);
@@ -140,26 +144,22 @@ void checkInvariants(const HivedCore& core) {
       }
     }
     // totalLeftCellNum matches what the free list can actually produce
-    auto tlIt = core.totalLeftCellNum_.find(chain);
-    if (tlIt != core.totalLeftCellNum_.end()) {
-      for (auto& [level, left] : tlIt->second) {
-        int actual = countFreeListSubtree(freeList, level);
-        if (actual != left) {
-          std::ostringstream os;
-          os << "totalLeftCellNum mismatch at chain " << chain << " level " << level
-             << ": accounted " << left << ", free list yields " << actual;
-          fail(os.str());
-        }
+    for (int level = kLowestLevel; level <= st.top; level++) {
+      int left = st.totalLeft[level];
+      int actual = countFreeListSubtree(freeList, level);
+      if (actual != left) {
+        std::ostringstream os;
+        os << "totalLeftCellNum mismatch at chain " << chain << " level " << level
+           << ": accounted " << left << ", free list yields " << actual;
+        fail(os.str());
       }
     }
   }
   // ---- VC safety: totalLeft >= allVCFree at every level ----
-  for (auto& [chain, perLevel] : core.allVCFreeCellNum_) {
-    auto tlIt = core.totalLeftCellNum_.find(chain);
-    if (tlIt == core.totalLeftCellNum_.end()) continue;
-    for (auto& [level, vcFree] : perLevel) {
-      auto it = tlIt->second.find(level);
-      int left = it == tlIt->second.end() ? 0 : it->second;
+  for (auto& [chain, st] : core.chainStates_) {
+    for (int level = kLowestLevel; level <= st.top; level++) {
+      int vcFree = st.allVCFree[level];
+      int left = st.totalLeft[level];
       if (left < vcFree) {
         std::ostringstream os;
         os << "VC safety broken at chain " << chain << " level " << level << ": " << left
@@ -169,24 +169,25 @@ void checkInvariants(const HivedCore& core) {
     }
   }
   // ---- allVCFreeCellNum == sum of vcFreeCellNum ----
-  std::map<std::string, std::map<int, int>> sum;
-  for (auto& [vc, perChain] : core.vcFreeCellNum_) {
-    (void)vc;
-    for (auto& [chain, perLevel] : perChain) {
-      for (auto& [level, n] : perLevel) sum[chain][level] += n;
-    }
-  }
-  for (auto& [chain, perLevel] : core.allVCFreeCellNum_) {
-    for (auto& [level, n] : perLevel) {
-      int s = sum.count(chain) && sum[chain].count(level) ? sum[chain][level] : 0;
-      if (s != n) {
+  for (auto& [chain, st] : core.chainStates_) {
+    for (int level = kLowestLevel; level <= st.top; level++) {
+      int s = 0;
+      for (const VCChainState* vcc : st.vcs) s += vcc->free[level];
+      if (s != st.allVCFree[level]) {
         fail("allVCFreeCellNum mismatch at " + chain + " level " + std::to_string(level));
+      }
+      // the doom checks trust this count to tell that no VC has a doomed cell
+      size_t doomed = 0;
+      for (const VCChainState* vcc : st.vcs) doomed += vcc->doomed.at(level).size();
+      if (static_cast<int>(doomed) != st.allVCDoomedBadCellNum[level]) {
+        fail("allVCDoomedBadCellNum mismatch at " + chain + " level " + std::to_string(level));
       }
     }
   }
   // ---- doomed-bad cells: every entry is bound symmetrically ----
-  for (auto& [vcName, perChain] : core.vcDoomedBadCells_) {
-    for (auto& [chain, ccl] : perChain) {
+  for (auto& [vcName, perChain] : core.vcChainStates_) {
+    for (auto& [chain, vcc] : perChain) {
+      const ChainCellList& ccl = vcc.doomed;
       for (int l = 1; l <= ccl.top(); l++) {
         for (Cell* cc : ccl.at(l)) {
           auto* pc = static_cast<PhysicalCell*>(cc);

@@ -1,6 +1,6 @@
 // Stand-alone check of the leaf-count containers of core.hpp: FlatLeafMap
 // against std::map<int, V> over random operations, PodCells against a vector
-// of vectors, InlineVec against std::vector. No core object is linked.
+// of vectors, InlineVec and SmallVec against std::vector. No core object is linked.
 // Compile and run (from hivedscheduler_amd/), on the CPU, with the sanitizers:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined
 //       -o flatcontainerstest core/flat_containers_test_main.cpp && ./flatcontainerstest
@@ -258,6 +258,34 @@ void inlineVec() {
   }
 }
 
+// SmallVec against std::vector: pushes across the inline capacity and two
+// doublings beyond it, pops, clears (the heap block is kept and reused)
+void smallVec() {
+  std::mt19937 rng(5);
+  SmallVec<int*, 4> vec;
+  std::vector<int*> ref;
+  int cells[64];
+  for (int op = 0; op < 3000; op++) {
+    const unsigned what = rng() % 16;
+    if (what == 0) {
+      vec.clear();
+      ref.clear();
+    } else if (what < 5 && !ref.empty()) {
+      CHECK(vec.back() == ref.back());
+      vec.pop_back();
+      ref.pop_back();
+    } else if (ref.size() < 20) {
+      vec.push_back(&cells[op % 64]);
+      ref.push_back(&cells[op % 64]);
+    }
+    CHECK(vec.size() == ref.size() && vec.empty() == ref.empty());
+    CHECK(static_cast<size_t>(vec.end() - vec.begin()) == ref.size());
+    size_t i = 0;
+    for (int* c : vec) CHECK(c == ref[i++]);
+    for (size_t j = 0; j < ref.size(); j++) CHECK(vec[j] == ref[j]);
+  }
+}
+
 }  // namespace
 
 int main() {
@@ -269,6 +297,7 @@ int main() {
   capacityEdges<Owner>([](int v) { return Owner(v); });
   podCells();
   inlineVec();
+  smallVec();
   printf("flat containers OK (%ld checks)\n", gChecks);
   return 0;
 }
