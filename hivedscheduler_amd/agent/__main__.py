@@ -52,6 +52,11 @@ def main() -> None:
                          "per-SIMD attribution) every N sweeps (on deep sweeps); 0 = never")
     ap.add_argument("--scalar-probe", action="store_true",
                     help="with --local: also run the scalar probe")
+    ap.add_argument("--atomic-probe-every", type=int, default=0,
+                    help="atomic probe (exact atomic burn per CU, contended ticket / reduce / "
+                         "cmpswap across all XCDs) every N sweeps (on deep sweeps); 0 = never")
+    ap.add_argument("--atomic-probe", action="store_true",
+                    help="with --local: also run the atomic probe")
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
@@ -67,7 +72,8 @@ def main() -> None:
                                      lds_march=args.lds_march, hbm_march=args.hbm_march,
                                      min_xcd_ratio=args.min_xcd_ratio,
                                      simd_probe=args.simd_probe,
-                                     scalar_probe=args.scalar_probe)
+                                     scalar_probe=args.scalar_probe,
+                                     atomic_probe=args.atomic_probe)
         if args.p2p_matrix:
             try:
                 m = p2p_link_matrix()
@@ -90,7 +96,8 @@ def main() -> None:
                             hbm_march_every=args.hbm_march_every,
                             min_xcd_ratio=args.min_xcd_ratio,
                             simd_probe_every=args.simd_probe_every,
-                            scalar_probe_every=args.scalar_probe_every)
+                            scalar_probe_every=args.scalar_probe_every,
+                            atomic_probe_every=args.atomic_probe_every)
     if args.once:
         import json
 

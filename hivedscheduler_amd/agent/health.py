@@ -60,6 +60,7 @@ def collect_node_health(
     min_xcd_ratio: Optional[float] = None,
     simd_probe: bool = False,
     scalar_probe: bool = False,
+    atomic_probe: bool = False,
 ) -> dict:
     """One health sweep over all visible GPUs. deep=True also runs the HIP
     kernels (HBM + MFMA); sweep=True adds the 16 GiB HBM stuck-bit pattern
@@ -104,6 +105,15 @@ def collect_node_health(
     loaded wrong, as xcc, se, sh, cu, simd; a key of its own beside
     `bad_simds`), and a failed probe marks the leaf bad.
 
+    atomic_probe=True (with deep) adds the atomic probe (the exact atomic burn
+    on cells each lane owns and the contended ticket, reduce and cmpswap
+    sections on shared cells): per GPU it records `atomic_probe_ok`,
+    `atomic_burn_ok`, `atomic_contend_ok`, `atomic_bad_cus` (the CUs of any
+    wave whose atomics returned or left a wrong value, as xcc, se, sh, cu; a
+    key of its own beside `bad_cus` and `lds_bad_cus`) and `atomic_bad_cells`
+    (the shared cells that ended wrong, as cell, section, op), and a failed
+    probe marks the leaf bad.
+
     The stuck-bit scan transiently holds up to 16 GiB of HBM; on a GPU
     running tenant jobs this can make the tenant's own allocations fail.
     Keep sweep on the low-frequency cadence and prefer idle GPUs (the
@@ -125,7 +135,8 @@ def collect_node_health(
         from ..ops import gpu_health_report, hbm_slow_xcds
 
         kwargs = _set_flags(burn=burn, lds_march=lds_march, hbm_march=hbm_march,
-                            simd_probe=simd_probe, scalar_probe=scalar_probe)
+                            simd_probe=simd_probe, scalar_probe=scalar_probe,
+                            atomic_probe=atomic_probe)
         for i in range(n):
             gpu = report["gpus"][str(i)]
             try:
@@ -202,6 +213,19 @@ def collect_node_health(
                     )
                     if not p["ok"] or p["bad_simds"]:
                         gpu["healthy"] = False
+                if atomic_probe:
+                    p = rep["atomic_probe"]
+                    gpu.update(
+                        atomic_probe_ok=bool(p["ok"]),
+                        atomic_burn_ok=bool(p["burn"]["ok"]),
+                        atomic_contend_ok=bool(p["contend"]["ok"]),
+                        atomic_bad_cus=[{k: c[k] for k in ("xcc", "se", "sh", "cu")}
+                                        for c in p["bad_cus"]],
+                        atomic_bad_cells=[{k: c[k] for k in ("cell", "section", "op")}
+                                          for c in p["bad_cells"]],
+                    )
+                    if not p["ok"] or p["bad_cus"] or p["bad_cells"]:
+                        gpu["healthy"] = False
             except Exception as e:
                 gpu.update(healthy=False, error=str(e)[:200])
     if probe_pairs and n >= 2:
@@ -276,7 +300,8 @@ class NodeHealthAgent:
                  p2p_matrix_every: int = 30, burn_every: int = 0,
                  min_mfma_tflops: Optional[float] = None, lds_march_every: int = 0,
                  hbm_march_every: int = 0, min_xcd_ratio: Optional[float] = None,
-                 simd_probe_every: int = 0, scalar_probe_every: int = 0):
+                 simd_probe_every: int = 0, scalar_probe_every: int = 0,
+                 atomic_probe_every: int = 0):
         self.scheduler_url = scheduler_url.rstrip("/")
         self.node_name = node_name or socket.gethostname()
         self.interval_s = interval_s
@@ -311,6 +336,11 @@ class NodeHealthAgent:
         # same pattern; 0 = never (tens of milliseconds per GPU, during which
         # it keeps every CU's scalar unit busy)
         self.scalar_probe_every = scalar_probe_every
+        # atomic probe cadence (atomic burn + contended sections), same
+        # pattern; 0 = never (tens of milliseconds per GPU, during which the
+        # contended sections load the L2 and memory-side atomic units of
+        # every XCD)
+        self.atomic_probe_every = atomic_probe_every
         self._rounds = 0
 
     def post_report(self, report: dict) -> bool:
@@ -367,7 +397,8 @@ class NodeHealthAgent:
                             lds_march=deep and self._due(self.lds_march_every),
                             hbm_march=deep and self._due(self.hbm_march_every),
                             simd_probe=deep and self._due(self.simd_probe_every),
-                            scalar_probe=deep and self._due(self.scalar_probe_every))
+                            scalar_probe=deep and self._due(self.scalar_probe_every),
+                            atomic_probe=deep and self._due(self.atomic_probe_every))
         self._rounds += 1
         if "burn" in kwargs:
             kwargs["min_mfma_tflops"] = self.min_mfma_tflops

@@ -5,11 +5,22 @@ extension is REQUIRED: failure to load raises (no silent eager fallback).
 
 Here: the loader, `gpu_health_report` and the single-tile MFMA checks. Each
 opt-in probe has a module of its own (mfma_burn, lds_march, hbm_march,
-simd_probe, scalar_probe) on top of `records`; their public names are re-exported here, and
-their report functions reach the extension through `_ops_on` below.
+simd_probe, scalar_probe, atomic_probe) on top of `records`; their public names
+are re-exported here, and their report functions reach the extension through
+`_ops_on` below.
 """
 from __future__ import annotations
 
+from .atomic_probe import (ATOMIC_CELLS, ATOMIC_FP_OPS, ATOMIC_INT_OPS,  # noqa: F401
+                           ATOMIC_LDS_MAX_CHAIN, ATOMIC_SECTIONS, ATOMIC_STEP_OPS,
+                           CONTEND_CELL_BYTES, CONTEND_SECTIONS, REDUCE_OPS,
+                           REDUCE_OR_CONTRIBUTIONS, REDUCE_PK_CONTRIBUTIONS,
+                           atomic_burn_checksum, atomic_burn_expected, atomic_burn_outcomes,
+                           atomic_burn_report, atomic_cas_cap, atomic_cas_expected,
+                           atomic_contend_report, atomic_fp_exact, atomic_probe_report,
+                           atomic_reduce_contributions, atomic_reduce_expected,
+                           contend_lanes_on_cell, summarize_atomic_burn,
+                           summarize_atomic_contend)
 from .hbm_march import (HBM_MARCH_TILE_BYTES, hbm_march_pattern, hbm_march_report,  # noqa: F401
                         hbm_slow_xcds, summarize_hbm_march)
 from .lds_march import (LDS_MARCH_WORDS, lds_march_block_checksum, lds_march_pattern,  # noqa: F401
@@ -55,7 +66,7 @@ def _ops_on(device: int):
 def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
                       bw_samples: int = 1, burn: bool = False, lds_march: bool = False,
                       hbm_march: bool = False, simd_probe: bool = False,
-                      scalar_probe: bool = False) -> dict:
+                      scalar_probe: bool = False, atomic_probe: bool = False) -> dict:
     """Run the health-probe kernels on one GPU and return measured facts.
 
     Feeds leaf-cell healthiness: HBM bandwidth deficit, MFMA mismatch, or
@@ -95,6 +106,12 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     registers of every wave and the scalar-load check in five widths) as
     report["scalar_probe"] and ANDs its verdict into `healthy`. Off by
     default, and the report is then unchanged.
+
+    atomic_probe=True adds the atomic probe (`atomic_probe_report`: the exact
+    atomic burn per section on cells each lane owns, tens of milliseconds, and
+    the contended ticket, reduce and cmpswap sections on cells every workgroup
+    shares, a few milliseconds) as report["atomic_probe"] and ANDs its verdict
+    into `healthy`. Off by default, and the report is then unchanged.
     """
     import torch
 
@@ -165,6 +182,9 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     if scalar_probe:
         report["scalar_probe"] = scalar_probe_report(device)
         report["healthy"] = bool(report["healthy"] and report["scalar_probe"]["ok"])
+    if atomic_probe:
+        report["atomic_probe"] = atomic_probe_report(device)
+        report["healthy"] = bool(report["healthy"] and report["atomic_probe"]["ok"])
     return report
 
 

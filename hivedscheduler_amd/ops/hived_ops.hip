@@ -23,6 +23,12 @@
 //                across waves; the SIMD, register and bits of any mismatch
 //  - scalar_load_check: a pattern and its complement read through the scalar
 //                data cache in all five load widths, compared on the SALU
+//  - atomic_burn: global and LDS atomics (integer, float, packed, cmpswap) on
+//                cells each lane owns, returning and non-returning, every
+//                returned value and final cell verified bitwise; the CU of any
+//                wave that was wrong
+//  - atomic_contend: tickets, order-independent reductions and a cmpswap loop
+//                from every workgroup on a few shared cells, judged by the host
 //  - hbm_march:  a bounded span of HBM, both bit polarities, 16 B per lane,
 //                values unique across the sweep; the offset, bits and direction
 //                of any mismatch, and a bandwidth per XCD from device clocks
@@ -2697,6 +2703,754 @@ py::dict hbm_march(long max_bytes, long chunk_bytes, long seed, long blocks, lon
   return d;
 }
 
+// ---------------------------------------------------------------------------
+// Atomic probe, part 1: the exact atomic burn (ops.atomic_burn).
+//
+// Every lane owns its cells; cell j of lane l of a wave sits at element
+// j*64 + l of the wave's region, so one wave-instruction touches 256 (4-byte
+// cells) or 512 (8-byte cells) contiguous bytes. Cells are seeded from (seed,
+// section, cell, lane) only: every wave computes the same thing. A step issues
+// the section's fixed sequence of atomics, each operation once returning and
+// once non-returning (result unused: the compiler selects the no-return
+// instruction), with operands hashed from the lane's register mirror of the
+// cell, the step and the operation. Every returned old value is compared with
+// the mirror, which the VALU then advances; after the chain the cells are read
+// back with relaxed atomic loads and compared with `expected`, the host
+// mirror's final values (ops.atomic_burn_expected).
+//
+// Integer cells (sections g32, g64 and the u32 cells of lds), by what survives
+// a wrong value: cell 0 add, sub, xor (bijective in the cell: a difference
+// stays to the end of the round); cell 1 smin, smax, umin, umax; cell 2 and,
+// or, swap; cell 3 inc, dec, cmpswap with the true value (must succeed),
+// cmpswap with a wrong value (must fail and leave the cell alone).
+// Float cells (section gfp and the float cells of lds): add f32, add f64,
+// min / max f64, pk_add f16, pk_add bf16 on integers small enough that every
+// sum is exact (ops.atomic_fp_exact proves it per seed and chain).
+// Section lds runs the same on per-lane LDS cells, plus a u64 cell (add, xor),
+// plus once per launch a ticket: all 256 lanes of the workgroup draw `chain`
+// tickets from one LDS word and mark owner[ticket]; after a barrier the
+// workgroup counts the unmarked entries and checks the word.
+//
+// No wave waits for another; every loop bound is a launch argument; a ticket
+// is range-checked before it indexes. Operation index within a step: 2*k for
+// the returning, 2*k + 1 for the non-returning form of the k-th operation in
+// the order above (lds: integer cells, then the u64 cell, then the float
+// cells); the index after the last one stands for the final compare.
+//
+// Record per wave: {hw word, mismatches (lane-steps, the final compare counting
+// as one more step), first bad round (-1), lowest bad lane in it (-1),
+// checksum lo, checksum hi (xor of the final cell values over lanes and
+// rounds), that lane's first bad operation index (-1), ticket faults (lds:
+// unmarked entries + out-of-range tickets + 1 if the word is not 256*chain)}.
+//
+// inject_* (default -1 = off): in wave inject_wave, at round inject_round, lane
+// inject_lane issues one extra atomic xor of bit inject_bit on its own first
+// cell before the chain: memory really differs from the mirror.
+// ---------------------------------------------------------------------------
+enum { ATOMIC_G32 = 0, ATOMIC_G64 = 1, ATOMIC_GFP = 2, ATOMIC_LDS = 3 };
+enum { ATOMIC_INT_OPS = 28, ATOMIC_U64_OPS = 4, ATOMIC_FP_OPS = 12 };
+enum { ATOMIC_FP_BYTES = 1792, ATOMIC_LDS_WAVE_BYTES = 512 + 1024 + ATOMIC_FP_BYTES };
+enum { ATOMIC_LDS_MAX_CHAIN = 64 };  // owner[256 * chain] as u16: 32 KiB
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef short bf16x2 __attribute__((ext_vector_type(2)));
+
+struct AtomicLaneCheck {
+  int bad = 0;        // this step returned a wrong old value
+  int first_op = -1;  // first wrong operation of this round
+  __device__ __forceinline__ void see(bool wrong, int op) {
+    if (wrong) {
+      bad = 1;
+      if (first_op < 0) first_op = op;
+    }
+  }
+};
+
+__device__ __forceinline__ unsigned atomic_operand(unsigned m, unsigned c, int i) {
+  return fmix32(m ^ (c * 0x9E3779B1u + (unsigned)i * 0x85EBCA6Bu));
+}
+__device__ __forceinline__ unsigned long long atomic_operand(unsigned long long m, unsigned c,
+                                                             int i) {
+  return mix64(m ^ (unsigned long long)(c * 0x9E3779B1u + (unsigned)i * 0x85EBCA6Bu));
+}
+
+// the integer atomics on T (unsigned or unsigned long long) and what each does
+// to the mirror
+template <typename T, int SCOPE> struct AtomicInt {
+  typedef typename std::make_signed<T>::type S;
+  static __device__ __forceinline__ T add(T* p, T x) {
+    return __hip_atomic_fetch_add(p, x, __ATOMIC_RELAXED, SCOPE);
+  }
+  static __device__ __forceinline__ T sub(T* p, T x) {
+    return __hip_atomic_fetch_sub(p, x, __ATOMIC_RELAXED, SCOPE);
+  }
+  static __device__ __forceinline__ T xor_(T* p, T x) {
+    return __hip_atomic_fetch_xor(p, x, __ATOMIC_RELAXED, SCOPE);
+  }
+  static __device__ __forceinline__ T and_(T* p, T x) {
+    return __hip_atomic_fetch_and(p, x, __ATOMIC_RELAXED, SCOPE);
+  }
+  static __device__ __forceinline__ T or_(T* p, T x) {
+    return __hip_atomic_fetch_or(p, x, __ATOMIC_RELAXED, SCOPE);
+  }
+  static __device__ __forceinline__ T umin(T* p, T x) {
+    return __hip_atomic_fetch_min(p, x, __ATOMIC_RELAXED, SCOPE);
+  }
+  static __device__ __forceinline__ T umax(T* p, T x) {
+    return __hip_atomic_fetch_max(p, x, __ATOMIC_RELAXED, SCOPE);
+  }
+  static __device__ __forceinline__ T smin(T* p, T x) {
+    return (T)__hip_atomic_fetch_min(reinterpret_cast<S*>(p), (S)x, __ATOMIC_RELAXED, SCOPE);
+  }
+  static __device__ __forceinline__ T smax(T* p, T x) {
+    return (T)__hip_atomic_fetch_max(reinterpret_cast<S*>(p), (S)x, __ATOMIC_RELAXED, SCOPE);
+  }
+  static __device__ __forceinline__ T swap(T* p, T x) {
+    return __hip_atomic_exchange(p, x, __ATOMIC_RELAXED, SCOPE);
+  }
+  static __device__ __forceinline__ T inc(T* p, T x) {
+    if constexpr (sizeof(T) == 4) {
+      if constexpr (SCOPE == __HIP_MEMORY_SCOPE_AGENT)
+        return __builtin_amdgcn_atomic_inc32(p, x, __ATOMIC_RELAXED, "agent");
+      else
+        return __builtin_amdgcn_atomic_inc32(p, x, __ATOMIC_RELAXED, "workgroup");
+    } else {
+      return __builtin_amdgcn_atomic_inc64(reinterpret_cast<unsigned long*>(p), x,
+                                           __ATOMIC_RELAXED, "agent");
+    }
+  }
+  static __device__ __forceinline__ T dec(T* p, T x) {
+    if constexpr (sizeof(T) == 4) {
+      if constexpr (SCOPE == __HIP_MEMORY_SCOPE_AGENT)
+        return __builtin_amdgcn_atomic_dec32(p, x, __ATOMIC_RELAXED, "agent");
+      else
+        return __builtin_amdgcn_atomic_dec32(p, x, __ATOMIC_RELAXED, "workgroup");
+    } else {
+      return __builtin_amdgcn_atomic_dec64(reinterpret_cast<unsigned long*>(p), x,
+                                           __ATOMIC_RELAXED, "agent");
+    }
+  }
+  // the old value; the cell becomes x when it held cmp
+  static __device__ __forceinline__ T cas(T* p, T cmp, T x) {
+    __hip_atomic_compare_exchange_strong(p, &cmp, x, __ATOMIC_RELAXED, __ATOMIC_RELAXED, SCOPE);
+    return cmp;
+  }
+  static __device__ __forceinline__ T m_smin(T m, T x) { return (S)x < (S)m ? x : m; }
+  static __device__ __forceinline__ T m_smax(T m, T x) { return (S)x > (S)m ? x : m; }
+  static __device__ __forceinline__ T m_inc(T m, T x) { return m >= x ? (T)0 : m + 1; }
+  static __device__ __forceinline__ T m_dec(T m, T x) { return (m == 0 || m > x) ? x : m - 1; }
+};
+
+// operation K on cell J: returning (compared), then non-returning
+#define HVD_ATOMIC_PAIR(K, J, FETCH, APPLY)                       \
+  x = atomic_operand(m[J], c, 2 * (K));                           \
+  old = A::FETCH(p[J], x);                                        \
+  chk.see(old != m[J], op_base + 2 * (K));                        \
+  m[J] = APPLY;                                                   \
+  x = atomic_operand(m[J], c, 2 * (K) + 1);                       \
+  (void)A::FETCH(p[J], x);                                        \
+  m[J] = APPLY;
+
+template <typename T, int SCOPE> struct AtomicIntLane {
+  typedef AtomicInt<T, SCOPE> A;
+  T* p[4];
+  T m[4];
+  __device__ __forceinline__ void init(unsigned char* wave_base, int lane) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) p[j] = reinterpret_cast<T*>(wave_base) + j * 64 + lane;
+  }
+  __device__ __forceinline__ void seed(unsigned sd, int sec, int lane) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      m[j] = (T)valu_seed_state(sd, sec, j * 64 + lane);
+      __hip_atomic_store(p[j], m[j], __ATOMIC_RELAXED, SCOPE);
+    }
+  }
+  __device__ __forceinline__ void inject(int bit) {
+    (void)A::xor_(p[0], (T)1 << bit);
+  }
+  __device__ __forceinline__ void step(unsigned c, AtomicLaneCheck& chk, int op_base) {
+    T x, old;
+    HVD_ATOMIC_PAIR(0, 0, add, m[0] + x)
+    HVD_ATOMIC_PAIR(1, 0, sub, m[0] - x)
+    HVD_ATOMIC_PAIR(2, 0, xor_, m[0] ^ x)
+    HVD_ATOMIC_PAIR(3, 1, smin, A::m_smin(m[1], x))
+    HVD_ATOMIC_PAIR(4, 1, smax, A::m_smax(m[1], x))
+    HVD_ATOMIC_PAIR(5, 1, umin, (x < m[1] ? x : m[1]))
+    HVD_ATOMIC_PAIR(6, 1, umax, (x > m[1] ? x : m[1]))
+    HVD_ATOMIC_PAIR(7, 2, and_, m[2] & x)
+    HVD_ATOMIC_PAIR(8, 2, or_, m[2] | x)
+    HVD_ATOMIC_PAIR(9, 2, swap, x)
+    HVD_ATOMIC_PAIR(10, 3, inc, A::m_inc(m[3], x))
+    HVD_ATOMIC_PAIR(11, 3, dec, A::m_dec(m[3], x))
+    // cmpswap, true value: succeeds
+    x = atomic_operand(m[3], c, 24);
+    old = A::cas(p[3], m[3], x);
+    chk.see(old != m[3], op_base + 24);
+    m[3] = x;
+    x = atomic_operand(m[3], c, 25);
+    (void)A::cas(p[3], m[3], x);
+    m[3] = x;
+    // cmpswap, wrong value (differs in bit 0 at least): fails, cell untouched
+    x = atomic_operand(m[3], c, 26);
+    old = A::cas(p[3], m[3] ^ (x | 1), x);
+    chk.see(old != m[3], op_base + 26);
+    x = atomic_operand(m[3], c, 27);
+    (void)A::cas(p[3], m[3] ^ (x | 1), x);
+  }
+  // expected: this group's cell 0, lane 0
+  __device__ __forceinline__ bool wrong_final(const long long* expected, int lane,
+                                              unsigned long long& checksum) {
+    bool wrong = false;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const T got = __hip_atomic_load(p[j], __ATOMIC_RELAXED, SCOPE);
+      wrong |= got != (T)expected[j * 64 + lane];
+      checksum ^= (unsigned long long)got << (sizeof(T) == 4 ? 32 * (j & 1) : 0);
+    }
+    return wrong;
+  }
+};
+
+// the u64 LDS cell: add, xor
+struct AtomicLds64Lane {
+  typedef AtomicInt<unsigned long long, __HIP_MEMORY_SCOPE_WORKGROUP> A;
+  unsigned long long* p[1];
+  unsigned long long m[1];
+  __device__ __forceinline__ void seed(unsigned sd, int sec, int lane) {
+    m[0] = valu_seed_state(sd, sec, 4 * 64 + lane);
+    __hip_atomic_store(p[0], m[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  __device__ __forceinline__ void step(unsigned c, AtomicLaneCheck& chk, int op_base) {
+    unsigned long long x, old;
+    HVD_ATOMIC_PAIR(0, 0, add, m[0] + x)
+    HVD_ATOMIC_PAIR(1, 0, xor_, m[0] ^ x)
+  }
+};
+#undef HVD_ATOMIC_PAIR
+
+__device__ __forceinline__ unsigned f16_bits(int v) {
+  return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)v);
+}
+__device__ __forceinline__ unsigned bf16_bits(int v) {  // exact for |v| <= 256
+  return __float_as_uint((float)v) >> 16;
+}
+__device__ __forceinline__ unsigned long long f64_bits(long long v) {
+  return (unsigned long long)__double_as_longlong((double)v);
+}
+
+// The float cells of one lane: byte offsets in the wave's region f64 add 0,
+// f64 min/max 512, f32 1024, packed f16 1280, packed bf16 1536. The mirrors
+// are integers: the sums are exact while ops.atomic_fp_exact holds.
+template <bool LDS, int SCOPE> struct AtomicFpLane {
+  float* pf;
+  double* pd;
+  double* pm;
+  unsigned* ph;
+  unsigned* pb;
+  int f, h0, h1, b0, b1;
+  long long d, mm;
+  __device__ __forceinline__ void init(unsigned char* wave_base, int lane) {
+    pd = reinterpret_cast<double*>(wave_base) + lane;
+    pm = reinterpret_cast<double*>(wave_base + 512) + lane;
+    pf = reinterpret_cast<float*>(wave_base + 1024) + lane;
+    ph = reinterpret_cast<unsigned*>(wave_base + 1280) + lane;
+    pb = reinterpret_cast<unsigned*>(wave_base + 1536) + lane;
+  }
+  static __device__ __forceinline__ unsigned pk_f16(unsigned* p, unsigned bits) {
+    const f16x2 v = __builtin_bit_cast(f16x2, bits);
+    if constexpr (LDS)
+      return __builtin_bit_cast(unsigned, __builtin_amdgcn_ds_atomic_fadd_v2f16(
+          (__attribute__((address_space(3))) f16x2*)p, v));
+    else
+      return __builtin_bit_cast(unsigned, __builtin_amdgcn_global_atomic_fadd_v2f16(
+          (__attribute__((address_space(1))) f16x2*)p, v));
+  }
+  static __device__ __forceinline__ unsigned pk_bf16(unsigned* p, unsigned bits) {
+    const bf16x2 v = __builtin_bit_cast(bf16x2, bits);
+    if constexpr (LDS)
+      return __builtin_bit_cast(unsigned, __builtin_amdgcn_ds_atomic_fadd_v2bf16(
+          (__attribute__((address_space(3))) bf16x2*)p, v));
+    else
+      return __builtin_bit_cast(unsigned, __builtin_amdgcn_global_atomic_fadd_v2bf16(
+          (__attribute__((address_space(1))) bf16x2*)p, v));
+  }
+  // j0: the index of the f32 cell among the section's cells
+  __device__ __forceinline__ void seed(unsigned sd, int sec, int lane, int j0) {
+    const unsigned long long sf = valu_seed_state(sd, sec, j0 * 64 + lane);
+    const unsigned long long sdd = valu_seed_state(sd, sec, (j0 + 1) * 64 + lane);
+    const unsigned long long sm = valu_seed_state(sd, sec, (j0 + 2) * 64 + lane);
+    const unsigned sh = (unsigned)valu_seed_state(sd, sec, (j0 + 3) * 64 + lane);
+    const unsigned sb = (unsigned)valu_seed_state(sd, sec, (j0 + 4) * 64 + lane);
+    f = (int)((unsigned)sf & 0xFFFFFu) - 0x80000;
+    d = (long long)(sdd & ((1ull << 50) - 1)) - (1ll << 49);
+    mm = (long long)(sm & ((1ull << 50) - 1)) - (1ll << 49);
+    h0 = (int)(sh & 511u) - 256;
+    h1 = (int)((sh >> 16) & 511u) - 256;
+    b0 = (int)(sb & 63u) - 32;
+    b1 = (int)((sb >> 16) & 63u) - 32;
+    __hip_atomic_store(pf, (float)f, __ATOMIC_RELAXED, SCOPE);
+    __hip_atomic_store(pd, (double)d, __ATOMIC_RELAXED, SCOPE);
+    __hip_atomic_store(pm, (double)mm, __ATOMIC_RELAXED, SCOPE);
+    __hip_atomic_store(ph, f16_bits(h0) | (f16_bits(h1) << 16), __ATOMIC_RELAXED, SCOPE);
+    __hip_atomic_store(pb, bf16_bits(b0) | (bf16_bits(b1) << 16), __ATOMIC_RELAXED, SCOPE);
+  }
+  __device__ __forceinline__ void inject(int bit) {
+    (void)__hip_atomic_fetch_xor(reinterpret_cast<unsigned*>(pf), 1u << bit, __ATOMIC_RELAXED,
+                                 SCOPE);
+  }
+  __device__ __forceinline__ void step(unsigned c, AtomicLaneCheck& chk, int op_base) {
+#pragma unroll
+    for (int form = 0; form < 2; form++) {  // add f32
+      const int x = (int)(atomic_operand((unsigned)f, c, form) % 2047u) - 1023;
+      const float old = __hip_atomic_fetch_add(pf, (float)x, __ATOMIC_RELAXED, SCOPE);
+      if (form == 0) chk.see(__float_as_uint(old) != __float_as_uint((float)f), op_base);
+      f += x;
+    }
+#pragma unroll
+    for (int form = 0; form < 2; form++) {  // add f64
+      const long long x =
+          (long long)(atomic_operand((unsigned long long)d, c, 2 + form) & ((1ull << 41) - 1)) -
+          (1ll << 40);
+      const double old = __hip_atomic_fetch_add(pd, (double)x, __ATOMIC_RELAXED, SCOPE);
+      if (form == 0)
+        chk.see((unsigned long long)__double_as_longlong(old) != f64_bits(d), op_base + 2);
+      d += x;
+    }
+#pragma unroll
+    for (int form = 0; form < 4; form++) {  // min f64 (forms 0, 1), max f64 (forms 2, 3)
+      const long long x =
+          (long long)(atomic_operand((unsigned long long)mm, c, 4 + form) & ((1ull << 52) - 1)) -
+          (1ll << 51);
+      const double old = form < 2 ? __hip_atomic_fetch_min(pm, (double)x, __ATOMIC_RELAXED, SCOPE)
+                                  : __hip_atomic_fetch_max(pm, (double)x, __ATOMIC_RELAXED, SCOPE);
+      if ((form & 1) == 0)
+        chk.see((unsigned long long)__double_as_longlong(old) != f64_bits(mm), op_base + 4 + form);
+      mm = form < 2 ? (x < mm ? x : mm) : (x > mm ? x : mm);
+    }
+#pragma unroll
+    for (int form = 0; form < 2; form++) {  // pk_add f16
+      const unsigned mirror = f16_bits(h0) | (f16_bits(h1) << 16);
+      const unsigned h = atomic_operand(mirror, c, 8 + form);
+      const int x0 = (int)((h & 0xFFFFu) % 31u) - 15, x1 = (int)((h >> 16) % 31u) - 15;
+      const unsigned old = pk_f16(ph, f16_bits(x0) | (f16_bits(x1) << 16));
+      if (form == 0) chk.see(old != mirror, op_base + 8);
+      h0 += x0;
+      h1 += x1;
+    }
+#pragma unroll
+    for (int form = 0; form < 2; form++) {  // pk_add bf16
+      const unsigned mirror = bf16_bits(b0) | (bf16_bits(b1) << 16);
+      const unsigned h = atomic_operand(mirror, c, 10 + form);
+      const int x0 = (int)((h & 0xFFFFu) % 7u) - 3, x1 = (int)((h >> 16) % 7u) - 3;
+      const unsigned old = pk_bf16(pb, bf16_bits(x0) | (bf16_bits(x1) << 16));
+      if (form == 0) chk.see(old != mirror, op_base + 10);
+      b0 += x0;
+      b1 += x1;
+    }
+  }
+  // expected: the f32 cell, lane 0
+  __device__ __forceinline__ bool wrong_final(const long long* expected, int lane,
+                                              unsigned long long& checksum) {
+    const unsigned gf =
+        __hip_atomic_load(reinterpret_cast<unsigned*>(pf), __ATOMIC_RELAXED, SCOPE);
+    const unsigned long long gd =
+        __hip_atomic_load(reinterpret_cast<unsigned long long*>(pd), __ATOMIC_RELAXED, SCOPE);
+    const unsigned long long gm =
+        __hip_atomic_load(reinterpret_cast<unsigned long long*>(pm), __ATOMIC_RELAXED, SCOPE);
+    const unsigned gh = __hip_atomic_load(ph, __ATOMIC_RELAXED, SCOPE);
+    const unsigned gb = __hip_atomic_load(pb, __ATOMIC_RELAXED, SCOPE);
+    checksum ^= gd ^ gm ^ ((unsigned long long)gf << 32) ^ gh ^ ((unsigned long long)gb << 32);
+    return gf != (unsigned)expected[lane] || gd != (unsigned long long)expected[64 + lane] ||
+           gm != (unsigned long long)expected[128 + lane] ||
+           gh != (unsigned)expected[192 + lane] || gb != (unsigned)expected[256 + lane];
+  }
+};
+
+template <int SEC>
+__global__ void __launch_bounds__(256)
+atomic_burn_kernel(const long long* __restrict__ expected, unsigned char* __restrict__ cells,
+                   long wave_bytes, int4* __restrict__ records, unsigned seed, int chain,
+                   int rounds, int inject_wave, int inject_round, int inject_lane,
+                   int inject_bit) {
+  constexpr bool kLds = SEC == ATOMIC_LDS;
+  constexpr bool kInt = SEC != ATOMIC_GFP;
+  constexpr bool kFp = SEC == ATOMIC_GFP || kLds;
+  constexpr int kScope = kLds ? __HIP_MEMORY_SCOPE_WORKGROUP : __HIP_MEMORY_SCOPE_AGENT;
+  constexpr int kFinalOp = kLds ? ATOMIC_INT_OPS + ATOMIC_U64_OPS + ATOMIC_FP_OPS
+                           : kInt ? ATOMIC_INT_OPS : ATOMIC_FP_OPS;
+  typedef typename std::conditional<SEC == ATOMIC_G64, unsigned long long, unsigned>::type T;
+  __shared__ __attribute__((aligned(16))) unsigned char lds[kLds ? 4 * ATOMIC_LDS_WAVE_BYTES : 16];
+  __shared__ unsigned short owner[kLds ? 256 * ATOMIC_LDS_MAX_CHAIN : 2];
+  __shared__ unsigned ticket_word[2];
+  const int lane = threadIdx.x & 63;
+  const int wave = uniform_wave_index();
+  const unsigned place = hw_word();
+
+  // an LDS wave region: the u64 cell at 0, the u32 cells at 512, the float cells at 1536
+  unsigned char* base = kLds ? lds + (threadIdx.x >> 6) * ATOMIC_LDS_WAVE_BYTES
+                             : cells + (long)wave * wave_bytes;
+  AtomicIntLane<T, kScope> ints;
+  AtomicLds64Lane wide;
+  AtomicFpLane<kLds, kScope> fp;
+  if constexpr (kInt) ints.init(base + (kLds ? 512 : 0), lane);
+  if constexpr (kLds) wide.p[0] = reinterpret_cast<unsigned long long*>(base) + lane;
+  if constexpr (kFp) fp.init(base + (kLds ? 1536 : 0), lane);
+
+  const bool inject_here = wave == inject_wave && lane == inject_lane;
+  int mismatched = 0, first_round = -1, first_lane = -1, first_op = -1;
+  unsigned long long checksum = 0;
+  for (int round = 0; round < rounds; round++) {
+    if constexpr (kInt) ints.seed(seed, SEC, lane);
+    if constexpr (kLds) wide.seed(seed, SEC, lane);
+    if constexpr (kFp) fp.seed(seed, SEC, lane, kLds ? 5 : 0);
+    if (inject_here && round == inject_round) {
+      if constexpr (kInt) ints.inject(inject_bit);
+      else fp.inject(inject_bit);
+    }
+    AtomicLaneCheck chk;
+    unsigned bad_steps = 0;
+    for (int c = 0; c < chain; c++) {
+      chk.bad = 0;
+      if constexpr (kInt) ints.step((unsigned)c, chk, 0);
+      if constexpr (kLds) wide.step((unsigned)c, chk, ATOMIC_INT_OPS);
+      if constexpr (kFp) fp.step((unsigned)c, chk, kLds ? ATOMIC_INT_OPS + ATOMIC_U64_OPS : 0);
+      bad_steps += chk.bad;
+    }
+    bool wrong = false;
+    if constexpr (kInt) wrong |= ints.wrong_final(expected, lane, checksum);
+    if constexpr (kLds) {
+      const unsigned long long got =
+          __hip_atomic_load(wide.p[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      wrong |= got != (unsigned long long)expected[4 * 64 + lane];
+      checksum ^= got;
+    }
+    if constexpr (kFp) wrong |= fp.wrong_final(expected + (kLds ? 5 * 64 : 0), lane, checksum);
+    if (wrong) {
+      bad_steps++;
+      if (chk.first_op < 0) chk.first_op = kFinalOp;
+    }
+    const unsigned total = wave_add(bad_steps);
+    mismatched += (int)total;
+    if (total != 0 && first_round < 0) {
+      first_round = round;
+      first_lane = (int)wave_min(bad_steps ? (unsigned)lane : 64u);
+      first_op = (int)wave_min(lane == first_lane ? (unsigned)chk.first_op : 0x7FFFFFFFu);
+    }
+  }
+  checksum = wave_xor(checksum);
+
+  unsigned ticket_faults = 0;
+  if constexpr (kLds) {
+    const unsigned draws = 256u * (unsigned)chain;  // chain <= ATOMIC_LDS_MAX_CHAIN (host check)
+    for (unsigned i = threadIdx.x; i < draws; i += 256) owner[i] = 0;
+    if (threadIdx.x == 0) ticket_word[0] = 0;
+    __syncthreads();
+    // an index the compiler cannot prove uniform: every lane issues its own
+    // ds_add_rtn_u32 (a uniform address is rewritten into one add per wave)
+    int zero = 0;
+    asm volatile("" : "+v"(zero));
+    unsigned out_of_range = 0;
+    for (int c = 0; c < chain; c++) {
+      const unsigned t = __hip_atomic_fetch_add(&ticket_word[zero], 1u, __ATOMIC_RELAXED,
+                                                __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (t < draws) owner[t] = (unsigned short)(threadIdx.x + 1);
+      else out_of_range++;
+    }
+    __syncthreads();
+    unsigned holes = 0;
+    for (unsigned i = lane; i < draws; i += 64) holes += owner[i] == 0;
+    ticket_faults = wave_add(holes + out_of_range) + (ticket_word[0] != draws);
+  }
+  if (lane == 0)
+    store_record8(records, wave, (int)place, mismatched, first_round, first_lane,
+                  (int)(unsigned)checksum, (int)(unsigned)(checksum >> 32), first_op,
+                  (int)ticket_faults);
+}
+
+static int atomic_section_id(const std::string& section) {
+  return section == "g32" ? ATOMIC_G32 : section == "g64" ? ATOMIC_G64
+         : section == "gfp" ? ATOMIC_GFP : section == "lds" ? ATOMIC_LDS : -1;
+}
+
+// expected: int64 on the current device, cell j of lane l at [j*64 + l], the
+// raw bits of the final cell values (ops.atomic_burn_expected): 4 cells for
+// g32 and g64, 5 for gfp, 10 for lds. One untimed warm-up launch, then one
+// timed launch (warm_then_timed_ms); each launch seeds its own cells.
+// Returns (records [waves,8] int32, elapsed_ms of the timed launch).
+std::tuple<torch::Tensor, double> atomic_burn(torch::Tensor expected, const std::string& section,
+                                              long seed, long blocks, long chain, long rounds,
+                                              long inject_wave, long inject_round,
+                                              long inject_lane, long inject_bit) {
+  const int sec = atomic_section_id(section);
+  TORCH_CHECK(sec >= 0, "section must be one of g32, g64, gfp, lds; got ", section);
+  TORCH_CHECK(blocks >= 1 && blocks <= (1L << 14), "blocks must be in [1, 2^14]");
+  TORCH_CHECK(chain >= 1 && rounds >= 1, "chain and rounds must be >= 1");
+  // bounded run (BENCHMARKS.md "Atomic probe"): a step of the slowest section,
+  // g64, measures ~118 us at 2048 workgroups and ~960 us at 16384 (the time
+  // grows with the grid: ~58 ns per workgroup-step); 2^22 workgroup-steps
+  // are ~0.24 s, a quarter of a second. A grid too small to be bound by
+  // throughput is bound by the step's latency instead: see the 2^12-step cap's
+  // arithmetic in BENCHMARKS.md
+  TORCH_CHECK(chain <= (1L << 12) && rounds <= (1L << 12) && chain * rounds <= (1L << 12),
+              "chain*rounds must be <= 2^12");
+  TORCH_CHECK(blocks * chain * rounds <= (1L << 22), "blocks*chain*rounds must be <= 2^22");
+  TORCH_CHECK(sec != ATOMIC_LDS || chain <= ATOMIC_LDS_MAX_CHAIN,
+              "section lds: chain must be <= ", (int)ATOMIC_LDS_MAX_CHAIN,
+              " (the ticket's owner table lives in LDS)");
+  const long bits = sec == ATOMIC_G64 ? 64 : 32;
+  TORCH_CHECK(inject_wave >= -1 && inject_wave < blocks * 4 && inject_round >= -1 &&
+                  inject_round < rounds && inject_lane >= -1 && inject_lane < 64 &&
+                  inject_bit >= -1 && inject_bit < bits,
+              "inject_wave/inject_round/inject_lane/inject_bit out of range");
+  TORCH_CHECK(inject_wave < 0 || (inject_round >= 0 && inject_lane >= 0 && inject_bit >= 0),
+              "an injection needs inject_round, inject_lane and inject_bit");
+  const long ncells = sec == ATOMIC_GFP ? 5 : sec == ATOMIC_LDS ? 10 : 4;
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  TORCH_CHECK(expected.is_cuda() && expected.get_device() == dev,
+              "expected must be on the current GPU");
+  TORCH_CHECK(expected.dtype() == torch::kInt64 && expected.numel() == ncells * 64,
+              "expected must hold ", ncells * 64, " int64 values for section ", section);
+  expected = expected.contiguous();
+  const long long* want = reinterpret_cast<const long long*>(expected.data_ptr<int64_t>());
+  const long wave_bytes = sec == ATOMIC_G32 ? 1024 : sec == ATOMIC_G64 ? 2048
+                          : sec == ATOMIC_GFP ? (long)ATOMIC_FP_BYTES : 0;
+  auto cells = torch::zeros({std::max(blocks * 4 * wave_bytes, 256L)},
+                            torch::TensorOptions().dtype(torch::kUInt8).device(torch::kCUDA));
+  auto records = zero_records(blocks * 4, 8);
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  const double ms = warm_then_timed_ms(stream, [&]() {
+    dispatch_int<4>(sec, [&](auto sec_c) {
+      hipLaunchKernelGGL(atomic_burn_kernel<decltype(sec_c)::value>, dim3(blocks), dim3(256), 0,
+                         stream, want, cells.data_ptr<uint8_t>(), wave_bytes,
+                         reinterpret_cast<int4*>(records.data_ptr<int>()), (unsigned)seed,
+                         (int)chain, (int)rounds, (int)inject_wave, (int)inject_round,
+                         (int)inject_lane, (int)inject_bit);
+    });
+  });
+  return std::make_tuple(records, ms);
+}
+
+// ---------------------------------------------------------------------------
+// Atomic probe, part 2: contention on shared cells (ops.atomic_contend).
+//
+// `cells` shared cells sit 4 KiB apart (512 int64 each); lane gid of a
+// 256-lane workgroup works on cell gid % cells, so the lanes on a cell come
+// from every workgroup, hence from every CU and XCD the grid reaches. The
+// host zeroes or seeds every buffer before the launch and computes every
+// verdict from the buffers copied back after it: the kernel boundary is the
+// only synchronisation, and no wave waits for another.
+//   ticket: `per_lane` returning agent-scope fetch_add(1) on the cell's
+//           counter; owner[cell][ticket] = gid + 1 by a plain store,
+//           range-checked against the draws on that cell; a lane also checks
+//           that its own tickets increase.
+//   reduce: thirteen non-returning forms, one 128-byte slot of the cell each
+//           (slot k at int64 index 16*k): add u32, add u64, xor, or, and, umin,
+//           umax, smin, smax, add f32, add f64, pk_add bf16, pk_add f16. The
+//           float contributions are integers whose every partial sum is exact,
+//           so the result does not depend on the arrival order.
+//   cas:    `per_lane` adds of the lane's value by a cmpswap loop. A failed
+//           cmpswap means another lane's succeeded; N = lanes on the cell *
+//           per_lane succeed in the whole launch, so a lane can fail at most
+//           N - 1 times: a lane that fails N times gives up, which is a fault.
+// Record per wave: {hw word, non-increasing tickets, out-of-range tickets,
+// lanes that gave up, failed cmpswaps, 0, 0, 0}.
+// ---------------------------------------------------------------------------
+enum { CONTEND_TICKET = 0, CONTEND_REDUCE = 1, CONTEND_CAS = 2 };
+enum { CONTEND_CELL_WORDS = 512 };  // int64 per cell: 4 KiB
+
+__device__ __forceinline__ int contend_lanes_on_cell(int lanes, int cells, int cell) {
+  return lanes / cells + (cell < lanes % cells);
+}
+
+__global__ void __launch_bounds__(256)
+atomic_ticket_kernel(unsigned long long* __restrict__ shared, int* __restrict__ owner,
+                     int4* __restrict__ records, int per_lane, int cells, int width) {
+  const int gid = blockIdx.x * 256 + threadIdx.x;
+  const int lanes = gridDim.x * 256;
+  const int cell = gid % cells;
+  const unsigned draws = (unsigned)(contend_lanes_on_cell(lanes, cells, cell) * per_lane);
+  unsigned* counter = reinterpret_cast<unsigned*>(shared + (long)cell * CONTEND_CELL_WORDS);
+  unsigned previous = 0, not_increasing = 0, out_of_range = 0;
+  for (int j = 0; j < per_lane; j++) {
+    const unsigned t =
+        __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t < draws) owner[(long)cell * width + t] = gid + 1;  // draws <= width (host)
+    else out_of_range++;
+    if (j > 0 && t <= previous) not_increasing++;
+    previous = t;
+  }
+  const unsigned place = hw_word();
+  not_increasing = wave_add(not_increasing);
+  out_of_range = wave_add(out_of_range);
+  if ((threadIdx.x & 63) == 0)
+    store_record8(records, gid >> 6, (int)place, (int)not_increasing, (int)out_of_range, 0, 0, 0,
+                  0, 0);
+}
+
+__global__ void __launch_bounds__(256)
+atomic_reduce_kernel(unsigned long long* __restrict__ shared, int4* __restrict__ records,
+                     unsigned seed, int per_lane, int cells) {
+  const int gid = blockIdx.x * 256 + threadIdx.x;
+  const int cell = gid % cells;
+  unsigned long long* slot = shared + (long)cell * CONTEND_CELL_WORDS;
+  typedef __attribute__((address_space(1))) bf16x2* gbf;
+  typedef __attribute__((address_space(1))) f16x2* gf16;
+#define SLOT(K, TYPE) reinterpret_cast<TYPE*>(slot + 16 * (K))
+#define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+  for (int j = 0; j < per_lane; j++) {
+    const unsigned n = (unsigned)(gid / cells) * (unsigned)per_lane + (unsigned)j;
+    const unsigned h = fmix32(seed + (unsigned)gid * 0x9E3779B1u + (unsigned)j * 0x85EBCA6Bu);
+    unsigned hk[13];
+#pragma unroll
+    for (int k = 0; k < 13; k++) hk[k] = fmix32(h + (unsigned)k * 0x632BE5ABu);
+    (void)__hip_atomic_fetch_add(SLOT(0, unsigned), hk[0], RLX_AGENT);
+    (void)__hip_atomic_fetch_add(SLOT(1, unsigned long long),
+                                 ((unsigned long long)hk[1] << 32) | h, RLX_AGENT);
+    (void)__hip_atomic_fetch_xor(SLOT(2, unsigned), hk[2], RLX_AGENT);
+    (void)__hip_atomic_fetch_or(SLOT(3, unsigned), n < 24u ? 1u << (hk[3] & 31) : 0u, RLX_AGENT);
+    (void)__hip_atomic_fetch_and(SLOT(4, unsigned), n < 24u ? ~(1u << (hk[4] & 31)) : ~0u,
+                                 RLX_AGENT);
+    (void)__hip_atomic_fetch_min(SLOT(5, unsigned), hk[5], RLX_AGENT);
+    (void)__hip_atomic_fetch_max(SLOT(6, unsigned), hk[6], RLX_AGENT);
+    (void)__hip_atomic_fetch_min(SLOT(7, int), (int)hk[7], RLX_AGENT);
+    (void)__hip_atomic_fetch_max(SLOT(8, int), (int)hk[8], RLX_AGENT);
+    (void)__hip_atomic_fetch_add(SLOT(9, float), (float)((int)(hk[9] % 257u) - 128), RLX_AGENT);
+    (void)__hip_atomic_fetch_add(SLOT(10, double), (double)(int)hk[10], RLX_AGENT);
+    const bool active = n < 128u;
+    const unsigned b = active ? bf16_bits(hk[11] & 1 ? 1 : -1) | (bf16_bits(hk[11] & 2 ? 1 : -1) << 16)
+                              : 0u;
+    (void)__builtin_amdgcn_global_atomic_fadd_v2bf16((gbf)SLOT(11, unsigned),
+                                                     __builtin_bit_cast(bf16x2, b));
+    const unsigned f = active ? f16_bits((int)((hk[12] & 0xFFFFu) % 33u) - 16) |
+                                    (f16_bits((int)((hk[12] >> 16) % 33u) - 16) << 16)
+                              : 0u;
+    (void)__builtin_amdgcn_global_atomic_fadd_v2f16((gf16)SLOT(12, unsigned),
+                                                    __builtin_bit_cast(f16x2, f));
+  }
+#undef SLOT
+#undef RLX_AGENT
+  const unsigned place = hw_word();
+  if ((threadIdx.x & 63) == 0)
+    store_record8(records, gid >> 6, (int)place, 0, 0, 0, 0, 0, 0, 0);
+}
+
+__global__ void __launch_bounds__(256)
+atomic_cas_kernel(unsigned long long* __restrict__ shared, int4* __restrict__ records,
+                  unsigned seed, int per_lane, int cells) {
+  const int gid = blockIdx.x * 256 + threadIdx.x;
+  const int lanes = gridDim.x * 256;
+  const int cell = gid % cells;
+  const int cap = contend_lanes_on_cell(lanes, cells, cell) * per_lane;
+  unsigned long long* p = shared + (long)cell * CONTEND_CELL_WORDS;
+  const unsigned long long v = mix64(((unsigned long long)seed << 32) | (unsigned)gid);
+  unsigned long long current =
+      __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  int done = 0, failed = 0;
+  for (int tries = 0; tries < per_lane + cap; tries++) {
+    if (done >= per_lane || failed >= cap) break;
+    unsigned long long seen = current;
+    if (__hip_atomic_compare_exchange_strong(p, &seen, current + v, __ATOMIC_RELAXED,
+                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+      done++;
+      current += v;
+    } else {
+      failed++;
+      current = seen;
+    }
+  }
+  const unsigned place = hw_word();
+  const unsigned gave_up = wave_add((unsigned)(done < per_lane));
+  const unsigned retries = wave_add((unsigned)failed);
+  if ((threadIdx.x & 63) == 0)
+    store_record8(records, gid >> 6, (int)place, 0, 0, (int)gave_up, (int)retries, 0, 0, 0);
+}
+
+// Returns {"shared": int64 [cells, 512] (the cells after the launch; ticket:
+// the counter is the low word of [c, 0]; reduce: slot k at [c, 16*k]; cas: the
+// sum at [c, 0]), "owner": int32 [cells, width] (ticket; else [cells, 0]),
+// "records": int32 [blocks*4, 8], "ms": the launch between two events}. One
+// launch on throw-away buffers first, so that the timed one is warm.
+py::dict atomic_contend(const std::string& section, long seed, long blocks, long per_lane,
+                        long cells) {
+  const int sec = section == "ticket" ? CONTEND_TICKET : section == "reduce" ? CONTEND_REDUCE
+                  : section == "cas" ? CONTEND_CAS : -1;
+  TORCH_CHECK(sec >= 0, "section must be one of ticket, reduce, cas; got ", section);
+  TORCH_CHECK(blocks >= 1 && blocks <= (1L << 13), "blocks must be in [1, 2^13]");
+  TORCH_CHECK(per_lane >= 1 && per_lane <= 64, "per_lane must be in [1, 64]");
+  const long lanes = blocks * 256;
+  TORCH_CHECK(cells >= 1 && cells <= 4096 && cells <= lanes,
+              "cells must be in [1, min(4096, blocks*256)]");
+  // bounded run and exact floats (BENCHMARKS.md "Atomic probe"): at most 2^16
+  // operations on one cell (f32: 2^16 contributions of at most 128 stay below
+  // 2^24) and 2^23 in the launch: milliseconds. The cmpswap loop is bounded by
+  // its attempts: a success fails at most the other lanes of its cell once, so
+  // a cell sees at most lanes-on-it x successes-on-it of them, and one word
+  // takes ~88 atomics/us, all cells together ~5500: at most 2^14 successes and
+  // 2^26 attempts on a cell (measured there: 2^23.9 attempts, 179 ms) and 2^30
+  // over all cells (measured there, 256 cells: 8 ms)
+  const long lanes_on_cell = (lanes + cells - 1) / cells;
+  const long on_cell = lanes_on_cell * per_lane;
+  const long cap_cell = sec == CONTEND_CAS ? (1L << 14) : (1L << 16);
+  TORCH_CHECK(on_cell <= cap_cell, "at most ", cap_cell, " operations on one cell; got ", on_cell);
+  if (sec == CONTEND_CAS) {
+    TORCH_CHECK(lanes_on_cell * on_cell <= (1L << 26) &&
+                    cells * lanes_on_cell * on_cell <= (1L << 30),
+                "cas: lanes on a cell x operations on it must be <= 2^26, and <= 2^30 summed "
+                "over the cells");
+  } else {
+    TORCH_CHECK(lanes * per_lane <= (1L << 23), "at most 2^23 operations; got ",
+                lanes * per_lane);
+  }
+  const long width = sec == CONTEND_TICKET ? on_cell : 0;
+  auto init = torch::zeros({cells, (long)CONTEND_CELL_WORDS}, torch::kInt64);
+  int64_t* w = init.data_ptr<int64_t>();
+  for (long c = 0; c < cells; c++) {
+    int64_t* cell = w + c * CONTEND_CELL_WORDS;
+    if (sec == CONTEND_REDUCE) {
+      cell[16 * 4] = 0xFFFFFFFFLL;  // and
+      cell[16 * 5] = 0xFFFFFFFFLL;  // umin
+      cell[16 * 7] = 0x7FFFFFFFLL;  // smin
+      cell[16 * 8] = 0x80000000LL;  // smax
+    } else if (sec == CONTEND_CAS) {
+      unsigned long long x = ((unsigned long long)(unsigned)seed << 32) ^ (unsigned long long)c;
+      x += 0x9E3779B97F4A7C15ull;  // splitmix64, as mix64 on the device
+      x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+      x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+      cell[0] = (int64_t)(x ^ (x >> 31));
+    }
+  }
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  auto launch = [&](torch::Tensor& shared, torch::Tensor& owner, torch::Tensor& records) {
+    unsigned long long* sp = reinterpret_cast<unsigned long long*>(shared.data_ptr<int64_t>());
+    int4* rp = reinterpret_cast<int4*>(records.data_ptr<int>());
+    if (sec == CONTEND_TICKET)
+      hipLaunchKernelGGL(atomic_ticket_kernel, dim3(blocks), dim3(256), 0, stream, sp,
+                         owner.data_ptr<int>(), rp, (int)per_lane, (int)cells, (int)width);
+    else if (sec == CONTEND_REDUCE)
+      hipLaunchKernelGGL(atomic_reduce_kernel, dim3(blocks), dim3(256), 0, stream, sp, rp,
+                         (unsigned)seed, (int)per_lane, (int)cells);
+    else
+      hipLaunchKernelGGL(atomic_cas_kernel, dim3(blocks), dim3(256), 0, stream, sp, rp,
+                         (unsigned)seed, (int)per_lane, (int)cells);
+  };
+  torch::Tensor shared, owner, records;
+  double ms = 0;
+  for (int timed = 0; timed < 2; timed++) {
+    shared = init.to(torch::kCUDA);
+    owner = torch::zeros({cells, width},
+                         torch::TensorOptions().dtype(torch::kInt32).device(torch::kCUDA));
+    records = zero_records(blocks * 4, 8);
+    ms = timed_ms(stream, [&]() { launch(shared, owner, records); });
+  }
+  py::dict d;
+  d["shared"] = shared;
+  d["owner"] = owner;
+  d["records"] = records;
+  d["ms"] = ms;
+  return d;
+}
+
 py::dict device_info(int dev) {
   hipDeviceProp_t prop;
   HIP_CHECK(hipGetDeviceProperties(&prop, dev));
@@ -2781,6 +3535,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("blocks"), py::arg("rounds"),
         "Scalar-load check: every wave reads pattern [2,W] with s_load_dword, x2, x4, x8 and x16 "
         "and compares on the SALU; returns (per-wave records [blocks*4,8], ms)");
+  m.def("atomic_burn", &atomic_burn, py::arg("expected"), py::arg("section"), py::arg("seed") = 1,
+        py::arg("blocks") = 2048, py::arg("chain") = 8, py::arg("rounds") = 33,
+        py::arg("inject_wave") = -1, py::arg("inject_round") = -1, py::arg("inject_lane") = -1,
+        py::arg("inject_bit") = -1,
+        "Exact atomic burn (section g32|g64|gfp|lds): rounds x chain steps of returning and "
+        "non-returning atomics on cells each lane owns, every returned value and the final cells "
+        "verified bitwise; returns (per-wave records [waves,8], ms)");
+  m.def("atomic_contend", &atomic_contend, py::arg("section"), py::arg("seed"), py::arg("blocks"),
+        py::arg("per_lane"), py::arg("cells"),
+        "Contended atomics (section ticket|reduce|cas) from every workgroup on `cells` shared "
+        "cells 4 KiB apart; returns {shared, owner, records, ms} for the host to judge");
   m.def("cu_coverage", &cu_coverage, py::arg("blocks") = 4096,
         "Per-wave (XCC_ID<<16 | HW_ID) placement words for CU-coverage checks");
   m.def("device_info", &device_info, py::arg("dev") = 0);
