@@ -5,7 +5,8 @@ extension is REQUIRED: failure to load raises (no silent eager fallback).
 
 Here: the loader, `gpu_health_report` and the single-tile MFMA checks. Each
 opt-in probe has a module of its own (mfma_burn, lds_march, hbm_march,
-simd_probe, scalar_probe, atomic_probe) on top of `records`; their public names
+simd_probe, scalar_probe, atomic_probe) on top of `records`, and the
+single-tile checks' operands and verdict are in mfma_tiles; their public names
 are re-exported here, and their report functions reach the extension through
 `_ops_on` below.
 """
@@ -25,6 +26,11 @@ from .hbm_march import (HBM_MARCH_TILE_BYTES, hbm_march_pattern, hbm_march_repor
                         hbm_slow_xcds, summarize_hbm_march)
 from .lds_march import (LDS_MARCH_WORDS, lds_march_block_checksum, lds_march_pattern,  # noqa: F401
                         lds_march_report, summarize_lds_march)
+from .mfma_tiles import (E4M3_GROUP_WINDOW_BITS, E4M3_NAN_CODES, TILE_FORMATS,  # noqa: F401
+                         TILE_K, TILE_PROBE_SEEDS, _FP4_E2M1_VALUES, decode_tile_operand,
+                         e4m3_values, e4m3_within_group_window, encode_tile_operand, exact_tile,
+                         judge_mfma_tiles, mfma_tile_operands, mfma_tile_probe, run_mfma_tile,
+                         tile_operand_invariants, tile_product)
 from .mfma_burn import (BURN_FORMATS, _burn_integers, burn_chain_limit, burn_operands,  # noqa: F401
                         mfma_burn_report, summarize_burn)
 from .records import decode_hw_simd, decode_hw_word  # noqa: F401
@@ -113,8 +119,6 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     shares, a few milliseconds) as report["atomic_probe"] and ANDs its verdict
     into `healthy`. Off by default, and the report is then unchanged.
     """
-    import torch
-
     ops = _ops_on(device)
     size_mb = 256 if quick else 2048
     iters = 5 if quick else 20
@@ -124,25 +128,17 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     if len(samples) > 1:
         report["hbm_gbps_samples"] = [round(s, 1) for s in samples]
 
-    torch.manual_seed(0)
-    A = (torch.randn(16, 32, dtype=torch.float32) / 8).bfloat16().cuda(device)
-    B = (torch.randn(32, 16, dtype=torch.float32) / 8).bfloat16().cuda(device)
-    tiles = ops.mfma_check(A, B, 2048, 1)  # 8192 waves >> 256 CUs
-    ref = (A.float() @ B.float())
-    max_err = (tiles - ref.unsqueeze(0)).abs().max().item()
-    tile_spread = (tiles - tiles[0].unsqueeze(0)).abs().max().item()
-    report["mfma_max_err_vs_fp32"] = max_err
-    report["mfma_cross_cu_spread"] = tile_spread  # must be exactly 0
-    report["mfma_ok"] = bool(tile_spread == 0.0 and max_err < 0.1)
-    # Low-precision pipes (MI355X's headline datapaths): fp8 e4m3 MFMA, the
+    # Single-tile MFMA checks (mfma_tiles): operands whose product fp32 holds
+    # exactly, every wave's tile compared with it bitwise. bf16 first, then the
+    # low-precision pipes (MI355X's headline datapaths): fp8 e4m3 MFMA, the
     # MX block-scaled fp8 path (K=128), and MX fp4. A GPU whose bf16 pipes
     # work but whose fp8/fp4 units are broken passes the bf16 check alone.
-    for key, fn in (("mfma_fp8", _mfma_fp8_probe), ("mfma_mx8", _mfma_mx_probe_fp8),
-                    ("mfma_fp4", _mfma_mx_probe_fp4)):
-        err, spread = fn(ops, device)
-        report[f"{key}_max_err_vs_fp32"] = err
-        report[f"{key}_cross_cu_spread"] = spread
-        report[f"{key}_ok"] = bool(spread == 0.0 and err < 0.1)
+    for key, fn in (("mfma", _mfma_bf16_probe), ("mfma_fp8", _mfma_fp8_probe),
+                    ("mfma_mx8", _mfma_mx_probe_fp8), ("mfma_fp4", _mfma_mx_probe_fp4)):
+        err, spread, ok = fn(ops, device)
+        report[f"{key}_max_err_vs_fp32"] = err  # must be exactly 0
+        report[f"{key}_cross_cu_spread"] = spread  # must be exactly 0
+        report[f"{key}_ok"] = bool(ok and err == 0.0 and spread == 0.0)
     report["mfma_lowprec_ok"] = bool(report["mfma_fp8_ok"] and report["mfma_mx8_ok"]
                                      and report["mfma_fp4_ok"])
     # CU coverage: a big grid must place waves on every CU of every XCD; a
@@ -188,48 +184,23 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     return report
 
 
-_FP4_E2M1_VALUES = [0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0,
-                    -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0]
+def _mfma_bf16_probe(ops, device):
+    """bf16 16x16x32 MFMA on every CU against the exact tile of
+    mfma_tile_operands("bf16", 0). Returns (max_err, cross_cu_spread, ok)."""
+    return mfma_tile_probe(ops, device, "bf16")
 
 
 def _mfma_fp8_probe(ops, device):
-    """fp8 e4m3 16x16x32 MFMA vs a torch fp32 reference decoded from the
-    same raw e4m3 bytes. Returns (max_err, cross_cu_spread)."""
-    import torch
-
-    torch.manual_seed(1)
-    A8 = (torch.randn(16, 32) / 8).to(torch.float8_e4m3fn).cuda(device)
-    B8 = (torch.randn(32, 16) / 8).to(torch.float8_e4m3fn).cuda(device)
-    tiles = ops.mfma_check_fp8(A8.view(torch.uint8), B8.view(torch.uint8), 2048)
-    ref = A8.float() @ B8.float()
-    return ((tiles - ref.unsqueeze(0)).abs().max().item(),
-            (tiles - tiles[0].unsqueeze(0)).abs().max().item())
+    """fp8 e4m3 16x16x32 MFMA against the exact product of the same raw e4m3
+    bytes."""
+    return mfma_tile_probe(ops, device, "fp8")
 
 
 def _mfma_mx_probe_fp8(ops, device):
     """MX block-scaled fp8 (16x16x128 f8f6f4, fmt=0) with unit scales."""
-    import torch
-
-    torch.manual_seed(2)
-    A8 = (torch.randn(16, 128) / 16).to(torch.float8_e4m3fn).cuda(device)
-    B8 = (torch.randn(128, 16) / 16).to(torch.float8_e4m3fn).cuda(device)
-    tiles = ops.mfma_check_mx(A8.view(torch.uint8), B8.view(torch.uint8), 2048, 0)
-    ref = A8.float() @ B8.float()
-    return ((tiles - ref.unsqueeze(0)).abs().max().item(),
-            (tiles - tiles[0].unsqueeze(0)).abs().max().item())
+    return mfma_tile_probe(ops, device, "mx8")
 
 
 def _mfma_mx_probe_fp4(ops, device):
-    """MX block-scaled fp4 (e2m1 codes, fmt=4) with unit scales. Values are
-    exactly representable and the K=128 dot products stay small, so the fp32
-    reference matches bit-for-bit on healthy hardware."""
-    import torch
-
-    g = torch.Generator().manual_seed(3)
-    A4 = torch.randint(0, 16, (16, 128), generator=g, dtype=torch.uint8).cuda(device)
-    B4 = torch.randint(0, 16, (128, 16), generator=g, dtype=torch.uint8).cuda(device)
-    lut = torch.tensor(_FP4_E2M1_VALUES, dtype=torch.float32).cuda(device)
-    tiles = ops.mfma_check_mx(A4, B4, 2048, 4)
-    ref = lut[A4.long()] @ lut[B4.long()]
-    return ((tiles - ref.unsqueeze(0)).abs().max().item(),
-            (tiles - tiles[0].unsqueeze(0)).abs().max().item())
+    """MX block-scaled fp4 (e2m1 codes, fmt=4) with unit scales."""
+    return mfma_tile_probe(ops, device, "mx4")

@@ -16,20 +16,57 @@ pytestmark = pytest.mark.gpu
 needs_gpu = pytest.mark.skipif(not torch.cuda.is_available(), reason="no GPU")
 
 
+# The one inexact MFMA case: bf16 randn/4 against a ramp has 16-bit products at
+# many exponents, so fp32 cannot hold the sum exactly and the result depends on
+# how the pipe accumulates. Per element, |tile - float64 product| must stay
+# within BF16_RANDN_C * 2^-24 * (|A| @ |B|). Any-order fp32 accumulation with
+# truncation would give about 2K = 64; the constant is the next power of two
+# above four times the largest ratio measured on an MI355X over seeds 0..31
+# (BF16_RANDN_MEASURED_RATIO, BENCHMARKS.md), the kernel being deterministic
+# and the margin covering only the variation between seeds.
+BF16_RANDN_MEASURED_RATIO = 0.782   # seed 7 itself: 0.339
+BF16_RANDN_C = 4
+
+
+def bf16_randn_operands(seed=7):
+    """(A, B) bf16 on the CPU; asymmetric B catches transposed C-write layouts."""
+    g = torch.Generator().manual_seed(seed)
+    A = (torch.randn(16, 32, generator=g) / 4).bfloat16()
+    B = (torch.arange(32 * 16, dtype=torch.float32).reshape(32, 16) / 997 - 0.25).bfloat16()
+    return A, B
+
+
+def bf16_error_ratio(tiles, A, B):
+    """max over waves and elements of |tile - float64 product| in units of
+    2^-24 * (|A| @ |B|)."""
+    a, b = A.double().cpu(), B.double().cpu()
+    unit = (a.abs() @ b.abs()) * 2.0 ** -24
+    return ((tiles.double().cpu() - (a @ b).unsqueeze(0)).abs() / unit.unsqueeze(0)).max().item()
+
+
+def assert_all_waves_equal(tiles, expected, what):
+    """Every wave's tile equals the float64-derived one: no tolerance."""
+    tiles = tiles.cpu()
+    assert tiles.shape[1:] == expected.shape
+    wrong = tiles != expected.unsqueeze(0)
+    assert not wrong.any(), (
+        f"{what}: {int(wrong.sum())} elements in {int(wrong.any(-1).any(-1).sum())} of "
+        f"{tiles.shape[0]} waves differ, max |err| {(tiles - expected).abs().max().item()}")
+    assert torch.equal(tiles, expected.expand_as(tiles))
+
+
 @needs_gpu
 def test_mfma_numerics_vs_fp32():
-    """MFMA bf16 tile GEMM vs plain PyTorch fp32 reference of the same op."""
+    """MFMA bf16 tile GEMM on inexact inputs vs a float64 reference of the
+    same op, every wave, within the relative per-element bound above."""
     from hivedscheduler_amd.ops import get_ops
 
     ops = get_ops()
-    torch.manual_seed(7)
-    # asymmetric B catches transposed C-write layouts
-    A = (torch.randn(16, 32) / 4).bfloat16().cuda()
-    B = (torch.arange(32 * 16, dtype=torch.float32).reshape(32, 16) / 997 - 0.25).bfloat16().cuda()
-    tiles = ops.mfma_check(A, B, 64, 1)
-    ref = A.float() @ B.float()  # fp32 reference (bf16 inputs upcast)
-    err = (tiles[0] - ref).abs().max().item()
-    assert err < 0.05, f"MFMA result deviates from fp32 reference: {err}"
+    A, B = bf16_randn_operands()
+    tiles = ops.mfma_check(A.cuda(), B.cuda(), 64, 1)
+    ratio = bf16_error_ratio(tiles, A, B)
+    print(f"bf16 randn/4 error ratio {ratio} (bound {BF16_RANDN_C})")
+    assert ratio <= BF16_RANDN_C, f"MFMA result deviates from float64 reference: ratio {ratio}"
     # every wave on every CU must produce the identical tile
     spread = (tiles - tiles[0].unsqueeze(0)).abs().max().item()
     assert spread == 0.0, f"cross-CU MFMA mismatch: {spread}"
@@ -46,67 +83,59 @@ def test_mfma_identity():
         A[i, i] = 1.0
     B = (torch.randn(32, 16) / 4)
     tiles = ops.mfma_check(A.bfloat16().cuda(), B.bfloat16().cuda(), 8, 1)
-    ref = A.bfloat16().float() @ B.bfloat16().float()
-    assert torch.allclose(tiles[0].cpu(), ref, atol=1e-3), "identity check failed"
+    assert_all_waves_equal(tiles, B.bfloat16().float()[:16], "identity check")
 
 
 @needs_gpu
 def test_mfma_fp8_numerics_vs_fp32():
-    """fp8 e4m3 MFMA (v_mfma_f32_16x16x32_fp8_fp8) vs a torch fp32 reference
-    decoded from the same raw e4m3 bytes; exercises the CDNA4 low-precision
-    pipes the bf16 check cannot see."""
-    from hivedscheduler_amd.ops import get_ops
+    """fp8 e4m3 MFMA (v_mfma_f32_16x16x32_fp8_fp8) vs the float64 product
+    decoded from the same raw e4m3 bytes, which fp32 holds exactly (sum
+    |a||b| < 64 in multiples of 2^-18) and which stays inside the window the
+    fp8 pipes keep (e4m3_within_group_window); exercises the CDNA4
+    low-precision pipes the bf16 check cannot see."""
+    from hivedscheduler_amd.ops import e4m3_within_group_window, exact_tile, get_ops
 
     ops = get_ops()
     torch.manual_seed(11)
-    A8 = (torch.randn(16, 32) / 8).to(torch.float8_e4m3fn).cuda()
+    A8 = (torch.randn(16, 32) / 8).to(torch.float8_e4m3fn).view(torch.uint8)
     # asymmetric B catches transposed C-write layouts
     B8 = ((torch.arange(32 * 16, dtype=torch.float32).reshape(32, 16) / 997 - 0.25)
-          .to(torch.float8_e4m3fn).cuda())
-    tiles = ops.mfma_check_fp8(A8.view(torch.uint8), B8.view(torch.uint8), 64)
-    ref = A8.float() @ B8.float()
-    err = (tiles[0] - ref).abs().max().item()
-    assert err < 0.05, f"fp8 MFMA deviates from fp32 reference: {err}"
-    spread = (tiles - tiles[0].unsqueeze(0)).abs().max().item()
-    assert spread == 0.0, f"cross-CU fp8 MFMA mismatch: {spread}"
+          .to(torch.float8_e4m3fn).view(torch.uint8))
+    # bitwise only because no product falls below the window the pipe keeps
+    assert e4m3_within_group_window("fp8", A8, B8).all()
+    tiles = ops.mfma_check_fp8(A8.cuda(), B8.cuda(), 64)
+    assert_all_waves_equal(tiles, exact_tile("fp8", A8, B8), "fp8 MFMA")
 
 
 @needs_gpu
 def test_mfma_mx_fp8_numerics_vs_fp32():
     """MX block-scaled fp8 (v_mfma_f32_16x16x128_f8f6f4, fmt=0, unit scales)
-    vs torch fp32 — the instruction behind the ~5 PF fp8 headline rate."""
-    from hivedscheduler_amd.ops import get_ops
+    vs the exact float64 product — the instruction behind the ~5 PF fp8
+    headline rate."""
+    from hivedscheduler_amd.ops import e4m3_within_group_window, exact_tile, get_ops
 
     ops = get_ops()
     torch.manual_seed(12)
-    A8 = (torch.randn(16, 128) / 16).to(torch.float8_e4m3fn).cuda()
+    A8 = (torch.randn(16, 128) / 16).to(torch.float8_e4m3fn).view(torch.uint8)
     B8 = ((torch.arange(128 * 16, dtype=torch.float32).reshape(128, 16) / 4093 - 0.25)
-          .to(torch.float8_e4m3fn).cuda())
-    tiles = ops.mfma_check_mx(A8.view(torch.uint8), B8.view(torch.uint8), 64, 0)
-    ref = A8.float() @ B8.float()
-    err = (tiles[0] - ref).abs().max().item()
-    assert err < 0.05, f"MX fp8 MFMA deviates from fp32 reference: {err}"
-    spread = (tiles - tiles[0].unsqueeze(0)).abs().max().item()
-    assert spread == 0.0, f"cross-CU MX fp8 MFMA mismatch: {spread}"
+          .to(torch.float8_e4m3fn).view(torch.uint8))
+    assert e4m3_within_group_window("mx8", A8, B8).all()
+    tiles = ops.mfma_check_mx(A8.cuda(), B8.cuda(), 64, 0)
+    assert_all_waves_equal(tiles, exact_tile("mx8", A8, B8), "MX fp8 MFMA")
 
 
 @needs_gpu
 def test_mfma_mx_fp4_numerics_exact():
     """MX fp4 (e2m1 codes, fmt=4, unit scales): all products are multiples of
-    0.25 with sums << 2^24, so the fp32 reference must match bit-for-bit."""
-    from hivedscheduler_amd.ops import get_ops, _FP4_E2M1_VALUES
+    0.25 with sums << 2^24, so the float64 product must match bit-for-bit."""
+    from hivedscheduler_amd.ops import exact_tile, get_ops
 
     ops = get_ops()
     g = torch.Generator().manual_seed(13)
-    A4 = torch.randint(0, 16, (16, 128), generator=g, dtype=torch.uint8).cuda()
-    B4 = torch.randint(0, 16, (128, 16), generator=g, dtype=torch.uint8).cuda()
-    lut = torch.tensor(_FP4_E2M1_VALUES, dtype=torch.float32).cuda()
-    tiles = ops.mfma_check_mx(A4, B4, 64, 4)
-    ref = lut[A4.long()] @ lut[B4.long()]
-    assert torch.equal(tiles[0], ref), (
-        f"MX fp4 MFMA mismatch: max err {(tiles[0] - ref).abs().max().item()}")
-    spread = (tiles - tiles[0].unsqueeze(0)).abs().max().item()
-    assert spread == 0.0, f"cross-CU MX fp4 MFMA mismatch: {spread}"
+    A4 = torch.randint(0, 16, (16, 128), generator=g, dtype=torch.uint8)
+    B4 = torch.randint(0, 16, (128, 16), generator=g, dtype=torch.uint8)
+    tiles = ops.mfma_check_mx(A4.cuda(), B4.cuda(), 64, 4)
+    assert_all_waves_equal(tiles, exact_tile("mx4", A4, B4), "MX fp4 MFMA")
 
 
 @needs_gpu
