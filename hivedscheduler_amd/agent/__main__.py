@@ -57,6 +57,12 @@ def main() -> None:
                          "cmpswap across all XCDs) every N sweeps (on deep sweeps); 0 = never")
     ap.add_argument("--atomic-probe", action="store_true",
                     help="with --local: also run the atomic probe")
+    ap.add_argument("--mx-scale-probe-every", type=int, default=0,
+                    help="MX scale probe (block-scaled MFMA with per-lane scales: exact tiles in "
+                         "every format and both shapes, scaled burn per CU) every N sweeps (on "
+                         "deep sweeps); 0 = never")
+    ap.add_argument("--mx-scale-probe", action="store_true",
+                    help="with --local: also run the MX scale probe")
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
@@ -73,7 +79,8 @@ def main() -> None:
                                      min_xcd_ratio=args.min_xcd_ratio,
                                      simd_probe=args.simd_probe,
                                      scalar_probe=args.scalar_probe,
-                                     atomic_probe=args.atomic_probe)
+                                     atomic_probe=args.atomic_probe,
+                                     mx_scale_probe=args.mx_scale_probe)
         if args.p2p_matrix:
             try:
                 m = p2p_link_matrix()
@@ -97,7 +104,8 @@ def main() -> None:
                             min_xcd_ratio=args.min_xcd_ratio,
                             simd_probe_every=args.simd_probe_every,
                             scalar_probe_every=args.scalar_probe_every,
-                            atomic_probe_every=args.atomic_probe_every)
+                            atomic_probe_every=args.atomic_probe_every,
+                            mx_scale_probe_every=args.mx_scale_probe_every)
     if args.once:
         import json
 

@@ -61,6 +61,7 @@ def collect_node_health(
     simd_probe: bool = False,
     scalar_probe: bool = False,
     atomic_probe: bool = False,
+    mx_scale_probe: bool = False,
 ) -> dict:
     """One health sweep over all visible GPUs. deep=True also runs the HIP
     kernels (HBM + MFMA); sweep=True adds the 16 GiB HBM stuck-bit pattern
@@ -114,6 +115,14 @@ def collect_node_health(
     (the shared cells that ended wrong, as cell, section, op), and a failed
     probe marks the leaf bad.
 
+    mx_scale_probe=True (with deep) adds the MX scale probe (the block-scaled
+    MFMA with per-lane scales in every format and both shapes, as exact tiles
+    and as a burn): per GPU it records `mx_scale_probe_ok`,
+    `mx_scale_tiles_ok`, `mx_scale_burn_ok`, `mx_scale_tflops` ({case:
+    TFLOP/s}, reported, not judged) and `mx_scale_bad_cus` (the CUs of any
+    wave whose burn result was wrong, as xcc, se, sh, cu; a key of its own),
+    and a failed probe marks the leaf bad.
+
     The stuck-bit scan transiently holds up to 16 GiB of HBM; on a GPU
     running tenant jobs this can make the tenant's own allocations fail.
     Keep sweep on the low-frequency cadence and prefer idle GPUs (the
@@ -136,7 +145,7 @@ def collect_node_health(
 
         kwargs = _set_flags(burn=burn, lds_march=lds_march, hbm_march=hbm_march,
                             simd_probe=simd_probe, scalar_probe=scalar_probe,
-                            atomic_probe=atomic_probe)
+                            atomic_probe=atomic_probe, mx_scale_probe=mx_scale_probe)
         for i in range(n):
             gpu = report["gpus"][str(i)]
             try:
@@ -226,6 +235,19 @@ def collect_node_health(
                     )
                     if not p["ok"] or p["bad_cus"] or p["bad_cells"]:
                         gpu["healthy"] = False
+                if mx_scale_probe:
+                    p = rep["mx_scale_probe"]
+                    gpu.update(
+                        mx_scale_probe_ok=bool(p["ok"]),
+                        mx_scale_tiles_ok=bool(p["tiles"]["ok"]),
+                        mx_scale_burn_ok=bool(p["burn"]["ok"]),
+                        mx_scale_tflops={name: round(s["tflops"], 1)
+                                         for name, s in p["burn"]["cases"].items()},
+                        mx_scale_bad_cus=[{k: c[k] for k in ("xcc", "se", "sh", "cu")}
+                                          for c in p["bad_cus"]],
+                    )
+                    if not p["ok"] or p["bad_cus"]:
+                        gpu["healthy"] = False
             except Exception as e:
                 gpu.update(healthy=False, error=str(e)[:200])
     if probe_pairs and n >= 2:
@@ -301,7 +323,7 @@ class NodeHealthAgent:
                  min_mfma_tflops: Optional[float] = None, lds_march_every: int = 0,
                  hbm_march_every: int = 0, min_xcd_ratio: Optional[float] = None,
                  simd_probe_every: int = 0, scalar_probe_every: int = 0,
-                 atomic_probe_every: int = 0):
+                 atomic_probe_every: int = 0, mx_scale_probe_every: int = 0):
         self.scheduler_url = scheduler_url.rstrip("/")
         self.node_name = node_name or socket.gethostname()
         self.interval_s = interval_s
@@ -341,6 +363,10 @@ class NodeHealthAgent:
         # contended sections load the L2 and memory-side atomic units of
         # every XCD)
         self.atomic_probe_every = atomic_probe_every
+        # MX scale probe cadence (exact scaled tiles + scaled burn), same
+        # pattern; 0 = never (about 0.2 s of matrix-core time per GPU, on
+        # cores a tenant may be using)
+        self.mx_scale_probe_every = mx_scale_probe_every
         self._rounds = 0
 
     def post_report(self, report: dict) -> bool:
@@ -398,7 +424,8 @@ class NodeHealthAgent:
                             hbm_march=deep and self._due(self.hbm_march_every),
                             simd_probe=deep and self._due(self.simd_probe_every),
                             scalar_probe=deep and self._due(self.scalar_probe_every),
-                            atomic_probe=deep and self._due(self.atomic_probe_every))
+                            atomic_probe=deep and self._due(self.atomic_probe_every),
+                            mx_scale_probe=deep and self._due(self.mx_scale_probe_every))
         self._rounds += 1
         if "burn" in kwargs:
             kwargs["min_mfma_tflops"] = self.min_mfma_tflops

@@ -5,7 +5,7 @@ extension is REQUIRED: failure to load raises (no silent eager fallback).
 
 Here: the loader, `gpu_health_report` and the single-tile MFMA checks. Each
 opt-in probe has a module of its own (mfma_burn, lds_march, hbm_march,
-simd_probe, scalar_probe, atomic_probe) on top of `records`, and the
+simd_probe, scalar_probe, atomic_probe, mx_scale) on top of `records`, and the
 single-tile checks' operands and verdict are in mfma_tiles; their public names
 are re-exported here, and their report functions reach the extension through
 `_ops_on` below.
@@ -33,6 +33,14 @@ from .mfma_tiles import (E4M3_GROUP_WINDOW_BITS, E4M3_NAN_CODES, TILE_FORMATS,  
                          tile_operand_invariants, tile_product)
 from .mfma_burn import (BURN_FORMATS, _burn_integers, burn_chain_limit, burn_operands,  # noqa: F401
                         mfma_burn_report, summarize_burn)
+from .mx_scale import (MX_BURN_FORMATS, MX_FORMATS, MX_FULL_WIDTH_DELTAS,  # noqa: F401
+                       MX_SCALE_PAIRS, MX_SCALE_SPREAD, MX_SHAPE_NAMES, MX_SHAPES, e8m0_value,
+                       mx_code_count, mx_decode, mx_decode_sweep_case, mx_encode, mx_exactness,
+                       mx_full_width_case, mx_k_slot_case, mx_scale_burn_operands,
+                       mx_scale_burn_report, mx_scale_case_name, mx_scale_chain_limit,
+                       mx_scale_invariants, mx_scale_operands, mx_scale_probe_report,
+                       mx_scale_tile_report, mx_scaled_product, mx_slot_sweep_case,
+                       summarize_mx_scale_burn)
 from .records import decode_hw_simd, decode_hw_word  # noqa: F401
 from .scalar_probe import (SALU_CHAINS, SALU_SECTIONS, SGPR_MARCH_FIRST_REG,  # noqa: F401
                            SGPR_MARCH_INJECT_REG, SGPR_MARCH_REGS, salu_burn_checksum,
@@ -72,7 +80,8 @@ def _ops_on(device: int):
 def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
                       bw_samples: int = 1, burn: bool = False, lds_march: bool = False,
                       hbm_march: bool = False, simd_probe: bool = False,
-                      scalar_probe: bool = False, atomic_probe: bool = False) -> dict:
+                      scalar_probe: bool = False, atomic_probe: bool = False,
+                      mx_scale_probe: bool = False) -> dict:
     """Run the health-probe kernels on one GPU and return measured facts.
 
     Feeds leaf-cell healthiness: HBM bandwidth deficit, MFMA mismatch, or
@@ -118,6 +127,13 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     the contended ticket, reduce and cmpswap sections on cells every workgroup
     shares, a few milliseconds) as report["atomic_probe"] and ANDs its verdict
     into `healthy`. Off by default, and the report is then unchanged.
+
+    mx_scale_probe=True adds the MX scale probe (`mx_scale_probe_report`: the
+    block-scaled MFMA with per-lane E8M0 scales, every scale byte, e5m2 and
+    the 6-bit formats, mixed formats and the 32x32x64 shape, as exact tiles
+    and as a burn of tens of milliseconds per format and shape) as
+    report["mx_scale_probe"] and ANDs its verdict into `healthy`. Off by
+    default, and the report is then unchanged.
     """
     ops = _ops_on(device)
     size_mb = 256 if quick else 2048
@@ -181,6 +197,9 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     if atomic_probe:
         report["atomic_probe"] = atomic_probe_report(device)
         report["healthy"] = bool(report["healthy"] and report["atomic_probe"]["ok"])
+    if mx_scale_probe:
+        report["mx_scale_probe"] = mx_scale_probe_report(device)
+        report["healthy"] = bool(report["healthy"] and report["mx_scale_probe"]["ok"])
     return report
 
 

@@ -10,6 +10,9 @@
 //                so that fp32 holds it exactly — catches broken matrix cores
 //  - mfma_burn:  sustained, timed MFMA issue per datapath, verified bitwise in
 //                the kernel; TFLOP/s plus the CU of any wave that was wrong
+//  - mx_scale_tile / mx_scale_burn: the block-scaled MFMA with per-lane E8M0
+//                scales, all four scale bytes, e5m2 and the 6-bit formats, mixed
+//                formats and the 32x32x64 shape, bitwise against float64
 //  - lds_march:  all 160 KiB of every CU's LDS, both bit polarities, narrow
 //                and wide reads, timed; the CU, word and bits of any mismatch
 //  - valu_burn:  sustained, timed vector-ALU issue per section (integer, f32,
@@ -762,6 +765,373 @@ std::tuple<torch::Tensor, double> mfma_burn(torch::Tensor A, torch::Tensor B,
     dispatch_int<4>(f, [&](auto fmt_c) {
       hipLaunchKernelGGL((mfma_burn_kernel<decltype(fmt_c)::value>), dim3(blocks), dim3(256), 0,
                          stream, A.data_ptr(), B.data_ptr(), expected.data_ptr<float>(),
+                         reinterpret_cast<int4*>(records.data_ptr<int>()), (int)chain, (int)rounds,
+                         (int)inject_wave, (int)inject_round);
+    });
+  });
+  return std::make_tuple(records, ms);
+}
+
+// ---------------------------------------------------------------------------
+// MX scale probe: what every real MXFP8/MXFP6/MXFP4 GEMM uses of
+// v_mfma_scale_f32_{16x16x128,32x32x64}_f8f6f4 and the checks above leave
+// out: a per-lane E8M0 scale operand, the four-way byte select (op_sel,
+// op_sel_hi), different scales in different K blocks, the 6-bit unpackers
+// (e2m3, e3m2), the e5m2 decoder, mixed A/B formats (cbsz != blgp) and the
+// 32x32x64 shape. mx_scale_tile returns one tile per wave for the host to
+// compare bitwise with the float64 product (ops/mx_scale.py); mx_scale_burn
+// is the sustained, timed run with the compare in the kernel.
+//
+// Format codes are the instruction's own: 0 e4m3, 1 e5m2, 2 e2m3, 3 e3m2,
+// 4 e2m1. In memory an operand is one code per byte (raw bytes for the 8-bit
+// formats, 0..63 and 0..15 for the others).
+//
+// Layouts (gfx950), with M the tile edge and one lane group = M lanes:
+//   16x16x128: lane l has i = l & 15, g = l >> 4 (4 groups);
+//              D reg r of 4  -> row 4g + r, col i
+//   32x32x64:  lane l has i = l & 31, g = l >> 5 (2 groups);
+//              D reg r of 16 -> row 8*(r>>2) + 4g + (r&3), col i
+//   K walk:    the lane holds A[i][k(g,j)] and B[k(g,j)][i], j in [0,32).
+//              6-bit and 4-bit formats: k = 32g + j, a lane group's K share
+//              is exactly one 32-element MX block. 8-bit formats (measured on
+//              an MI355X, BENCHMARKS.md "MX scale probe"): the instruction
+//              takes VGPRs 0-3 of all groups as the first half of K and VGPRs
+//              4-7 as the second, k = (j>>4) * 16G + 16g + (j&15) with G the
+//              number of groups, so a lane holds 16 elements of each of two
+//              blocks and the scales it applies come from two other lanes.
+//              Without per-block scales the walk cannot be observed (A and B
+//              permute alike), which is why mfma_check_mx passes with 32g + j.
+//   registers: element j of the lane's 32 is byte j of 8 VGPRs (8-bit
+//              formats), bits [6j, 6j+6) of a 192-bit little-endian stream
+//              in 6 VGPRs (6-bit), bits [4j, 4j+4) of 4 VGPRs (4-bit); the
+//              upper registers of the i32x8 operand are zero.
+//   scales:    byte `sel` (the instruction's op_sel | op_sel_hi << 1) of the
+//              lane's scale VGPR is the E8M0 scale (2^(s-127)) of A's row i,
+//              block g; for the B operand of B's column i, block g. The host
+//              passes the four bytes a lane holds: scale_a [M, K/32, 4],
+//              scale_b [K/32, M, 4].
+//
+// Fragments are packed in registers straight from global byte loads, with no
+// LDS staging: each code is read by exactly one lane, once per launch, so
+// there is nothing for LDS to share, and the burn's hot loop touches no
+// memory at all. B's loads walk a column (stride M), which neighbouring lanes
+// coalesce. Each format of a mixed pair walks K its own way; the instruction
+// pairs elements by k.
+//
+// op_sel is an immediate, so the runtime (sel_a, sel_b) of the tile kernel is
+// a wave-uniform switch over the 16 combinations, and the burn's chain is
+// unrolled by four with step c issuing op_sel = c & 3 on both sides.
+// ---------------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+
+constexpr int mx_bits(int fmt) { return fmt <= 1 ? 8 : fmt <= 3 ? 6 : 4; }
+
+template <int SHAPE> struct MxShape;
+
+template <> struct MxShape<0> {  // 16x16x128
+  static constexpr int M = 16, LOG_M = 4, K = 128, G = 4, NREG = 4;
+  typedef f32x4 acc;
+  static __device__ __forceinline__ int row(int r, int g) { return 4 * g + r; }
+  template <int FA, int FB, int SEL_A, int SEL_B>
+  static __device__ __forceinline__ acc mma(i32x8 a, i32x8 b, acc c, int sa, int sb) {
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, FA, FB, SEL_A, sa, SEL_B, sb);
+  }
+};
+
+template <> struct MxShape<1> {  // 32x32x64
+  static constexpr int M = 32, LOG_M = 5, K = 64, G = 2, NREG = 16;
+  typedef f32x16 acc;
+  static __device__ __forceinline__ int row(int r, int g) {
+    return 8 * (r >> 2) + 4 * g + (r & 3);
+  }
+  template <int FA, int FB, int SEL_A, int SEL_B>
+  static __device__ __forceinline__ acc mma(i32x8 a, i32x8 b, acc c, int sa, int sb) {
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, FA, FB, SEL_A, sa, SEL_B, sb);
+  }
+};
+
+// the lane's 32 codes, packed BITS apiece into the operand: element j is
+// p[mx_k<BITS, G>(g, j) * stride]
+template <int BITS, int G>
+__device__ __forceinline__ constexpr int mx_k(int g, int j) {
+  return BITS == 8 ? (j >> 4) * 16 * G + 16 * g + (j & 15) : 32 * g + j;
+}
+
+template <int BITS, int G>
+__device__ __forceinline__ i32x8 mx_pack(const unsigned char* __restrict__ p, int g, int stride) {
+  unsigned w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int j = 0; j < 32; j++) {
+    const unsigned code = p[mx_k<BITS, G>(g, j) * stride] & ((1u << BITS) - 1);
+    const int bit = j * BITS, word = bit >> 5, at = bit & 31;
+    w[word] |= code << at;
+    if (at + BITS > 32) w[word + 1] |= code >> (32 - at);  // a 6-bit code across two VGPRs
+  }
+  return (i32x8){(int)w[0], (int)w[1], (int)w[2], (int)w[3],
+                 (int)w[4], (int)w[5], (int)w[6], (int)w[7]};
+}
+
+// one MFMA with the runtime byte selects sel = sel_a * 4 + sel_b (wave-uniform)
+template <int SHAPE, int FA, int FB>
+__device__ __forceinline__ typename MxShape<SHAPE>::acc
+mx_mma_sel(i32x8 a, i32x8 b, typename MxShape<SHAPE>::acc c, int sa, int sb, int sel) {
+  typedef MxShape<SHAPE> S;
+  switch (sel) {
+#define MX_SEL_CASE(n) \
+  case n: return S::template mma<FA, FB, ((n) >> 2), ((n) & 3)>(a, b, c, sa, sb);
+    MX_SEL_CASE(0) MX_SEL_CASE(1) MX_SEL_CASE(2) MX_SEL_CASE(3)
+    MX_SEL_CASE(4) MX_SEL_CASE(5) MX_SEL_CASE(6) MX_SEL_CASE(7)
+    MX_SEL_CASE(8) MX_SEL_CASE(9) MX_SEL_CASE(10) MX_SEL_CASE(11)
+    MX_SEL_CASE(12) MX_SEL_CASE(13) MX_SEL_CASE(14) MX_SEL_CASE(15)
+#undef MX_SEL_CASE
+  }
+  return c;
+}
+
+template <int SHAPE, int FA, int FB>
+__global__ void __launch_bounds__(256)
+mx_scale_tile_kernel(const unsigned char* __restrict__ A, const unsigned char* __restrict__ B,
+                     const int* __restrict__ scale_a, const int* __restrict__ scale_b,
+                     float* __restrict__ C, int sel) {
+  typedef MxShape<SHAPE> S;
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int i = lane & (S::M - 1), g = lane >> S::LOG_M;
+  const i32x8 a = mx_pack<mx_bits(FA), S::G>(A + i * S::K, g, 1);
+  const i32x8 b = mx_pack<mx_bits(FB), S::G>(B + i, g, S::M);
+  const int sa = scale_a[i * S::G + g];
+  const int sb = scale_b[g * S::M + i];
+  typename S::acc acc;
+#pragma unroll
+  for (int r = 0; r < S::NREG; r++) acc[r] = 0.f;
+  acc = mx_mma_sel<SHAPE, FA, FB>(a, b, acc, sa, sb, sel);
+  float* out = C + (size_t)wave * (S::M * S::M);
+#pragma unroll
+  for (int r = 0; r < S::NREG; r++) out[S::row(r, g) * S::M + i] = acc[r];
+}
+
+// the (fmt_a, fmt_b) pairs the kernels are instantiated for, in both shapes
+constexpr int MX_PAIRS = 9;
+constexpr int MX_PAIR_FMT[MX_PAIRS][2] = {{0, 0}, {1, 1}, {2, 2}, {3, 3}, {4, 4},
+                                          {0, 4}, {4, 0}, {2, 1}, {3, 4}};
+
+// what both entry points require of the operands: uint8 on one device, the
+// shapes of `rows` stacked A tiles, codes inside each format's width, no NaN
+// scale byte, scale tables a lane can read as one dword
+static void mx_check_operands(const torch::Tensor& A, const torch::Tensor& B,
+                              const torch::Tensor& scale_a, const torch::Tensor& scale_b,
+                              long fmt_a, long fmt_b, long shape, long tiles) {
+  TORCH_CHECK(shape == 0 || shape == 1, "shape must be 0 (16x16x128) or 1 (32x32x64)");
+  TORCH_CHECK(fmt_a >= 0 && fmt_a <= 4 && fmt_b >= 0 && fmt_b <= 4,
+              "format codes are 0 e4m3, 1 e5m2, 2 e2m3, 3 e3m2, 4 e2m1");
+  const long M = shape == 0 ? 16 : 32, K = shape == 0 ? 128 : 64;
+  for (const torch::Tensor* t : {&A, &B, &scale_a, &scale_b}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == A.device(),
+                "A, B and the scales must be on one GPU");
+    TORCH_CHECK(t->dtype() == torch::kUInt8, "A, B and the scales must be uint8");
+  }
+  TORCH_CHECK(A.sizes() == torch::IntArrayRef({tiles * M, K}) &&
+                  B.sizes() == torch::IntArrayRef({K, M}) &&
+                  scale_a.sizes() == torch::IntArrayRef({tiles * M, K / 32, 4}) &&
+                  scale_b.sizes() == torch::IntArrayRef({K / 32, M, 4}),
+              "shapes must be A [", tiles * M, ",", K, "], B [", K, ",", M, "], scale_a [",
+              tiles * M, ",", K / 32, ",4], scale_b [", K / 32, ",", M, ",4]");
+  TORCH_CHECK(A.max().item<int>() < (1 << mx_bits((int)fmt_a)) &&
+                  B.max().item<int>() < (1 << mx_bits((int)fmt_b)),
+              "an operand holds a code outside its format's width");
+  TORCH_CHECK(scale_a.max().item<int>() < 255 && scale_b.max().item<int>() < 255,
+              "scale byte 255 is the E8M0 NaN");
+}
+
+static const int* mx_scale_words(const torch::Tensor& scale) {
+  auto p = reinterpret_cast<uintptr_t>(scale.data_ptr());
+  TORCH_CHECK(p % 4 == 0, "a scale table must be 4-byte aligned");
+  return reinterpret_cast<const int*>(p);
+}
+
+// A: [M,K], B: [K,M], scale_a: [M,K/32,4], scale_b: [K/32,M,4], all uint8.
+// shape 0: M=16, K=128; shape 1: M=32, K=64. Returns [waves, M, M] fp32 tiles.
+torch::Tensor mx_scale_tile(torch::Tensor A, torch::Tensor B, torch::Tensor scale_a,
+                            torch::Tensor scale_b, long fmt_a, long fmt_b, long shape,
+                            long sel_a, long sel_b, long blocks) {
+  mx_check_operands(A, B, scale_a, scale_b, fmt_a, fmt_b, shape, 1);
+  TORCH_CHECK(sel_a >= 0 && sel_a <= 3 && sel_b >= 0 && sel_b <= 3,
+              "sel_a/sel_b select one of the four scale bytes: 0..3");
+  TORCH_CHECK(blocks >= 1 && blocks <= (1L << 16), "blocks must be in [1, 2^16]");
+  int pair = -1;
+  for (int p = 0; p < MX_PAIRS; p++)
+    if (MX_PAIR_FMT[p][0] == fmt_a && MX_PAIR_FMT[p][1] == fmt_b) pair = p;
+  TORCH_CHECK(pair >= 0, "no kernel for the format pair (", fmt_a, ", ", fmt_b, ")");
+  A = A.contiguous();
+  B = B.contiguous();
+  scale_a = scale_a.contiguous();
+  scale_b = scale_b.contiguous();
+  const long M = shape == 0 ? 16 : 32;
+  auto C = torch::empty({blocks * 4, M, M},
+                        torch::TensorOptions().dtype(torch::kFloat32).device(A.device()));
+  const int* sa = mx_scale_words(scale_a);
+  const int* sb = mx_scale_words(scale_b);
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  dispatch_int<2 * MX_PAIRS>((int)shape * MX_PAIRS + pair, [&](auto which) {
+    constexpr int W = decltype(which)::value;
+    constexpr int SHAPE = W / MX_PAIRS, FA = MX_PAIR_FMT[W % MX_PAIRS][0],
+                  FB = MX_PAIR_FMT[W % MX_PAIRS][1];
+    hipLaunchKernelGGL((mx_scale_tile_kernel<SHAPE, FA, FB>), dim3(blocks), dim3(256), 0, stream,
+                       A.data_ptr<unsigned char>(), B.data_ptr<unsigned char>(), sa, sb,
+                       C.data_ptr<float>(), (int)(sel_a * 4 + sel_b));
+  });
+  HIP_CHECK(hipGetLastError());
+  return C;
+}
+
+// ---------------------------------------------------------------------------
+// MX scale burn: the protocol of mfma_burn (operands, scales and expected
+// bits in registers once, no memory traffic in the hot loop, one int4 record
+// per wave: {placement word, mismatched elements, first bad round, xor
+// checksum}; inject flips the lowest mantissa bit of acc[0][0] in registers)
+// with two differences: every lane carries its own four scale bytes, and
+// chain step c issues with op_sel = c & 3 on both sides, so sustained issue
+// rotates through the byte mux. The chain is unrolled by four (chain % 4 == 0).
+//
+// Exactness by construction: operands are integers in {-2..2}, scale bytes
+// lie in 127 + [-2, 2] per side, so every term is an integer of magnitude
+// <= 4 times 2^d, d in [-4, 4]: in units of 2^-4 a partial sum stays below
+// 4 * K * chain * 2^8, exact in fp32 while that is <= 2^24. The expected
+// tile is (chain / 4) * sum over sel of tile_sel.
+//
+// Four independent accumulators per wave in both shapes; they live in AGPRs.
+// gfx950 build, 256 threads per workgroup, no scratch in any instantiation:
+//   16x16x128: 99 VGPRs (e4m3), 90 (e2m3), 84 (e2m1) + 16 AGPRs, 4 waves/SIMD
+//   32x32x64:  195 VGPRs (e4m3), 185 (e2m3), 175 (e2m1) + 64 AGPRs, 1 wave per
+//              SIMD for e4m3 and 2 for the others, of the 512 registers a
+//              lane has; the four accumulators cover the MFMA's latency
+// ---------------------------------------------------------------------------
+constexpr int MXB_NACC = 4;
+constexpr int MXB_FORMATS = 3;
+constexpr int MXB_FMT[MXB_FORMATS] = {0, 2, 4};
+
+template <int SHAPE, int FMT>
+__global__ void __launch_bounds__(256)
+mx_scale_burn_kernel(const unsigned char* __restrict__ A, const unsigned char* __restrict__ B,
+                     const int* __restrict__ scale_a, const int* __restrict__ scale_b,
+                     const float* __restrict__ expected, int4* __restrict__ records, int chain,
+                     int rounds, int inject_wave, int inject_round) {
+  typedef MxShape<SHAPE> S;
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int i = lane & (S::M - 1), g = lane >> S::LOG_M;
+  const unsigned place = hw_word();
+
+  i32x8 a[MXB_NACC];
+  int sa[MXB_NACC];
+  unsigned want[MXB_NACC][S::NREG];
+#pragma unroll
+  for (int n = 0; n < MXB_NACC; n++) {
+    a[n] = mx_pack<mx_bits(FMT), S::G>(A + (n * S::M + i) * S::K, g, 1);
+    sa[n] = scale_a[(n * S::M + i) * S::G + g];
+#pragma unroll
+    for (int r = 0; r < S::NREG; r++)
+      want[n][r] = __float_as_uint(expected[(n * S::M + S::row(r, g)) * S::M + i]);
+  }
+  const i32x8 b = mx_pack<mx_bits(FMT), S::G>(B + i, g, S::M);
+  const int sb = scale_b[g * S::M + i];
+
+  const bool inject_here = (wave == inject_wave) && (lane == 0);
+  int mismatched = 0, first_bad = -1;
+  unsigned checksum = 0;
+  for (int round = 0; round < rounds; round++) {
+    typename S::acc acc[MXB_NACC];
+#pragma unroll
+    for (int n = 0; n < MXB_NACC; n++) {
+#pragma unroll
+      for (int r = 0; r < S::NREG; r++) acc[n][r] = 0.f;
+      // opaque to the optimiser: every round really recomputes its chain
+      asm volatile("" : "+v"(acc[n]));
+    }
+    for (int c = 0; c < chain; c += 4) {
+#pragma unroll
+      for (int n = 0; n < MXB_NACC; n++)
+        acc[n] = S::template mma<FMT, FMT, 0, 0>(a[n], b, acc[n], sa[n], sb);
+#pragma unroll
+      for (int n = 0; n < MXB_NACC; n++)
+        acc[n] = S::template mma<FMT, FMT, 1, 1>(a[n], b, acc[n], sa[n], sb);
+#pragma unroll
+      for (int n = 0; n < MXB_NACC; n++)
+        acc[n] = S::template mma<FMT, FMT, 2, 2>(a[n], b, acc[n], sa[n], sb);
+#pragma unroll
+      for (int n = 0; n < MXB_NACC; n++)
+        acc[n] = S::template mma<FMT, FMT, 3, 3>(a[n], b, acc[n], sa[n], sb);
+    }
+    if (inject_here && round == inject_round)
+      acc[0][0] = __uint_as_float(__float_as_uint(acc[0][0]) ^ 1u);
+    int bad = 0;
+#pragma unroll
+    for (int n = 0; n < MXB_NACC; n++) {
+#pragma unroll
+      for (int r = 0; r < S::NREG; r++) {
+        const unsigned bits = __float_as_uint(acc[n][r]);
+        bad += (bits != want[n][r]);
+        checksum ^= bits;
+      }
+    }
+    for (int off = 32; off > 0; off >>= 1) bad += __shfl_xor(bad, off);
+    mismatched += bad;
+    if (bad && first_bad < 0) first_bad = round;
+  }
+  checksum = wave_xor(checksum);
+  if (lane == 0) records[wave] = make_int4((int)place, mismatched, first_bad, (int)checksum);
+}
+
+// A: [4M,K], B: [K,M], scale_a: [4M,K/32,4], scale_b: [K/32,M,4] uint8, scale
+// bytes in 125..129; expected: [4,M,M] fp32 (= chain/4 * sum over sel of the
+// scaled A_n @ B). fmt 0 e4m3, 2 e2m3 or 4 e2m1 on both sides. One untimed
+// warm-up launch, then one timed launch (warm_then_timed_ms).
+// Returns (records [waves,4] int32, elapsed_ms of the timed launch).
+std::tuple<torch::Tensor, double> mx_scale_burn(torch::Tensor A, torch::Tensor B,
+                                                torch::Tensor scale_a, torch::Tensor scale_b,
+                                                torch::Tensor expected, long fmt, long shape,
+                                                long blocks, long chain, long rounds,
+                                                long inject_wave, long inject_round) {
+  mx_check_operands(A, B, scale_a, scale_b, fmt, fmt, shape, MXB_NACC);
+  int f = -1;
+  for (int k = 0; k < MXB_FORMATS; k++)
+    if (MXB_FMT[k] == fmt) f = k;
+  TORCH_CHECK(f >= 0, "the burn runs formats 0 (e4m3), 2 (e2m3) and 4 (e2m1); got ", fmt);
+  const long M = shape == 0 ? 16 : 32, K = shape == 0 ? 128 : 64;
+  TORCH_CHECK(expected.is_cuda() && expected.device() == A.device() &&
+                  expected.dtype() == torch::kFloat32 &&
+                  expected.sizes() == torch::IntArrayRef({MXB_NACC, M, M}),
+              "expected must be float32 [4,", M, ",", M, "] on the operands' GPU");
+  TORCH_CHECK(scale_a.min().item<int>() >= 125 && scale_a.max().item<int>() <= 129 &&
+                  scale_b.min().item<int>() >= 125 && scale_b.max().item<int>() <= 129,
+              "burn scale bytes must lie in 125..129");
+  TORCH_CHECK(blocks >= 1 && blocks <= (1L << 20), "blocks must be in [1, 2^20]");
+  TORCH_CHECK(chain >= 4 && chain % 4 == 0 && rounds >= 1,
+              "chain must be a positive multiple of 4 and rounds >= 1");
+  // |operand| <= 2 and scales 2^[-2,2] per side: a partial sum is an integer
+  // <= 4*K*chain*2^8 in units of 2^-4, exact in fp32 only up to 2^24
+  TORCH_CHECK(4 * K * chain * 256 <= (1L << 24), "chain ", chain,
+              " breaks fp32 exactness for K=", K, " (need 4*K*chain*2^8 <= 2^24)");
+  TORCH_CHECK(rounds <= (1L << 22) && chain * rounds <= (1L << 22),
+              "chain*rounds must be <= 2^22");
+  TORCH_CHECK(inject_wave >= -1 && inject_wave < blocks * 4 && inject_round >= -1 &&
+                  inject_round < rounds,
+              "inject_wave/inject_round out of range");
+  A = A.contiguous();
+  B = B.contiguous();
+  scale_a = scale_a.contiguous();
+  scale_b = scale_b.contiguous();
+  expected = expected.contiguous();
+  const int* sa = mx_scale_words(scale_a);
+  const int* sb = mx_scale_words(scale_b);
+  auto records = zero_records(blocks * 4, 4, A.device());
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  const double ms = warm_then_timed_ms(stream, [&]() {
+    dispatch_int<2 * MXB_FORMATS>((int)shape * MXB_FORMATS + f, [&](auto which) {
+      constexpr int W = decltype(which)::value;
+      hipLaunchKernelGGL((mx_scale_burn_kernel<W / MXB_FORMATS, MXB_FMT[W % MXB_FORMATS]>),
+                         dim3(blocks), dim3(256), 0, stream, A.data_ptr<unsigned char>(),
+                         B.data_ptr<unsigned char>(), sa, sb, expected.data_ptr<float>(),
                          reinterpret_cast<int4*>(records.data_ptr<int>()), (int)chain, (int)rounds,
                          (int)inject_wave, (int)inject_round);
     });
@@ -3505,6 +3875,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("inject_wave") = -1, py::arg("inject_round") = -1,
         "Sustained MFMA burn-in (fmt bf16|fp8|mx8|mx4): rounds x chain dependent MFMAs on 4 "
         "accumulators per wave, verified bitwise; returns (per-wave records [waves,4], ms)");
+  m.def("mx_scale_tile", &mx_scale_tile, py::arg("A"), py::arg("B"), py::arg("scale_a"),
+        py::arg("scale_b"), py::arg("fmt_a"), py::arg("fmt_b"), py::arg("shape"),
+        py::arg("sel_a") = 0, py::arg("sel_b") = 0, py::arg("blocks") = 2048,
+        "Per-wave MX block-scaled MFMA tile with per-lane E8M0 scales: formats 0 e4m3, 1 e5m2, "
+        "2 e2m3, 3 e3m2, 4 e2m1 (one code per byte), shape 0 = 16x16x128, 1 = 32x32x64, "
+        "sel_a/sel_b the scale byte each side reads; returns [waves, M, M] fp32");
+  m.def("mx_scale_burn", &mx_scale_burn, py::arg("A"), py::arg("B"), py::arg("scale_a"),
+        py::arg("scale_b"), py::arg("expected"), py::arg("fmt"), py::arg("shape"),
+        py::arg("blocks") = 2048, py::arg("chain") = 128, py::arg("rounds") = 256,
+        py::arg("inject_wave") = -1, py::arg("inject_round") = -1,
+        "Sustained MX block-scaled MFMA burn (fmt 0|2|4, shape 0|1) with per-lane scales and the "
+        "scale byte select rotating every step, verified bitwise; returns (per-wave records "
+        "[waves,4], ms)");
   m.def("p2p_gbps", &p2p_gbps, py::arg("src_dev"), py::arg("dst_dev"), py::arg("size_mb") = 256,
         py::arg("iters") = 10, "xGMI peer-to-peer copy bandwidth in GB/s");
   m.def("hbm_sweep", &hbm_sweep, py::arg("max_gib") = 16, py::arg("chunk_gib") = 4,
