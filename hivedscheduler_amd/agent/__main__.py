@@ -63,6 +63,12 @@ def main() -> None:
                          "deep sweeps); 0 = never")
     ap.add_argument("--mx-scale-probe", action="store_true",
                     help="with --local: also run the MX scale probe")
+    ap.add_argument("--mempath-probe-every", type=int, default=0,
+                    help="memory-path probe (buffer addressing and its bounds check, direct-to-LDS "
+                         "loads, sub-dword, d16 and wide forms, per CU) every N sweeps (on deep "
+                         "sweeps); 0 = never")
+    ap.add_argument("--mempath-probe", action="store_true",
+                    help="with --local: also run the memory-path probe")
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
@@ -80,7 +86,8 @@ def main() -> None:
                                      simd_probe=args.simd_probe,
                                      scalar_probe=args.scalar_probe,
                                      atomic_probe=args.atomic_probe,
-                                     mx_scale_probe=args.mx_scale_probe)
+                                     mx_scale_probe=args.mx_scale_probe,
+                                     mempath_probe=args.mempath_probe)
         if args.p2p_matrix:
             try:
                 m = p2p_link_matrix()
@@ -105,7 +112,8 @@ def main() -> None:
                             simd_probe_every=args.simd_probe_every,
                             scalar_probe_every=args.scalar_probe_every,
                             atomic_probe_every=args.atomic_probe_every,
-                            mx_scale_probe_every=args.mx_scale_probe_every)
+                            mx_scale_probe_every=args.mx_scale_probe_every,
+                            mempath_probe_every=args.mempath_probe_every)
     if args.once:
         import json
 

@@ -62,6 +62,7 @@ def collect_node_health(
     scalar_probe: bool = False,
     atomic_probe: bool = False,
     mx_scale_probe: bool = False,
+    mempath_probe: bool = False,
 ) -> dict:
     """One health sweep over all visible GPUs. deep=True also runs the HIP
     kernels (HBM + MFMA); sweep=True adds the 16 GiB HBM stuck-bit pattern
@@ -123,6 +124,13 @@ def collect_node_health(
     wave whose burn result was wrong, as xcc, se, sh, cu; a key of its own),
     and a failed probe marks the leaf bad.
 
+    mempath_probe=True (with deep) adds the memory-path probe (buffer
+    addressing and its bounds check, direct-to-LDS loads, the sub-dword, d16
+    and wide forms): per GPU it records `mempath_probe_ok`, `mempath_gbps`
+    ({section: GB/s}, reported, not judged) and `mempath_bad_cus` (the CUs of
+    any wave that read back wrong data, as xcc, se, sh, cu), and a failed
+    probe marks the leaf bad.
+
     The stuck-bit scan transiently holds up to 16 GiB of HBM; on a GPU
     running tenant jobs this can make the tenant's own allocations fail.
     Keep sweep on the low-frequency cadence and prefer idle GPUs (the
@@ -145,7 +153,8 @@ def collect_node_health(
 
         kwargs = _set_flags(burn=burn, lds_march=lds_march, hbm_march=hbm_march,
                             simd_probe=simd_probe, scalar_probe=scalar_probe,
-                            atomic_probe=atomic_probe, mx_scale_probe=mx_scale_probe)
+                            atomic_probe=atomic_probe, mx_scale_probe=mx_scale_probe,
+                            mempath_probe=mempath_probe)
         for i in range(n):
             gpu = report["gpus"][str(i)]
             try:
@@ -248,6 +257,17 @@ def collect_node_health(
                     )
                     if not p["ok"] or p["bad_cus"]:
                         gpu["healthy"] = False
+                if mempath_probe:
+                    p = rep["mempath_probe"]
+                    gpu.update(
+                        mempath_probe_ok=bool(p["ok"]),
+                        mempath_gbps={name: round(s["gbps"], 1)
+                                      for name, s in p["sections"].items()},
+                        mempath_bad_cus=[{k: c[k] for k in ("xcc", "se", "sh", "cu")}
+                                         for c in p["bad_cus"]],
+                    )
+                    if not p["ok"] or p["bad_cus"]:
+                        gpu["healthy"] = False
             except Exception as e:
                 gpu.update(healthy=False, error=str(e)[:200])
     if probe_pairs and n >= 2:
@@ -323,7 +343,8 @@ class NodeHealthAgent:
                  min_mfma_tflops: Optional[float] = None, lds_march_every: int = 0,
                  hbm_march_every: int = 0, min_xcd_ratio: Optional[float] = None,
                  simd_probe_every: int = 0, scalar_probe_every: int = 0,
-                 atomic_probe_every: int = 0, mx_scale_probe_every: int = 0):
+                 atomic_probe_every: int = 0, mx_scale_probe_every: int = 0,
+                 mempath_probe_every: int = 0):
         self.scheduler_url = scheduler_url.rstrip("/")
         self.node_name = node_name or socket.gethostname()
         self.interval_s = interval_s
@@ -367,6 +388,9 @@ class NodeHealthAgent:
         # pattern; 0 = never (about 0.2 s of matrix-core time per GPU, on
         # cores a tenant may be using)
         self.mx_scale_probe_every = mx_scale_probe_every
+        # memory-path probe cadence (buffer addressing, bounds check,
+        # direct-to-LDS, narrow and wide forms), same pattern; 0 = never
+        self.mempath_probe_every = mempath_probe_every
         self._rounds = 0
 
     def post_report(self, report: dict) -> bool:
@@ -425,7 +449,8 @@ class NodeHealthAgent:
                             simd_probe=deep and self._due(self.simd_probe_every),
                             scalar_probe=deep and self._due(self.scalar_probe_every),
                             atomic_probe=deep and self._due(self.atomic_probe_every),
-                            mx_scale_probe=deep and self._due(self.mx_scale_probe_every))
+                            mx_scale_probe=deep and self._due(self.mx_scale_probe_every),
+                            mempath_probe=deep and self._due(self.mempath_probe_every))
         self._rounds += 1
         if "burn" in kwargs:
             kwargs["min_mfma_tflops"] = self.min_mfma_tflops

@@ -5,7 +5,7 @@ extension is REQUIRED: failure to load raises (no silent eager fallback).
 
 Here: the loader, `gpu_health_report` and the single-tile MFMA checks. Each
 opt-in probe has a module of its own (mfma_burn, lds_march, hbm_march,
-simd_probe, scalar_probe, atomic_probe, mx_scale) on top of `records`, and the
+simd_probe, scalar_probe, atomic_probe, mx_scale, mempath_probe) on top of `records`, and the
 single-tile checks' operands and verdict are in mfma_tiles; their public names
 are re-exported here, and their report functions reach the extension through
 `_ops_on` below.
@@ -26,6 +26,9 @@ from .hbm_march import (HBM_MARCH_TILE_BYTES, hbm_march_pattern, hbm_march_repor
                         hbm_slow_xcds, summarize_hbm_march)
 from .lds_march import (LDS_MARCH_WORDS, lds_march_block_checksum, lds_march_pattern,  # noqa: F401
                         lds_march_report, summarize_lds_march)
+from .mempath_probe import (MEMPATH_SECTIONS, mempath_oob_cases, mempath_pattern,  # noqa: F401
+                            mempath_probe_report, mempath_section_report, mempath_steps,
+                            mempath_wave_checksum, summarize_mempath)
 from .mfma_tiles import (E4M3_GROUP_WINDOW_BITS, E4M3_NAN_CODES, TILE_FORMATS,  # noqa: F401
                          TILE_K, TILE_PROBE_SEEDS, _FP4_E2M1_VALUES, decode_tile_operand,
                          e4m3_values, e4m3_within_group_window, encode_tile_operand, exact_tile,
@@ -81,7 +84,7 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
                       bw_samples: int = 1, burn: bool = False, lds_march: bool = False,
                       hbm_march: bool = False, simd_probe: bool = False,
                       scalar_probe: bool = False, atomic_probe: bool = False,
-                      mx_scale_probe: bool = False) -> dict:
+                      mx_scale_probe: bool = False, mempath_probe: bool = False) -> dict:
     """Run the health-probe kernels on one GPU and return measured facts.
 
     Feeds leaf-cell healthiness: HBM bandwidth deficit, MFMA mismatch, or
@@ -134,6 +137,13 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     and as a burn of tens of milliseconds per format and shape) as
     report["mx_scale_probe"] and ANDs its verdict into `healthy`. Off by
     default, and the report is then unchanged.
+
+    mempath_probe=True adds the memory-path probe (`mempath_probe_report`:
+    buffer addressing in every width, the descriptor's bounds check,
+    direct-to-LDS loads and the sub-dword, d16 and wide forms: four timed
+    launches of about 7 ms together on an idle MI355X, each after a warm-up
+    launch of the same length) as report["mempath_probe"] and ANDs its verdict into
+    `healthy`. Off by default, and the report is then unchanged.
     """
     ops = _ops_on(device)
     size_mb = 256 if quick else 2048
@@ -200,6 +210,9 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     if mx_scale_probe:
         report["mx_scale_probe"] = mx_scale_probe_report(device)
         report["healthy"] = bool(report["healthy"] and report["mx_scale_probe"]["ok"])
+    if mempath_probe:
+        report["mempath_probe"] = mempath_probe_report(device)
+        report["healthy"] = bool(report["healthy"] and report["mempath_probe"]["ok"])
     return report
 
 

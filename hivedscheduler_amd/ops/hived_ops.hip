@@ -36,6 +36,10 @@
 //  - hbm_march:  a bounded span of HBM, both bit polarities, 16 B per lane,
 //                values unique across the sweep; the offset, bits and direction
 //                of any mismatch, and a bandwidth per XCD from device clocks
+//  - mempath_probe: buffer loads and stores in every width, the descriptor's
+//                bounds check at sharp lengths, direct-to-LDS loads and the
+//                sub-dword, d16 and wide forms, every value verified bitwise;
+//                the CU and instruction form of any mismatch
 //  - p2p copy:   xGMI link bandwidth between two GPUs (expected ~153 GB/s per
 //                link per direction); a degraded link marks the PAIR cell bad
 //
@@ -3835,6 +3839,967 @@ py::dict atomic_contend(const std::string& section, long seed, long blocks, long
   return d;
 }
 
+// ---------------------------------------------------------------------------
+// Memory-path probe: how production GEMM and attention kernels move tiles,
+// which no kernel above executes. Four sections, one kernel each (SEC):
+//   buf    raw buffer loads and stores in every width, the byte address split
+//          between voffset, soffset and the immediate differently per step,
+//          cross-checked against plain global stores and loads
+//   oob    the descriptor's hardware bounds check at sharp lengths: an access
+//          wholly in range returns the data, one wholly out returns 0 and its
+//          store is dropped
+//   lds    direct-to-LDS loads (global_load_lds_dword/x4, buffer_load_dword/x4
+//          ... lds), read back with ds_read_b128
+//   forms  the sub-dword, d16 and wide forms on the global and the LDS path
+//          that the marches leave out
+// All of it is data movement, so every result is exact and the host mirror
+// (ops/mempath_probe.py) states it bit for bit.
+//
+// Memory: one int32 row of MP_ROW_WORDS per wave, a slice of 3072 words the
+// wave fills and moves around and behind it a guard of 64 words whose every
+// byte is non-zero (MP_GUARD_SENTINEL). A wave only reads what it wrote
+// itself, after an agent-scope fence; no wave waits for another and every loop
+// bound is a launch argument. The value of word i in round r is
+//   v(i) = fmix32((seed + r*0x9E3779B9 + wave*0x7F4A7C15) ^ (i*0x85EBCA6B)),
+// complemented in odd rounds: a bijection in i, so an address alias reads back
+// as wrong data, and every bit travels each path holding 0 and holding 1.
+//
+// A section is a fixed list of steps (ops.mempath_steps names them); the
+// global step index is round*n_steps + step. Store steps write v ^ (step+1)*
+// 0x9E3779B9 and are read back through another form.
+//
+// Safety of the oob section: every address an instruction would form without
+// the check, base + voffset + soffset + imm + width, lies inside the wave's own
+// row (static_asserts below, asserted again per case by ops.mempath_oob_cases),
+// soffset is 0, and an access that straddles the length is never issued. A
+// wrong descriptor or a broken check reads a sentinel or dirties the guard,
+// which the step itself and the round's last step (the guard read with plain
+// loads) report; it cannot fault. Word 3 of the descriptor, 0x00020000, is
+// what Composable Kernel uses for raw buffers on the gfx9 family
+// (CK_BUFFER_RESOURCE_3RD_DWORD in ck/ck.hpp of the ROCm installation).
+//
+// Layout of a direct-to-LDS load, from the LLVM AMDGPU description of
+// llvm.amdgcn.global.load.lds / raw.ptr.buffer.load.lds (the LDS base goes to
+// M0, the immediate offset applies to the memory and the LDS address) and
+// ck_tile's async_buffer_load_dwordxn_v / amd_direct_load_global_to_lds: lane
+// l's N bytes land at M0 base + imm + l*N. The host mirror is written from
+// that, not from what the kernel returns. What an out-of-range lane of
+// `buffer_load_dword ... lds` does to LDS (writes 0 or leaves it) is recorded
+// in field [7] (1 = zero, 2 = left alone), not judged.
+//
+// Per wave, lane 0 writes one record of eight int32 (store_record8):
+//   [0] placement word (hw_word)
+//   [1] mismatched elements
+//   [2] first bad global step (-1 if none)
+//   [3] lowest bad byte offset within that step (-1 if none)
+//   [4] dropped mask, [5] raised mask, of the compared element zero-extended
+//   [6] sum mod 2^32 of every value compared in the even rounds
+//   [7] flags (lds section, see above; forms: the other half after a d16
+//       load, 1 kept, 2 zeroed, 4 neither), else 0
+//
+// inject_* (default -1 = off): in wave 0 of block inject_block, at global step
+// inject_step, lane 0 flips bit inject_bit of the element at byte offset
+// inject_offset of what the step is about to read: the slice (flipped back
+// after a load step, so later steps see clean data), the read-back target of a
+// store step after the store, the LDS region after a direct load. A plain
+// store into the wave's own memory. In the oob section injection instead
+// lengthens the descriptor of all four waves of the block so that the first
+// wholly-out access of that step is in range: it returns (or overwrites, and
+// the step restores) slice or guard data inside the row.
+//
+// Checked in the gfx950 disassembly: each step issues the form it is named
+// after, with one exception: of the four signed sub-dword loads of a batch
+// that the builtins and plain C++ produce (buffer_load_sbyte/sshort,
+// global_load_sbyte/sshort, ds_read_i8/i16) the compiler emits one as the
+// unsigned load and a v_bfe_i32, so both appear in those steps. The compiler
+// merges neighbouring accesses and splits wide ones; the empty asm with a
+// memory clobber after an access keeps it single, as in the LDS march, and
+// the d16, wide LDS and read2/write2 forms are inline asm. The new code has
+// no floating-point arithmetic. gfx950 build: buf 121, oob 44, lds 62 and
+// forms 70 VGPRs, no scratch; lds and forms hold 64 KiB of LDS, so
+// two of their workgroups fit a CU.
+// ---------------------------------------------------------------------------
+constexpr int MP_SLICE_WORDS = 3072;  // 64 lanes x 12 B and 64 x 16 B divide it
+constexpr int MP_GUARD_WORDS = 64;
+constexpr int MP_ROW_WORDS = MP_SLICE_WORDS + MP_GUARD_WORDS;
+constexpr int MP_SLICE_BYTES = 4 * MP_SLICE_WORDS;
+constexpr int MP_ROW_BYTES = 4 * MP_ROW_WORDS;
+constexpr int MP_LDS_WAVE_WORDS = 4096;  // 16 KiB of the 64 KiB per wave
+constexpr unsigned MP_GUARD_SENTINEL = 0xC3A5E17Bu;  // every byte non-zero
+constexpr unsigned MP_LDS_SENTINEL = 0x5AA5C33Cu;
+constexpr unsigned MP_OOB_MARKER = 0xD1B2E4F7u;
+constexpr unsigned MP_D16_CANARY = 0x9C6A3B57u;  // preset in a d16 load's register
+constexpr int MP_RSRC_WORD3 = 0x00020000;
+enum { MP_BUF = 0, MP_OOB, MP_LDS, MP_FORMS, MP_SECTIONS };
+constexpr int MP_STEPS[MP_SECTIONS] = {14, 61, 5, 39};
+// oob: lanes 0..15 access offsets lo + lane*W in a window across the length L
+__host__ __device__ constexpr int mp_oob_length(int li) {
+  return li == 0 ? MP_SLICE_BYTES : li == 1 ? MP_SLICE_BYTES - 1 : li == 2 ? MP_SLICE_BYTES - 3
+                                                                 : li == 3 ? 4 : 0;
+}
+constexpr int MP_OOB_LANES = 16;
+constexpr int MP_OOB_MAX_WIDTH = 16;
+__host__ __device__ constexpr int mp_oob_lo(int L, int W) {
+  return L / W * W - (MP_OOB_LANES / 2) * W < 0 ? 0 : L / W * W - (MP_OOB_LANES / 2) * W;
+}
+__host__ __device__ constexpr int mp_oob_first_out(int L, int W) { return (L + W - 1) / W * W; }
+static_assert(mp_oob_lo(MP_SLICE_BYTES, MP_OOB_MAX_WIDTH) + MP_OOB_LANES * MP_OOB_MAX_WIDTH <=
+                      MP_ROW_BYTES &&
+                  mp_oob_lo(MP_SLICE_BYTES, 12) + MP_OOB_LANES * 12 <= MP_ROW_BYTES,
+              "every oob window must end inside the row");
+static_assert(MP_ROW_BYTES % 16 == 0 && MP_SLICE_BYTES % (64 * 12) == 0 &&
+                  MP_SLICE_BYTES % (4 * 64 * 16) == 0,
+              "rows stay 16 B aligned and every width tiles the slice in batches of four");
+// lds: where in the wave's 16 KiB each step's copy of the slice starts (bytes)
+__host__ __device__ constexpr int mp_lds_dst(int step) {
+  constexpr int dst[5] = {0, 4096, 2048, 16, 512};
+  return dst[step];
+}
+constexpr int MP_LDS_OOB_INRANGE = 32;  // lanes of the last step the descriptor covers
+
+typedef unsigned mp_u2 __attribute__((ext_vector_type(2)));
+typedef unsigned mp_u3 __attribute__((ext_vector_type(3)));
+typedef unsigned mp_u4 __attribute__((ext_vector_type(4)));
+#define MP_LDS_AS __attribute__((address_space(3)))
+
+struct MpPat {
+  unsigned rs, inv;
+  __device__ __forceinline__ unsigned word(int i) const {
+    return fmix32(rs ^ ((unsigned)i * 0x85EBCA6Bu)) ^ inv;
+  }
+  // the row as it must stand: the slice, then the guard
+  __device__ __forceinline__ unsigned row_word(int i) const {
+    return i < MP_SLICE_WORDS ? word(i) : MP_GUARD_SENTINEL;
+  }
+};
+
+// the E-byte element at byte offset `off` of a word, zero- or sign-extended
+template <int E, bool SIGNED>
+__device__ __forceinline__ unsigned mp_elem(unsigned word, int off) {
+  if constexpr (E == 1) {
+    const unsigned b = (word >> ((off & 3) * 8)) & 0xFFu;
+    return SIGNED ? (unsigned)(int)(signed char)b : b;
+  } else if constexpr (E == 2) {
+    const unsigned h = (word >> ((off & 2) * 8)) & 0xFFFFu;
+    return SIGNED ? (unsigned)(int)(short)h : h;
+  } else {
+    return word;
+  }
+}
+template <int W> constexpr int mp_elem_bytes() { return W < 4 ? W : 4; }
+template <int W> constexpr unsigned mp_elem_mask() {
+  return W == 1 ? 0xFFu : W == 2 ? 0xFFFFu : 0xFFFFFFFFu;
+}
+
+struct MpState {
+  int mismatched, first_step, first_off;
+  unsigned dropped, raised, checksum, sum_mask, flags;
+};
+
+__device__ __forceinline__ void mp_compare(MpState& s, unsigned got, unsigned want, unsigned emask,
+                                           int gstep, int off) {
+  const unsigned diff = got ^ want;
+  const bool bad = diff != 0;
+  const bool first = bad && (s.first_step < 0 || (s.first_step == gstep && off < s.first_off));
+  s.mismatched += bad;
+  s.dropped |= want & diff & emask;
+  s.raised |= got & diff & emask;
+  s.checksum += got & s.sum_mask;
+  s.first_step = first ? gstep : s.first_step;
+  s.first_off = first ? off : s.first_off;
+}
+
+// the wave's stores have reached memory and its next loads see them
+__device__ __forceinline__ void mp_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+}
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t mp_rsrc(const unsigned* base, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned*>(base), 0, bytes, MP_RSRC_WORD3);
+}
+
+template <int W, bool SIGNED>
+__device__ __forceinline__ void mp_buf_load(unsigned (&out)[4], __amdgpu_buffer_rsrc_t r, int voff,
+                                            int soff) {
+  if constexpr (W == 1) {
+    const unsigned char b = __builtin_amdgcn_raw_buffer_load_b8(r, voff, soff, 0);
+    out[0] = SIGNED ? (unsigned)(int)(signed char)b : (unsigned)b;
+  } else if constexpr (W == 2) {
+    const unsigned short h = __builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, 0);
+    out[0] = SIGNED ? (unsigned)(int)(short)h : (unsigned)h;
+  } else if constexpr (W == 4) {
+    out[0] = __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0);
+  } else if constexpr (W == 8) {
+    const mp_u2 v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
+    out[0] = v.x, out[1] = v.y;
+  } else if constexpr (W == 12) {
+    const mp_u3 v = __builtin_amdgcn_raw_buffer_load_b96(r, voff, soff, 0);
+    out[0] = v.x, out[1] = v.y, out[2] = v.z;
+  } else {
+    const mp_u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
+    out[0] = v.x, out[1] = v.y, out[2] = v.z, out[3] = v.w;
+  }
+  asm volatile("" ::: "memory");
+}
+
+template <int W>
+__device__ __forceinline__ void mp_buf_store(const unsigned (&d)[4], __amdgpu_buffer_rsrc_t r,
+                                             int voff, int soff) {
+  if constexpr (W == 1) {
+    __builtin_amdgcn_raw_buffer_store_b8((unsigned char)d[0], r, voff, soff, 0);
+  } else if constexpr (W == 2) {
+    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)d[0], r, voff, soff, 0);
+  } else if constexpr (W == 4) {
+    __builtin_amdgcn_raw_buffer_store_b32(d[0], r, voff, soff, 0);
+  } else if constexpr (W == 8) {
+    __builtin_amdgcn_raw_buffer_store_b64(mp_u2{d[0], d[1]}, r, voff, soff, 0);
+  } else if constexpr (W == 12) {
+    __builtin_amdgcn_raw_buffer_store_b96(mp_u3{d[0], d[1], d[2]}, r, voff, soff, 0);
+  } else {
+    __builtin_amdgcn_raw_buffer_store_b128(mp_u4{d[0], d[1], d[2], d[3]}, r, voff, soff, 0);
+  }
+  asm volatile("" ::: "memory");
+}
+
+// W bytes at byte offset o of the row through plain typed loads and stores
+template <int W>
+__device__ __forceinline__ void mp_plain_load(unsigned (&out)[4], const unsigned* row, int o) {
+  if constexpr (W == 1) {
+    out[0] = reinterpret_cast<const unsigned char*>(row)[o];
+  } else if constexpr (W == 2) {
+    out[0] = reinterpret_cast<const unsigned short*>(row)[o >> 1];
+  } else {
+#pragma unroll
+    for (int c = 0; c < W / 4; c++) out[c] = row[(o >> 2) + c];
+  }
+  asm volatile("" ::: "memory");
+}
+template <int W>
+__device__ __forceinline__ void mp_plain_store(unsigned* row, int o, const unsigned (&d)[4]) {
+  if constexpr (W == 1) {
+    reinterpret_cast<unsigned char*>(row)[o] = (unsigned char)d[0];
+  } else if constexpr (W == 2) {
+    reinterpret_cast<unsigned short*>(row)[o >> 1] = (unsigned short)d[0];
+  } else {
+#pragma unroll
+    for (int c = 0; c < W / 4; c++) row[(o >> 2) + c] = d[c];
+  }
+  asm volatile("" ::: "memory");
+}
+
+// the slice := v ^ x, with global_store_dwordx4
+__device__ __forceinline__ void mp_fill_slice(unsigned* row, const MpPat& p, unsigned x, int lane) {
+  uint4* q = reinterpret_cast<uint4*>(row);
+  for (int k = lane; k < MP_SLICE_WORDS / 4; k += 64)
+    q[k] = make_uint4(p.word(4 * k) ^ x, p.word(4 * k + 1) ^ x, p.word(4 * k + 2) ^ x,
+                      p.word(4 * k + 3) ^ x);
+  mp_fence();
+}
+
+// the slice against v ^ x, with global_load_dword
+__device__ __forceinline__ void mp_check_slice(MpState& s, const unsigned* row, const MpPat& p,
+                                               unsigned x, int gstep, int lane) {
+  for (int k = lane; k < MP_SLICE_WORDS; k += 64) {
+    const unsigned got = row[k];
+    asm volatile("" ::: "memory");
+    mp_compare(s, got, p.word(k) ^ x, 0xFFFFFFFFu, gstep, 4 * k);
+  }
+}
+
+// lane 0 flips one bit of its wave's own row (wave-uniform `here`)
+__device__ __forceinline__ void mp_flip_global(unsigned* row, bool here, int off, int bit,
+                                               int lane) {
+  if (here) {
+    if (lane == 0) row[off >> 2] ^= 1u << (((off & 3) << 3) + bit);
+    mp_fence();
+  }
+}
+__device__ __forceinline__ void mp_flip_lds(unsigned* region, bool here, int off, int bit,
+                                            int lane) {
+  if (here) {
+    if (lane == 0) region[off >> 2] ^= 1u << (((off & 3) << 3) + bit);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  }
+}
+
+// Byte offset of access k of a lane when W-byte accesses tile the slice lane
+// by lane, in batches of four: outer is wave-uniform, inner a compile-time
+// constant that can become the instruction's immediate.
+// SPLIT 0: voffset = lane*W + inner (imm), soffset = outer
+// SPLIT 1: voffset = outer + lane*W + inner (imm), soffset = 0
+// SPLIT 2: voffset = lane*W, soffset = outer + inner
+template <int W, int SPLIT>
+__device__ __forceinline__ void mp_split(int outer, int inner, int lane, int& voff, int& soff) {
+  voff = SPLIT == 0 ? lane * W + inner : SPLIT == 1 ? outer + lane * W + inner : lane * W;
+  soff = SPLIT == 0 ? outer : SPLIT == 1 ? 0 : outer + inner;
+}
+
+template <int W, bool SIGNED, int SPLIT>
+__device__ __forceinline__ void mp_buf_load_step(MpState& s, __amdgpu_buffer_rsrc_t r,
+                                                 const MpPat& p, int gstep, int lane) {
+  constexpr int PER = MP_SLICE_BYTES / (64 * W);
+  constexpr int E = mp_elem_bytes<W>();
+#pragma unroll 1
+  for (int k0 = 0; k0 < PER; k0 += 4) {
+    unsigned got[4][4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      int voff, soff;
+      mp_split<W, SPLIT>(k0 * 64 * W, u * 64 * W, lane, voff, soff);
+      mp_buf_load<W, SIGNED>(got[u], r, voff, soff);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int off = (k0 + u) * 64 * W + lane * W;
+#pragma unroll
+      for (int c = 0; c < W / E; c++)
+        mp_compare(s, got[u][c], mp_elem<E, SIGNED>(p.word((off >> 2) + c), off),
+                   mp_elem_mask<W>(), gstep, off + 4 * c);
+    }
+  }
+}
+
+template <int W, int SPLIT>
+__device__ __forceinline__ void mp_buf_store_step(__amdgpu_buffer_rsrc_t r, const MpPat& p,
+                                                  unsigned x, int lane) {
+  constexpr int PER = MP_SLICE_BYTES / (64 * W);
+  constexpr int E = mp_elem_bytes<W>();
+#pragma unroll 1
+  for (int k0 = 0; k0 < PER; k0 += 4) {
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int off = (k0 + u) * 64 * W + lane * W;
+      unsigned d[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int c = 0; c < W / E; c++) d[c] = mp_elem<E, false>(p.word((off >> 2) + c) ^ x, off);
+      int voff, soff;
+      mp_split<W, SPLIT>(k0 * 64 * W, u * 64 * W, lane, voff, soff);
+      mp_buf_store<W>(d, r, voff, soff);
+    }
+  }
+}
+
+struct MpInject {
+  bool block_here, wave_here;  // the injected block; its wave 0
+  int step, offset, bit;
+};
+
+// --- section buf ---
+__device__ __forceinline__ void mp_section_buf(MpState& s, unsigned* row, const MpPat& p,
+                                               int gbase, const MpInject& inj, int lane) {
+  const __amdgpu_buffer_rsrc_t r = mp_rsrc(row, MP_SLICE_BYTES);
+  mp_fill_slice(row, p, 0u, lane);
+#define MP_BUF_LOAD(STEP, W, SIGNED, SPLIT)                                    \
+  {                                                                            \
+    const bool here = inj.wave_here && inj.step == gbase + (STEP);             \
+    mp_flip_global(row, here, inj.offset, inj.bit, lane);                      \
+    mp_buf_load_step<W, SIGNED, SPLIT>(s, r, p, gbase + (STEP), lane);         \
+    mp_flip_global(row, here, inj.offset, inj.bit, lane);                      \
+  }
+  MP_BUF_LOAD(0, 1, false, 0)
+  MP_BUF_LOAD(1, 1, true, 1)
+  MP_BUF_LOAD(2, 2, false, 2)
+  MP_BUF_LOAD(3, 2, true, 0)
+  MP_BUF_LOAD(4, 4, false, 1)
+  MP_BUF_LOAD(5, 8, false, 2)
+  MP_BUF_LOAD(6, 12, false, 0)
+  MP_BUF_LOAD(7, 16, false, 1)
+#undef MP_BUF_LOAD
+#define MP_BUF_STORE(STEP, W, SPLIT)                                                         \
+  {                                                                                          \
+    const unsigned x = (unsigned)((STEP) + 1) * 0x9E3779B9u;                                 \
+    mp_buf_store_step<W, SPLIT>(r, p, x, lane);                                              \
+    mp_fence();                                                                              \
+    mp_flip_global(row, inj.wave_here && inj.step == gbase + (STEP), inj.offset, inj.bit, lane); \
+    mp_check_slice(s, row, p, x, gbase + (STEP), lane);                                      \
+  }
+  MP_BUF_STORE(8, 1, 1)
+  MP_BUF_STORE(9, 2, 0)
+  MP_BUF_STORE(10, 4, 2)
+  MP_BUF_STORE(11, 8, 1)
+  MP_BUF_STORE(12, 12, 2)
+  MP_BUF_STORE(13, 16, 0)
+#undef MP_BUF_STORE
+}
+
+// --- section oob ---
+template <int W>
+__device__ __forceinline__ void mp_oob_load_step(MpState& s, const unsigned* row, const MpPat& p,
+                                                 int L, bool lengthen, int gstep, int lane) {
+  constexpr int E = mp_elem_bytes<W>();
+  const __amdgpu_buffer_rsrc_t r = mp_rsrc(row, lengthen ? mp_oob_first_out(L, W) + W : L);
+  const int o = mp_oob_lo(L, W) + lane * W;
+  const bool in = o + W <= L, out = o >= L;
+  if (lane < MP_OOB_LANES && (in || out)) {  // a straddling access is never issued
+    unsigned got[4];
+    mp_buf_load<W, false>(got, r, o, 0);
+#pragma unroll
+    for (int c = 0; c < W / E; c++)
+      mp_compare(s, got[c], in ? mp_elem<E, false>(p.word((o >> 2) + c), o) : 0u,
+                 mp_elem_mask<W>(), gstep, o + 4 * c);
+  }
+}
+
+template <int W>
+__device__ __forceinline__ void mp_oob_store_step(MpState& s, unsigned* row, const MpPat& p, int L,
+                                                  bool lengthen, int step, int gstep, int lane) {
+  constexpr int E = mp_elem_bytes<W>();
+  const __amdgpu_buffer_rsrc_t r = mp_rsrc(row, lengthen ? mp_oob_first_out(L, W) + W : L);
+  const unsigned x = (unsigned)(step + 1) * 0x9E3779B9u;
+  const int o = mp_oob_lo(L, W) + lane * W;
+  const bool in = o + W <= L, out = o >= L;
+  const bool active = lane < MP_OOB_LANES && (in || out);
+  unsigned was[4] = {0u, 0u, 0u, 0u}, want[4] = {0u, 0u, 0u, 0u};
+  if (active) {
+    unsigned d[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int c = 0; c < W / E; c++) {
+      was[c] = mp_elem<E, false>(p.row_word((o >> 2) + c), o);
+      // in range: the neighbours must land; out of range: a marker that must not
+      d[c] = in ? mp_elem<E, false>(p.word((o >> 2) + c) ^ x, o)
+                : mp_elem<E, false>(MP_OOB_MARKER, o);
+      want[c] = in ? d[c] : was[c];
+    }
+    mp_buf_store<W>(d, r, o, 0);
+  }
+  mp_fence();
+  if (active) {
+    unsigned got[4];
+    mp_plain_load<W>(got, row, o);
+#pragma unroll
+    for (int c = 0; c < W / E; c++)
+      mp_compare(s, got[c], want[c], mp_elem_mask<W>(), gstep, o + 4 * c);
+    mp_plain_store<W>(row, o, was);  // the row as it stood
+  }
+  mp_fence();
+}
+
+__device__ __forceinline__ void mp_section_oob(MpState& s, unsigned* row, const MpPat& p,
+                                               int gbase, const MpInject& inj, int lane) {
+  mp_fill_slice(row, p, 0u, lane);
+  for (int li = 0; li < 5; li++) {
+    const int L = mp_oob_length(li);
+    const int step0 = li * 12;
+#define MP_OOB_PAIR(K, W)                                                                  \
+  mp_oob_load_step<W>(s, row, p, L, inj.block_here && inj.step == gbase + step0 + (K),     \
+                      gbase + step0 + (K), lane);                                          \
+  mp_oob_store_step<W>(s, row, p, L, inj.block_here && inj.step == gbase + step0 + 6 + (K), \
+                       step0 + 6 + (K), gbase + step0 + 6 + (K), lane);
+    MP_OOB_PAIR(0, 1)
+    MP_OOB_PAIR(1, 2)
+    MP_OOB_PAIR(2, 4)
+    MP_OOB_PAIR(3, 8)
+    MP_OOB_PAIR(4, 12)
+    MP_OOB_PAIR(5, 16)
+#undef MP_OOB_PAIR
+  }
+  // the guard, with plain loads: no out-of-range store may have reached it
+  const unsigned got = row[MP_SLICE_WORDS + lane];
+  asm volatile("" ::: "memory");
+  mp_compare(s, got, MP_GUARD_SENTINEL, 0xFFFFFFFFu, gbase + 60, MP_SLICE_BYTES + 4 * lane);
+}
+
+// --- section lds ---
+// N bytes per lane; BUF: through the descriptor, else global_load_lds. With
+// oob_lanes > 0 a single issue whose descriptor covers only the lanes below.
+template <int N, bool BUF>
+__device__ __forceinline__ void mp_lds_step(MpState& s, unsigned* region, const unsigned* row,
+                                            const MpPat& p, int dst, int inrange, int gstep,
+                                            const MpInject& inj, int lane) {
+  uint4* q = reinterpret_cast<uint4*>(region);
+  for (int k = lane; k < MP_LDS_WAVE_WORDS / 4; k += 64)
+    q[k] = make_uint4(MP_LDS_SENTINEL, MP_LDS_SENTINEL, MP_LDS_SENTINEL, MP_LDS_SENTINEL);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  MP_LDS_AS unsigned* to = (MP_LDS_AS unsigned*)region + dst / 4;
+  int moved = MP_SLICE_WORDS;
+  if (inrange > 0) {
+    // addresses stay inside the row; lanes >= inrange are beyond the length
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(mp_rsrc(row, 4 * inrange), to, 4, lane * 4, 0, 0, 0);
+    moved = 64;
+  } else {
+    constexpr int CHUNK = 64 * N;
+    const __amdgpu_buffer_rsrc_t r = mp_rsrc(row, MP_SLICE_BYTES);
+#pragma unroll 1
+    for (int k0 = 0; k0 < MP_SLICE_BYTES / CHUNK; k0 += 4) {
+      MP_LDS_AS unsigned* to_k = to + k0 * (CHUNK / 4);  // wave-uniform: goes to M0
+      const int voff = k0 * CHUNK + lane * N;
+      const auto* from =
+          (__attribute__((address_space(1))) const unsigned*)(row + (k0 * CHUNK + lane * N) / 4);
+      // the size and the immediate must be literals for the builtins
+#define MP_LDS_ISSUE(SIZE, IMM)                                                   \
+  if constexpr (BUF)                                                              \
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, to_k, SIZE, voff, 0, IMM, 0);     \
+  else                                                                            \
+    __builtin_amdgcn_global_load_lds(from, to_k, SIZE, IMM, 0);
+#define MP_LDS_ISSUE4(SIZE)                                                       \
+  MP_LDS_ISSUE(SIZE, 0)                                                           \
+  MP_LDS_ISSUE(SIZE, 64 * SIZE) MP_LDS_ISSUE(SIZE, 128 * SIZE) MP_LDS_ISSUE(SIZE, 192 * SIZE)
+      if constexpr (N == 4) {
+        MP_LDS_ISSUE4(4)
+      } else if constexpr (N == 12) {
+        MP_LDS_ISSUE4(12)
+      } else {
+        MP_LDS_ISSUE4(16)
+      }
+#undef MP_LDS_ISSUE4
+#undef MP_LDS_ISSUE
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  mp_flip_lds(region, inj.wave_here && inj.step == gstep, inj.offset, inj.bit, lane);
+  for (int k = lane; k < MP_LDS_WAVE_WORDS / 4; k += 64) {
+    const uint4 v = q[k];
+    const unsigned got[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      const int i = 4 * k + c - dst / 4;  // the slice word that belongs here
+      if (inrange > 0 && i >= inrange && i < moved) {
+        // unknown: 0 written or the sentinel left; anything else is a mismatch
+        if (got[c] == 0u) s.flags |= 1u;
+        else if (got[c] == MP_LDS_SENTINEL) s.flags |= 2u;
+        else mp_compare(s, got[c], MP_LDS_SENTINEL, 0xFFFFFFFFu, gstep, 16 * k + 4 * c);
+      } else {
+        const bool copied = i >= 0 && i < (inrange > 0 ? inrange : moved);
+        mp_compare(s, got[c], copied ? p.word(i) : MP_LDS_SENTINEL, 0xFFFFFFFFu, gstep,
+                   16 * k + 4 * c);
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ void mp_section_lds(MpState& s, unsigned* region, unsigned* row,
+                                               const MpPat& p, int gbase, const MpInject& inj,
+                                               int lane) {
+  mp_fill_slice(row, p, 0u, lane);
+  // no dwordx3 step: measured on an MI355X, lane l's 12 bytes do not land at
+  // base + l*12 (BENCHMARKS.md "Memory-path probe"), and no description of
+  // another layout is at hand to write a mirror from
+  mp_lds_step<4, false>(s, region, row, p, mp_lds_dst(0), 0, gbase + 0, inj, lane);
+  mp_lds_step<16, false>(s, region, row, p, mp_lds_dst(1), 0, gbase + 1, inj, lane);
+  mp_lds_step<4, true>(s, region, row, p, mp_lds_dst(2), 0, gbase + 2, inj, lane);
+  mp_lds_step<16, true>(s, region, row, p, mp_lds_dst(3), 0, gbase + 3, inj, lane);
+  mp_lds_step<4, true>(s, region, row, p, mp_lds_dst(4), MP_LDS_OOB_INRANGE, gbase + 4, inj, lane);
+}
+
+// --- section forms ---
+// A d16 load writes one half of its register. Four loads per asm, the register
+// preset to a canary; the loaded half is compared, and whether the other half
+// survived is recorded in field [7], not judged: LLVM documents that the unused
+// bits are not preserved where SRAM ECC is on (d16PreservesUnusedBits), as on
+// the MI355X, where they read back zero.
+#define MP_D16_LOAD4(INSTR, ADDR, SFX, STRIDE, R)                                         \
+  asm volatile(INSTR " %0, %4" SFX " offset:0\n\t" INSTR " %1, %4" SFX " offset:%5\n\t"  \
+               INSTR " %2, %4" SFX " offset:%6\n\t" INSTR " %3, %4" SFX " offset:%7\n\t" \
+               "s_waitcnt vmcnt(0) lgkmcnt(0)"                                            \
+               : "+v"(R[0]), "+v"(R[1]), "+v"(R[2]), "+v"(R[3])                           \
+               : "v"(ADDR), "n"(STRIDE), "n"(2 * (STRIDE)), "n"(3 * (STRIDE))             \
+               : "memory")
+#define MP_D16_STORE4(INSTR, ADDR, SFX, STRIDE, R)                                        \
+  asm volatile(INSTR " %4, %0" SFX " offset:0\n\t" INSTR " %4, %1" SFX " offset:%5\n\t"  \
+               INSTR " %4, %2" SFX " offset:%6\n\t" INSTR " %4, %3" SFX " offset:%7"    \
+               :                                                                          \
+               : "v"(R[0]), "v"(R[1]), "v"(R[2]), "v"(R[3]), "v"(ADDR), "n"(STRIDE),      \
+                 "n"(2 * (STRIDE)), "n"(3 * (STRIDE))                                     \
+               : "memory")
+
+enum { MP_F_PLAIN = 0, MP_F_D16, MP_F_D16_HI };
+
+// One pass over the 12288 B at `base` (the slice, or the wave's LDS region) in
+// E-byte elements, lane by lane, four per batch; FORM says how each is loaded.
+template <bool LDS, int E, bool SIGNED, int FORM>
+__device__ __forceinline__ void mp_narrow_load_step(MpState& s, const unsigned* base,
+                                                    const MpPat& p, int gstep, int lane) {
+  constexpr int PER = MP_SLICE_BYTES / (64 * E);
+  constexpr int STRIDE = 64 * E;
+  const unsigned char* bytes = reinterpret_cast<const unsigned char*>(base);
+#pragma unroll 1
+  for (int k0 = 0; k0 < PER; k0 += 4) {
+    const int off0 = k0 * STRIDE + lane * E;
+    unsigned got[4] = {MP_D16_CANARY, MP_D16_CANARY, MP_D16_CANARY, MP_D16_CANARY};
+    if constexpr (FORM == MP_F_PLAIN) {
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const unsigned char* a = bytes + off0 + u * STRIDE;
+        if constexpr (E == 1)
+          got[u] = SIGNED ? (unsigned)(int)*reinterpret_cast<const signed char*>(a) : (unsigned)*a;
+        else
+          got[u] = SIGNED ? (unsigned)(int)*reinterpret_cast<const short*>(a)
+                          : (unsigned)*reinterpret_cast<const unsigned short*>(a);
+        asm volatile("" ::: "memory");
+      }
+    } else if constexpr (LDS) {
+      const unsigned a = (unsigned)(size_t)(MP_LDS_AS const unsigned char*)(bytes + off0);
+      if constexpr (E == 1 && !SIGNED && FORM == MP_F_D16) MP_D16_LOAD4("ds_read_u8_d16", a, "", STRIDE, got);
+      if constexpr (E == 1 && !SIGNED && FORM == MP_F_D16_HI) MP_D16_LOAD4("ds_read_u8_d16_hi", a, "", STRIDE, got);
+      if constexpr (E == 1 && SIGNED && FORM == MP_F_D16) MP_D16_LOAD4("ds_read_i8_d16", a, "", STRIDE, got);
+      if constexpr (E == 1 && SIGNED && FORM == MP_F_D16_HI) MP_D16_LOAD4("ds_read_i8_d16_hi", a, "", STRIDE, got);
+      if constexpr (E == 2 && FORM == MP_F_D16) MP_D16_LOAD4("ds_read_u16_d16", a, "", STRIDE, got);
+      if constexpr (E == 2 && FORM == MP_F_D16_HI) MP_D16_LOAD4("ds_read_u16_d16_hi", a, "", STRIDE, got);
+    } else {
+      const unsigned char* a = bytes + off0;
+      if constexpr (E == 1 && !SIGNED && FORM == MP_F_D16) MP_D16_LOAD4("global_load_ubyte_d16", a, ", off", STRIDE, got);
+      if constexpr (E == 1 && !SIGNED && FORM == MP_F_D16_HI) MP_D16_LOAD4("global_load_ubyte_d16_hi", a, ", off", STRIDE, got);
+      if constexpr (E == 1 && SIGNED && FORM == MP_F_D16) MP_D16_LOAD4("global_load_sbyte_d16", a, ", off", STRIDE, got);
+      if constexpr (E == 1 && SIGNED && FORM == MP_F_D16_HI) MP_D16_LOAD4("global_load_sbyte_d16_hi", a, ", off", STRIDE, got);
+      if constexpr (E == 2 && FORM == MP_F_D16) MP_D16_LOAD4("global_load_short_d16", a, ", off", STRIDE, got);
+      if constexpr (E == 2 && FORM == MP_F_D16_HI) MP_D16_LOAD4("global_load_short_d16_hi", a, ", off", STRIDE, got);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int off = off0 + u * STRIDE;
+      unsigned want = mp_elem<E, SIGNED>(p.word(off >> 2), off), g = got[u];
+      if constexpr (FORM != MP_F_PLAIN) {
+        // the element, extended to 16 bits, is judged; what became of the
+        // other half (the canary) is recorded: 1 kept, 2 zeroed, 4 neither
+        const unsigned other = FORM == MP_F_D16 ? g >> 16 : g & 0xFFFFu;
+        const unsigned canary = FORM == MP_F_D16 ? MP_D16_CANARY >> 16 : MP_D16_CANARY & 0xFFFFu;
+        s.flags |= other == canary ? 1u : other == 0u ? 2u : 4u;
+        g = FORM == MP_F_D16 ? g & 0xFFFFu : g >> 16;
+        want &= 0xFFFFu;
+      }
+      mp_compare(s, g, want, mp_elem_mask<E>(), gstep, off);
+    }
+  }
+}
+
+// the 12288 B at `base` := v ^ x in E-byte elements; HI: from the high half of
+// a register whose low half holds the complement
+template <bool LDS, int E, bool HI>
+__device__ __forceinline__ void mp_narrow_store_step(unsigned* base, const MpPat& p, unsigned x,
+                                                     int lane) {
+  constexpr int PER = MP_SLICE_BYTES / (64 * E);
+  constexpr int STRIDE = 64 * E;
+  unsigned char* bytes = reinterpret_cast<unsigned char*>(base);
+#pragma unroll 1
+  for (int k0 = 0; k0 < PER; k0 += 4) {
+    const int off0 = k0 * STRIDE + lane * E;
+    unsigned d[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int off = off0 + u * STRIDE;
+      const unsigned e = mp_elem<E, false>(p.word(off >> 2) ^ x, off);
+      d[u] = HI ? (e << 16) | (~e & 0xFFFFu) : e | (~e << 16);
+    }
+    if constexpr (LDS) {
+      const unsigned a = (unsigned)(size_t)(MP_LDS_AS unsigned char*)(bytes + off0);
+      if constexpr (E == 1 && !HI) MP_D16_STORE4("ds_write_b8", a, "", STRIDE, d);
+      if constexpr (E == 1 && HI) MP_D16_STORE4("ds_write_b8_d16_hi", a, "", STRIDE, d);
+      if constexpr (E == 2 && !HI) MP_D16_STORE4("ds_write_b16", a, "", STRIDE, d);
+      if constexpr (E == 2 && HI) MP_D16_STORE4("ds_write_b16_d16_hi", a, "", STRIDE, d);
+    } else {
+      unsigned char* a = bytes + off0;
+      if constexpr (E == 1 && !HI) MP_D16_STORE4("global_store_byte", a, ", off", STRIDE, d);
+      if constexpr (E == 1 && HI) MP_D16_STORE4("global_store_byte_d16_hi", a, ", off", STRIDE, d);
+      if constexpr (E == 2 && !HI) MP_D16_STORE4("global_store_short", a, ", off", STRIDE, d);
+      if constexpr (E == 2 && HI) MP_D16_STORE4("global_store_short_d16_hi", a, ", off", STRIDE, d);
+    }
+  }
+}
+
+// the first 12288 B of the LDS region := v ^ x with ds_write_b32, and the same
+// against v ^ x with ds_read_b128
+__device__ __forceinline__ void mp_fill_lds(unsigned* region, const MpPat& p, unsigned x, int lane) {
+  for (int k = lane; k < MP_SLICE_WORDS; k += 64) {
+    region[k] = p.word(k) ^ x;
+    asm volatile("" ::: "memory");
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+__device__ __forceinline__ void mp_check_lds(MpState& s, const unsigned* region, const MpPat& p,
+                                             unsigned x, int gstep, int lane) {
+  const uint4* q = reinterpret_cast<const uint4*>(region);
+  for (int k = lane; k < MP_SLICE_WORDS / 4; k += 64) {
+    const uint4 v = q[k];
+    asm volatile("" ::: "memory");
+    mp_compare(s, v.x, p.word(4 * k) ^ x, 0xFFFFFFFFu, gstep, 16 * k);
+    mp_compare(s, v.y, p.word(4 * k + 1) ^ x, 0xFFFFFFFFu, gstep, 16 * k + 4);
+    mp_compare(s, v.z, p.word(4 * k + 2) ^ x, 0xFFFFFFFFu, gstep, 16 * k + 8);
+    mp_compare(s, v.w, p.word(4 * k + 3) ^ x, 0xFFFFFFFFu, gstep, 16 * k + 12);
+  }
+}
+
+// Wide LDS forms. Each visits the 3072 words once; WIDE names the form:
+//   0 b64, 1 b96 on 16 B aligned quads with the fourth word through b32, 2 b128
+//   3 read2/write2_b32       words i and i+64   (offset1:64, units of 4 B)
+//   4 read2st64/write2st64   words i and i+384  (offset1:6, units of 256 B)
+//   5 read2/write2_b64       words i,i+1 and i+128,i+129 (offset1:64, units of 8 B)
+// `first[j]`: the word index of access j's first word for this lane; the other
+// words follow by the form.
+template <int WIDE> struct MpWide;
+template <> struct MpWide<0> { static constexpr int N = 24, WORDS = 2;
+  __device__ static int first(int j, int lane) { return 2 * (j * 64 + lane); }
+  __device__ static int word(int c) { return c; } };
+template <> struct MpWide<1> { static constexpr int N = 12, WORDS = 4;  // b96, and b32 for the 4th
+  __device__ static int first(int j, int lane) { return 4 * (j * 64 + lane); }
+  __device__ static int word(int c) { return c; } };
+template <> struct MpWide<2> { static constexpr int N = 12, WORDS = 4;
+  __device__ static int first(int j, int lane) { return 4 * (j * 64 + lane); }
+  __device__ static int word(int c) { return c; } };
+template <> struct MpWide<3> { static constexpr int N = 24, WORDS = 2;
+  __device__ static int first(int j, int lane) { return j * 128 + lane; }
+  __device__ static int word(int c) { return 64 * c; } };
+template <> struct MpWide<4> { static constexpr int N = 24, WORDS = 2;
+  __device__ static int first(int j, int lane) { return (j / 6) * 768 + (j % 6) * 64 + lane; }
+  __device__ static int word(int c) { return 384 * c; } };
+template <> struct MpWide<5> { static constexpr int N = 12, WORDS = 4;
+  __device__ static int first(int j, int lane) { return j * 256 + 2 * lane; }
+  __device__ static int word(int c) { return (c & 1) + 128 * (c >> 1); } };
+
+template <int WIDE>
+__device__ __forceinline__ void mp_wide_read_step(MpState& s, const unsigned* region,
+                                                  const MpPat& p, int gstep, int lane) {
+  using F = MpWide<WIDE>;
+#pragma unroll 1
+  for (int j = 0; j < F::N; j++) {
+    const int i0 = F::first(j, lane);
+    const unsigned a = (unsigned)(size_t)(MP_LDS_AS const unsigned*)(region + i0);
+    unsigned got[4] = {0u, 0u, 0u, 0u};
+    if constexpr (WIDE == 0) {
+      mp_u2 v;
+      asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(a) : "memory");
+      got[0] = v.x, got[1] = v.y;
+    } else if constexpr (WIDE == 1) {
+      mp_u3 v;
+      asm volatile("ds_read_b96 %0, %2\n\tds_read_b32 %1, %2 offset:12\n\ts_waitcnt lgkmcnt(0)"
+                   : "=&v"(v), "=&v"(got[3]) : "v"(a) : "memory");
+      got[0] = v.x, got[1] = v.y, got[2] = v.z;
+    } else if constexpr (WIDE == 3 || WIDE == 4) {
+      mp_u2 v;
+      if constexpr (WIDE == 3)
+        asm volatile("ds_read2_b32 %0, %1 offset1:64\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(a) : "memory");
+      else
+        asm volatile("ds_read2st64_b32 %0, %1 offset1:6\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(a) : "memory");
+      got[0] = v.x, got[1] = v.y;
+    } else {
+      mp_u4 v;
+      asm volatile("ds_read2_b64 %0, %1 offset1:64\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(a) : "memory");
+      got[0] = v.x, got[1] = v.y, got[2] = v.z, got[3] = v.w;
+    }
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int c = 0; c < F::WORDS; c++) {
+      const int i = i0 + F::word(c);
+      mp_compare(s, got[c], p.word(i), 0xFFFFFFFFu, gstep, 4 * i);
+    }
+  }
+}
+
+template <int WIDE>
+__device__ __forceinline__ void mp_wide_write_step(unsigned* region, const MpPat& p, unsigned x,
+                                                   int lane) {
+  using F = MpWide<WIDE>;
+#pragma unroll 1
+  for (int j = 0; j < F::N; j++) {
+    const int i0 = F::first(j, lane);
+    const unsigned a = (unsigned)(size_t)(MP_LDS_AS unsigned*)(region + i0);
+    unsigned d[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int c = 0; c < F::WORDS; c++) d[c] = p.word(i0 + F::word(c)) ^ x;
+    if constexpr (WIDE == 0) {
+      asm volatile("ds_write_b64 %0, %1" : : "v"(a), "v"(mp_u2{d[0], d[1]}) : "memory");
+    } else if constexpr (WIDE == 1) {
+      asm volatile("ds_write_b96 %0, %1\n\tds_write_b32 %0, %2 offset:12"
+                   : : "v"(a), "v"(mp_u3{d[0], d[1], d[2]}), "v"(d[3]) : "memory");
+    } else if constexpr (WIDE == 2) {
+      asm volatile("ds_write_b128 %0, %1" : : "v"(a), "v"(mp_u4{d[0], d[1], d[2], d[3]}) : "memory");
+    } else if constexpr (WIDE == 3) {
+      asm volatile("ds_write2_b32 %0, %1, %2 offset1:64" : : "v"(a), "v"(d[0]), "v"(d[1]) : "memory");
+    } else if constexpr (WIDE == 4) {
+      asm volatile("ds_write2st64_b32 %0, %1, %2 offset1:6" : : "v"(a), "v"(d[0]), "v"(d[1]) : "memory");
+    } else {
+      asm volatile("ds_write2_b64 %0, %1, %2 offset1:64"
+                   : : "v"(a), "v"(mp_u2{d[0], d[1]}), "v"(mp_u2{d[2], d[3]}) : "memory");
+    }
+    asm volatile("" ::: "memory");
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
+__device__ __forceinline__ void mp_section_forms(MpState& s, unsigned* region, unsigned* row,
+                                                 const MpPat& p, int gbase, const MpInject& inj,
+                                                 int lane) {
+  int step = 0;
+  mp_fill_slice(row, p, 0u, lane);
+  mp_fill_lds(region, p, 0u, lane);
+#define MP_HERE (inj.wave_here && inj.step == gbase + step)
+#define MP_GLOAD(E, SIGNED, FORM)                                                      \
+  {                                                                                    \
+    const bool here = MP_HERE;                                                         \
+    mp_flip_global(row, here, inj.offset, inj.bit, lane);                              \
+    mp_narrow_load_step<false, E, SIGNED, FORM>(s, row, p, gbase + step, lane);        \
+    mp_flip_global(row, here, inj.offset, inj.bit, lane);                              \
+    step++;                                                                            \
+  }
+#define MP_GSTORE(E, HI)                                                               \
+  {                                                                                    \
+    const unsigned x = (unsigned)(step + 1) * 0x9E3779B9u;                             \
+    mp_narrow_store_step<false, E, HI>(row, p, x, lane);                               \
+    mp_fence();                                                                        \
+    mp_flip_global(row, MP_HERE, inj.offset, inj.bit, lane);                           \
+    mp_check_slice(s, row, p, x, gbase + step, lane);                                  \
+    step++;                                                                            \
+  }
+#define MP_LREAD(CALL)                                                                 \
+  {                                                                                    \
+    const bool here = MP_HERE;                                                         \
+    mp_flip_lds(region, here, inj.offset, inj.bit, lane);                              \
+    CALL;                                                                              \
+    mp_flip_lds(region, here, inj.offset, inj.bit, lane);                              \
+    step++;                                                                            \
+  }
+#define MP_LWRITE(CALL)                                                                \
+  {                                                                                    \
+    const unsigned x = (unsigned)(step + 1) * 0x9E3779B9u;                             \
+    CALL;                                                                              \
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                 \
+    mp_flip_lds(region, MP_HERE, inj.offset, inj.bit, lane);                           \
+    mp_check_lds(s, region, p, x, gbase + step, lane);                                 \
+    step++;                                                                            \
+  }
+  // global path: steps 0..13
+  MP_GLOAD(1, false, MP_F_PLAIN)
+  MP_GLOAD(1, true, MP_F_PLAIN)
+  MP_GLOAD(2, false, MP_F_PLAIN)
+  MP_GLOAD(2, true, MP_F_PLAIN)
+  MP_GLOAD(1, false, MP_F_D16)
+  MP_GLOAD(1, false, MP_F_D16_HI)
+  MP_GLOAD(1, true, MP_F_D16)
+  MP_GLOAD(1, true, MP_F_D16_HI)
+  MP_GLOAD(2, false, MP_F_D16)
+  MP_GLOAD(2, false, MP_F_D16_HI)
+  MP_GSTORE(1, false)
+  MP_GSTORE(1, true)
+  MP_GSTORE(2, false)
+  MP_GSTORE(2, true)
+  // LDS reads: steps 14..28
+  MP_LREAD((mp_narrow_load_step<true, 1, false, MP_F_PLAIN>(s, region, p, gbase + step, lane)))
+  MP_LREAD((mp_narrow_load_step<true, 1, true, MP_F_PLAIN>(s, region, p, gbase + step, lane)))
+  MP_LREAD((mp_narrow_load_step<true, 2, false, MP_F_PLAIN>(s, region, p, gbase + step, lane)))
+  MP_LREAD((mp_narrow_load_step<true, 2, true, MP_F_PLAIN>(s, region, p, gbase + step, lane)))
+  MP_LREAD((mp_narrow_load_step<true, 1, false, MP_F_D16>(s, region, p, gbase + step, lane)))
+  MP_LREAD((mp_narrow_load_step<true, 1, false, MP_F_D16_HI>(s, region, p, gbase + step, lane)))
+  MP_LREAD((mp_narrow_load_step<true, 1, true, MP_F_D16>(s, region, p, gbase + step, lane)))
+  MP_LREAD((mp_narrow_load_step<true, 1, true, MP_F_D16_HI>(s, region, p, gbase + step, lane)))
+  MP_LREAD((mp_narrow_load_step<true, 2, false, MP_F_D16>(s, region, p, gbase + step, lane)))
+  MP_LREAD((mp_narrow_load_step<true, 2, false, MP_F_D16_HI>(s, region, p, gbase + step, lane)))
+  MP_LREAD((mp_wide_read_step<0>(s, region, p, gbase + step, lane)))
+  MP_LREAD((mp_wide_read_step<1>(s, region, p, gbase + step, lane)))
+  MP_LREAD((mp_wide_read_step<3>(s, region, p, gbase + step, lane)))
+  MP_LREAD((mp_wide_read_step<4>(s, region, p, gbase + step, lane)))
+  MP_LREAD((mp_wide_read_step<5>(s, region, p, gbase + step, lane)))
+  // LDS writes: steps 29..38
+  MP_LWRITE((mp_narrow_store_step<true, 1, false>(region, p, x, lane)))
+  MP_LWRITE((mp_narrow_store_step<true, 2, false>(region, p, x, lane)))
+  MP_LWRITE((mp_narrow_store_step<true, 1, true>(region, p, x, lane)))
+  MP_LWRITE((mp_narrow_store_step<true, 2, true>(region, p, x, lane)))
+  MP_LWRITE((mp_wide_write_step<0>(region, p, x, lane)))
+  MP_LWRITE((mp_wide_write_step<1>(region, p, x, lane)))
+  MP_LWRITE((mp_wide_write_step<2>(region, p, x, lane)))
+  MP_LWRITE((mp_wide_write_step<3>(region, p, x, lane)))
+  MP_LWRITE((mp_wide_write_step<4>(region, p, x, lane)))
+  MP_LWRITE((mp_wide_write_step<5>(region, p, x, lane)))
+#undef MP_HERE
+#undef MP_GLOAD
+#undef MP_GSTORE
+#undef MP_LREAD
+#undef MP_LWRITE
+}
+
+template <int SEC>
+__global__ void __launch_bounds__(256)
+mempath_kernel(int4* __restrict__ records, unsigned* rows, int rounds, unsigned seed,
+               int inject_block, int inject_step, int inject_offset, int inject_bit) {
+  constexpr bool USES_LDS = SEC == MP_LDS || SEC == MP_FORMS;
+  __shared__ __attribute__((aligned(16))) unsigned lds[USES_LDS ? 4 * MP_LDS_WAVE_WORDS : 4];
+  const int lane = threadIdx.x & 63;
+  const int wave = uniform_wave_index();
+  const unsigned place = hw_word();
+  unsigned* row = rows + (size_t)wave * MP_ROW_WORDS;
+  unsigned* region = lds + (USES_LDS ? (wave & 3) * MP_LDS_WAVE_WORDS : 0);
+  const bool block_here = (int)blockIdx.x == inject_block;
+  const MpInject inj = {block_here, block_here && (wave & 3) == 0, inject_step, inject_offset,
+                        inject_bit};
+
+  row[MP_SLICE_WORDS + lane] = MP_GUARD_SENTINEL;  // MP_GUARD_WORDS == 64 lanes
+  MpState s = {0, -1, -1, 0u, 0u, 0u, 0u, 0u};
+  for (int round = 0; round < rounds; round++) {
+    const MpPat p = {seed + (unsigned)round * 0x9E3779B9u + (unsigned)wave * 0x7F4A7C15u,
+                     (round & 1) ? 0xFFFFFFFFu : 0u};
+    s.sum_mask = (round & 1) ? 0u : 0xFFFFFFFFu;
+    constexpr int NSTEPS = MP_STEPS[SEC];
+    const int gbase = round * NSTEPS;
+    if constexpr (SEC == MP_BUF) mp_section_buf(s, row, p, gbase, inj, lane);
+    if constexpr (SEC == MP_OOB) mp_section_oob(s, row, p, gbase, inj, lane);
+    if constexpr (SEC == MP_LDS) mp_section_lds(s, region, row, p, gbase, inj, lane);
+    if constexpr (SEC == MP_FORMS) mp_section_forms(s, region, row, p, gbase, inj, lane);
+  }
+  const int mismatched = (int)wave_add((unsigned)s.mismatched);
+  const unsigned dropped = wave_or(s.dropped), raised = wave_or(s.raised);
+  const unsigned checksum = wave_add(s.checksum), flags = wave_or(s.flags);
+  // -1 as unsigned is the largest value: the earliest step, then the lowest
+  // offset among the lanes that failed in that step
+  const unsigned first_step = wave_min((unsigned)s.first_step);
+  const unsigned first_off =
+      wave_min((unsigned)s.first_step == first_step ? (unsigned)s.first_off : 0xFFFFFFFFu);
+  if (lane == 0)
+    store_record8(records, wave, (int)place, mismatched, (int)first_step, (int)first_off,
+                  (int)dropped, (int)raised, (int)checksum, (int)flags);
+}
+
+static int mempath_section_id(const std::string& section) {
+  static const char* names[MP_SECTIONS] = {"buf", "oob", "lds", "forms"};
+  for (int i = 0; i < MP_SECTIONS; i++)
+    if (section == names[i]) return i;
+  TORCH_CHECK(false, "mempath_probe: unknown section '", section, "' (buf|oob|lds|forms)");
+  return -1;
+}
+
+// One untimed warm-up launch, then one timed launch (warm_then_timed_ms); the
+// kernel rewrites the guard and the slice itself, so both start alike.
+// Returns (records [blocks*4, 8] int32, elapsed_ms of the timed launch).
+std::tuple<torch::Tensor, double> mempath_probe(const std::string& section, long blocks,
+                                                long rounds, long seed, long inject_block,
+                                                long inject_step, long inject_offset,
+                                                long inject_bit) {
+  const int sec = mempath_section_id(section);
+  TORCH_CHECK(blocks >= 1 && blocks <= (1L << 16), "blocks must be in [1, 2^16]");
+  TORCH_CHECK(rounds >= 1, "rounds must be >= 1");
+  // bounded run: a round of one workgroup measures ~1.0 ms in the oob section
+  // (61 steps of a few accesses, each behind two fences), ~0.3 ms in buf,
+  // ~0.5 ms in forms and ~0.05 ms in lds on an MI355X (BENCHMARKS.md
+  // "Memory-path probe"); it is latency, so a full GPU of 1024 workgroups
+  // amortises the oob round to ~4 us and puts 2^16 block-rounds at ~0.26 s
+  TORCH_CHECK(rounds <= (1L << 16) && blocks * rounds <= (1L << 16),
+              "blocks*rounds must be <= 2^16");
+  // the injected element: in the slice, or for the LDS steps in the wave's region
+  const long span = sec == MP_LDS ? 4L * MP_LDS_WAVE_WORDS : MP_SLICE_BYTES;
+  TORCH_CHECK(inject_block >= -1 && inject_block < blocks, "inject_block out of range");
+  TORCH_CHECK(inject_step >= -1 && inject_step < rounds * MP_STEPS[sec],
+              "inject_step out of range");
+  TORCH_CHECK(inject_offset >= -1 && inject_offset < span, "inject_offset out of range");
+  TORCH_CHECK(inject_bit >= 0 && inject_bit < 32 && (inject_offset & 3) * 8 + inject_bit < 32,
+              "inject_bit out of range");
+  TORCH_CHECK(inject_block < 0 || sec == MP_OOB || (inject_step >= 0 && inject_offset >= 0),
+              "an injection needs inject_step and inject_offset");
+  if (inject_block >= 0 && inject_offset < 0) inject_offset = 0;  // oob: unused
+  const long waves = blocks * 4;
+  auto rows = torch::empty({waves, (long)MP_ROW_WORDS},
+                           torch::TensorOptions().dtype(torch::kInt32).device(torch::kCUDA));
+  auto records = zero_records(waves, 8);
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  const double ms = warm_then_timed_ms(stream, [&]() {
+    dispatch_int<MP_SECTIONS>(sec, [&](auto s) {
+      hipLaunchKernelGGL(mempath_kernel<decltype(s)::value>, dim3(blocks), dim3(256), 0, stream,
+                         reinterpret_cast<int4*>(records.data_ptr<int>()),
+                         reinterpret_cast<unsigned*>(rows.data_ptr<int>()), (int)rounds,
+                         (unsigned)seed, (int)inject_block, (int)inject_step, (int)inject_offset,
+                         (int)inject_bit);
+    });
+  });
+  return std::make_tuple(records, ms);
+}
+
 py::dict device_info(int dev) {
   hipDeviceProp_t prop;
   HIP_CHECK(hipGetDeviceProperties(&prop, dev));
@@ -3944,6 +4909,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("per_lane"), py::arg("cells"),
         "Contended atomics (section ticket|reduce|cas) from every workgroup on `cells` shared "
         "cells 4 KiB apart; returns {shared, owner, records, ms} for the host to judge");
+  m.def("mempath_probe", &mempath_probe, py::arg("section"), py::arg("blocks"), py::arg("rounds"),
+        py::arg("seed"), py::arg("inject_block") = -1, py::arg("inject_step") = -1,
+        py::arg("inject_offset") = -1, py::arg("inject_bit") = 0,
+        "Memory-path probe (section buf|oob|lds|forms): buffer addressing in every width, the "
+        "descriptor's bounds check, direct-to-LDS loads, sub-dword, d16 and wide forms, verified "
+        "bitwise; returns (per-wave records [blocks*4,8], ms)");
   m.def("cu_coverage", &cu_coverage, py::arg("blocks") = 4096,
         "Per-wave (XCC_ID<<16 | HW_ID) placement words for CU-coverage checks");
   m.def("device_info", &device_info, py::arg("dev") = 0);
