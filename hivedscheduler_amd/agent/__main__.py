@@ -69,6 +69,12 @@ def main() -> None:
                          "sweeps); 0 = never")
     ap.add_argument("--mempath-probe", action="store_true",
                     help="with --local: also run the memory-path probe")
+    ap.add_argument("--matrix-probe-every", type=int, default=0,
+                    help="matrix-path probe (f64, f32, f16, i8, e5m2 and 32x32 MFMA shapes, 2:4 "
+                         "sparse smfmac, exact tiles and a burn, per CU) every N sweeps (on deep "
+                         "sweeps); 0 = never")
+    ap.add_argument("--matrix-probe", action="store_true",
+                    help="with --local: also run the matrix-path probe")
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
@@ -87,7 +93,8 @@ def main() -> None:
                                      scalar_probe=args.scalar_probe,
                                      atomic_probe=args.atomic_probe,
                                      mx_scale_probe=args.mx_scale_probe,
-                                     mempath_probe=args.mempath_probe)
+                                     mempath_probe=args.mempath_probe,
+                                     matrix_probe=args.matrix_probe)
         if args.p2p_matrix:
             try:
                 m = p2p_link_matrix()
@@ -113,7 +120,8 @@ def main() -> None:
                             scalar_probe_every=args.scalar_probe_every,
                             atomic_probe_every=args.atomic_probe_every,
                             mx_scale_probe_every=args.mx_scale_probe_every,
-                            mempath_probe_every=args.mempath_probe_every)
+                            mempath_probe_every=args.mempath_probe_every,
+                            matrix_probe_every=args.matrix_probe_every)
     if args.once:
         import json
 

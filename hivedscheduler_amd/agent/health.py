@@ -63,6 +63,7 @@ def collect_node_health(
     atomic_probe: bool = False,
     mx_scale_probe: bool = False,
     mempath_probe: bool = False,
+    matrix_probe: bool = False,
 ) -> dict:
     """One health sweep over all visible GPUs. deep=True also runs the HIP
     kernels (HBM + MFMA); sweep=True adds the 16 GiB HBM stuck-bit pattern
@@ -131,6 +132,13 @@ def collect_node_health(
     any wave that read back wrong data, as xcc, se, sh, cu), and a failed
     probe marks the leaf bad.
 
+    matrix_probe=True (with deep) adds the matrix-path probe (the f64, f32,
+    f16, i8, e5m2 and 32x32 MFMA shapes and the 2:4 sparse smfmac forms, as
+    exact tiles and as a burn): per GPU it records `matrix_probe_ok`,
+    `matrix_tflops` ({burn path: TFLOP/s}, reported, not judged) and
+    `matrix_bad_cus` (the CUs of any wave whose burn result was wrong, as xcc,
+    se, sh, cu), and a failed probe marks the leaf bad.
+
     The stuck-bit scan transiently holds up to 16 GiB of HBM; on a GPU
     running tenant jobs this can make the tenant's own allocations fail.
     Keep sweep on the low-frequency cadence and prefer idle GPUs (the
@@ -154,7 +162,7 @@ def collect_node_health(
         kwargs = _set_flags(burn=burn, lds_march=lds_march, hbm_march=hbm_march,
                             simd_probe=simd_probe, scalar_probe=scalar_probe,
                             atomic_probe=atomic_probe, mx_scale_probe=mx_scale_probe,
-                            mempath_probe=mempath_probe)
+                            mempath_probe=mempath_probe, matrix_probe=matrix_probe)
         for i in range(n):
             gpu = report["gpus"][str(i)]
             try:
@@ -268,6 +276,17 @@ def collect_node_health(
                     )
                     if not p["ok"] or p["bad_cus"]:
                         gpu["healthy"] = False
+                if matrix_probe:
+                    p = rep["matrix_probe"]
+                    gpu.update(
+                        matrix_probe_ok=bool(p["ok"]),
+                        matrix_tflops={name: round(s["tflops"], 1)
+                                       for name, s in p["burn"]["paths"].items()},
+                        matrix_bad_cus=[{k: c[k] for k in ("xcc", "se", "sh", "cu")}
+                                        for c in p["bad_cus"]],
+                    )
+                    if not p["ok"] or p["bad_cus"]:
+                        gpu["healthy"] = False
             except Exception as e:
                 gpu.update(healthy=False, error=str(e)[:200])
     if probe_pairs and n >= 2:
@@ -344,7 +363,7 @@ class NodeHealthAgent:
                  hbm_march_every: int = 0, min_xcd_ratio: Optional[float] = None,
                  simd_probe_every: int = 0, scalar_probe_every: int = 0,
                  atomic_probe_every: int = 0, mx_scale_probe_every: int = 0,
-                 mempath_probe_every: int = 0):
+                 mempath_probe_every: int = 0, matrix_probe_every: int = 0):
         self.scheduler_url = scheduler_url.rstrip("/")
         self.node_name = node_name or socket.gethostname()
         self.interval_s = interval_s
@@ -391,6 +410,10 @@ class NodeHealthAgent:
         # memory-path probe cadence (buffer addressing, bounds check,
         # direct-to-LDS, narrow and wide forms), same pattern; 0 = never
         self.mempath_probe_every = mempath_probe_every
+        # matrix-path probe cadence (f64, f32, f16, i8, e5m2, 32x32 and sparse
+        # matrix instructions), same pattern; 0 = never (about 0.1 s of
+        # matrix-core time per GPU, on cores a tenant may be using)
+        self.matrix_probe_every = matrix_probe_every
         self._rounds = 0
 
     def post_report(self, report: dict) -> bool:
@@ -450,7 +473,8 @@ class NodeHealthAgent:
                             scalar_probe=deep and self._due(self.scalar_probe_every),
                             atomic_probe=deep and self._due(self.atomic_probe_every),
                             mx_scale_probe=deep and self._due(self.mx_scale_probe_every),
-                            mempath_probe=deep and self._due(self.mempath_probe_every))
+                            mempath_probe=deep and self._due(self.mempath_probe_every),
+                            matrix_probe=deep and self._due(self.matrix_probe_every))
         self._rounds += 1
         if "burn" in kwargs:
             kwargs["min_mfma_tflops"] = self.min_mfma_tflops

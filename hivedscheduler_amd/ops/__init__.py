@@ -5,7 +5,8 @@ extension is REQUIRED: failure to load raises (no silent eager fallback).
 
 Here: the loader, `gpu_health_report` and the single-tile MFMA checks. Each
 opt-in probe has a module of its own (mfma_burn, lds_march, hbm_march,
-simd_probe, scalar_probe, atomic_probe, mx_scale, mempath_probe) on top of `records`, and the
+simd_probe, scalar_probe, atomic_probe, mx_scale, mempath_probe, matrix_paths)
+on top of `records`, and the
 single-tile checks' operands and verdict are in mfma_tiles; their public names
 are re-exported here, and their report functions reach the extension through
 `_ops_on` below.
@@ -26,6 +27,13 @@ from .hbm_march import (HBM_MARCH_TILE_BYTES, hbm_march_pattern, hbm_march_repor
                         hbm_slow_xcds, summarize_hbm_march)
 from .lds_march import (LDS_MARCH_WORDS, lds_march_block_checksum, lds_march_pattern,  # noqa: F401
                         lds_march_report, summarize_lds_march)
+from .matrix_paths import (MATRIX_ABIDS, MATRIX_BURN_PATHS, MATRIX_INDEX_PAIRS,  # noqa: F401
+                           MATRIX_PATHS, MATRIX_PROBE_SEED, MATRIX_SPARSE_PATHS,
+                           judge_matrix_tiles, matrix_burn_operands, matrix_burn_report,
+                           matrix_chain_limit, matrix_decode, matrix_exact, matrix_expand,
+                           matrix_index_case, matrix_k_slot_case, matrix_operand_invariants,
+                           matrix_operands, matrix_path_shape, matrix_probe_report,
+                           matrix_product, matrix_tile_report, summarize_matrix_burn)
 from .mempath_probe import (MEMPATH_SECTIONS, mempath_oob_cases, mempath_pattern,  # noqa: F401
                             mempath_probe_report, mempath_section_report, mempath_steps,
                             mempath_wave_checksum, summarize_mempath)
@@ -84,7 +92,8 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
                       bw_samples: int = 1, burn: bool = False, lds_march: bool = False,
                       hbm_march: bool = False, simd_probe: bool = False,
                       scalar_probe: bool = False, atomic_probe: bool = False,
-                      mx_scale_probe: bool = False, mempath_probe: bool = False) -> dict:
+                      mx_scale_probe: bool = False, mempath_probe: bool = False,
+                      matrix_probe: bool = False) -> dict:
     """Run the health-probe kernels on one GPU and return measured facts.
 
     Feeds leaf-cell healthiness: HBM bandwidth deficit, MFMA mismatch, or
@@ -144,6 +153,12 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     launches of about 7 ms together on an idle MI355X, each after a warm-up
     launch of the same length) as report["mempath_probe"] and ANDs its verdict into
     `healthy`. Off by default, and the report is then unchanged.
+
+    matrix_probe=True adds the matrix-path probe (`matrix_probe_report`: the
+    f64, f32, f16, i8, e5m2 and 32x32 MFMA shapes and the 2:4 sparse smfmac
+    forms, as exact tiles and as a burn of tens of milliseconds per burn
+    path) as report["matrix_probe"] and ANDs its verdict into `healthy`. Off
+    by default, and the report is then unchanged.
     """
     ops = _ops_on(device)
     size_mb = 256 if quick else 2048
@@ -213,6 +228,9 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     if mempath_probe:
         report["mempath_probe"] = mempath_probe_report(device)
         report["healthy"] = bool(report["healthy"] and report["mempath_probe"]["ok"])
+    if matrix_probe:
+        report["matrix_probe"] = matrix_probe_report(device)
+        report["healthy"] = bool(report["healthy"] and report["matrix_probe"]["ok"])
     return report
 
 

@@ -13,6 +13,9 @@
 //  - mx_scale_tile / mx_scale_burn: the block-scaled MFMA with per-lane E8M0
 //                scales, all four scale bytes, e5m2 and the 6-bit formats, mixed
 //                formats and the 32x32x64 shape, bitwise against float64
+//  - matrix_tile / matrix_burn: the f64, f32, f16, i8, e5m2 and 32x32 MFMA
+//                shapes and the 2:4 sparse smfmac forms, bitwise against float64
+//                or int64; the CU of any wave whose burn was wrong
 //  - lds_march:  all 160 KiB of every CU's LDS, both bit polarities, narrow
 //                and wide reads, timed; the CU, word and bits of any mismatch
 //  - valu_burn:  sustained, timed vector-ALU issue per section (integer, f32,
@@ -1138,6 +1141,427 @@ std::tuple<torch::Tensor, double> mx_scale_burn(torch::Tensor A, torch::Tensor B
                          B.data_ptr<unsigned char>(), sa, sb, expected.data_ptr<float>(),
                          reinterpret_cast<int4*>(records.data_ptr<int>()), (int)chain, (int)rounds,
                          (int)inject_wave, (int)inject_round);
+    });
+  });
+  return std::make_tuple(records, ms);
+}
+
+// ---------------------------------------------------------------------------
+// Matrix-path probe: the matrix instructions tenant jobs run and no probe
+// above issues. Dense: f64 16x16x4 (every DGEMM), f32 16x16x4 and 32x32x2,
+// f16 16x16x32 and 32x32x16, bf16 and e4m3 in the 32x32x16 shape, i8 to i32
+// in 16x16x64 and 32x32x32, e5m2 and the two mixed e4m3/e5m2 forms of the
+// unscaled 8-bit MFMA. Sparse: the 2:4 structured v_smfmac_* in f16 (16x16x64,
+// 32x32x32), bf16 (16x16x64) and i8 (16x16x128), with their index operand and
+// its part select. matrix_tile returns one tile per wave for the host to
+// compare bitwise with the float64 / int64 product (ops/matrix_paths.py);
+// matrix_burn is the sustained, timed run with the compare in the kernel.
+//
+// One trait per path (MatPath<PATH>, below) gives the element and fragment
+// types, load_a, load_b, mma and the output map; both kernels are written
+// once against it.
+//
+// Layouts (gfx950). M is the tile edge, a lane group is M lanes, G = 64/M
+// groups; lane l has i = l % M, g = l / M:
+//   A:   the lane holds row i of A, its KA = K/G elements A[i][KA*g + j]
+//        (sparse: of the compressed row, KA = K/2/G)
+//   B:   the lane holds column i of B, its KB = K/G elements B[kb(g, j)][i];
+//        dense: kb = KB*g + j. Sparse (measured on an MI355X with one-hot
+//        operands, BENCHMARKS.md "Matrix-path probe"): the first four VGPRs
+//        of all groups are the first half of K and the last four the second,
+//        kb = (j / H) * H*G + H*g + j % H with H = KB/2, the walk the 8-bit MX
+//        operands showed; A's compressed row stays consecutive.
+//   D:   16x16: reg r of 4  -> row 4g + r, col i
+//        32x32: reg r of 16 -> row 8*(r>>2) + 4g + (r&3), col i
+//        f64 16x16x4 (measured, BENCHMARKS.md "Matrix-path probe"): element
+//        r of 4, a register pair, -> row 4r + g, col i: a lane's four rows
+//        are 4 apart, not consecutive as in the 32-bit 16x16 shapes
+//   K:   a dense product does not change when A and B walk K by the same
+//        map, so which k the hardware calls register element j of group g
+//        cannot be seen from outside; the loaders above are "consecutive" and
+//        the one-hot cases (matrix_k_slot_case) prove that load_a and load_b
+//        name the same slot, element for element, in every path.
+//   2:4: a sparse A row is K/2 values plus, per value, its position 0..3 in
+//        its group of four along K (two values per group, positions strictly
+//        increasing). Register element j of A pairs with register element
+//        4*(j>>1) + position of B in the same lane group: the selection is
+//        made on the B registers of the group, so here the walk can be seen.
+//        The positions are packed two bits apiece, element j at bits
+//        [2j, 2j+2) of the part of the index VGPR that ABID selects: 16 bits
+//        per part for the 16-bit paths (KA = 8; ABID 0 reads [15:0], 1 reads
+//        [31:16]), all 32 bits for i8 (KA = 16). The parts ABID does not select
+//        are filled with another valid pattern (pair (0,1) becomes (2,3), every
+//        other pair (0,1)), so a wrong select gives a wrong tile.
+//
+// Operands go from global memory straight into registers, once per launch;
+// the burn's hot loop touches no memory.
+//
+// Burn protocol: that of mfma_burn (four independent accumulator tiles per
+// wave, `chain` dependent MFMAs per accumulator per round, accumulators reset
+// through an opaque asm each round, every element compared bitwise, one int4
+// record per wave {placement word, mismatched elements, first bad round, xor
+// checksum}; inject flips the lowest bit of acc[0][0] of lane 0 in registers).
+// Operands are integers of magnitude <= 2, so a partial sum is an integer of
+// magnitude <= 4*K*chain: exact while that stays within 2^24 (f32
+// accumulators), 2^53 (f64) or 2^31 (i32).
+// ---------------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(4))) double f64x4;
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+typedef __attribute__((ext_vector_type(16))) int i32x16;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(16))) _Float16 f16x16;
+typedef __attribute__((ext_vector_type(16))) short frag16;
+
+enum {
+  MAT_F64_16, MAT_F32_16, MAT_F32_32, MAT_F16_16, MAT_F16_32, MAT_BF16_32, MAT_I8_16, MAT_I8_32,
+  MAT_FP8_32, MAT_BF8_16, MAT_FP8BF8_16, MAT_BF8FP8_16,
+  MAT_SP_F16_16, MAT_SP_F16_32, MAT_SP_BF16_16, MAT_SP_I8_16, MAT_PATHS
+};
+constexpr int MAT_NACC = 4;
+
+// E: element as it lies in memory and in the fragment; FA, FB: the operand
+// registers; ACC, OUT: the accumulator vector and its element
+template <typename E, typename FA, typename FB, typename ACC, typename OUT, int M_, int K_,
+          bool SPARSE_>
+struct MatShape {
+  static constexpr int M = M_, K = K_, G = 64 / M_, NREG = M_ * M_ / 64;
+  static constexpr bool SPARSE = SPARSE_;
+  static constexpr int KA = (SPARSE_ ? K_ / 2 : K_) / G, KB = K_ / G;
+  typedef FA frag_a;
+  typedef FB frag_b;
+  typedef ACC acc;
+  typedef OUT out;
+  static_assert(sizeof(FA) == KA * sizeof(E) && sizeof(FB) == KB * sizeof(E),
+                "a fragment is the lane's share of K");
+  static __device__ __forceinline__ int row(int r, int g) {
+    if (sizeof(OUT) == 8) return 4 * r + g;
+    return M == 16 ? 4 * g + r : 8 * (r >> 2) + 4 * g + (r & 3);
+  }
+  static __device__ __forceinline__ FA load_a(const void* A, int row, int g) {
+    const E* p = static_cast<const E*>(A) + row * (KA * G) + KA * g;
+    union { FA v; E e[KA]; } f;
+#pragma unroll
+    for (int j = 0; j < KA; j++) f.e[j] = p[j];
+    return f.v;
+  }
+  // the row of B that register element j of lane group g holds
+  static __device__ __forceinline__ constexpr int kb(int g, int j) {
+    if constexpr (SPARSE_) {
+      constexpr int HALF = KB / 2;
+      return (j / HALF) * (HALF * G) + HALF * g + j % HALF;
+    } else {
+      return KB * g + j;
+    }
+  }
+  static __device__ __forceinline__ FB load_b(const void* B, int col, int g) {
+    const E* p = static_cast<const E*>(B) + col;
+    union { FB v; E e[KB]; } f;
+#pragma unroll
+    for (int j = 0; j < KB; j++) f.e[j] = p[kb(g, j) * M];
+    return f.v;
+  }
+};
+
+template <int PATH> struct MatPath;
+#define MAT_DENSE(PATH, E, F, ACC, OUT, M, K, INSTR)                                         \
+  template <> struct MatPath<PATH> : MatShape<E, F, F, ACC, OUT, M, K, false> {             \
+    template <int ABID> static __device__ __forceinline__ ACC mma(F a, F b, ACC c, int) {   \
+      return __builtin_amdgcn_mfma_##INSTR(a, b, c, 0, 0, 0);                                \
+    }                                                                                        \
+  }
+#define MAT_SPARSE(PATH, E, FA, FB, ACC, OUT, M, K, INSTR)                                   \
+  template <> struct MatPath<PATH> : MatShape<E, FA, FB, ACC, OUT, M, K, true> {            \
+    template <int ABID> static __device__ __forceinline__ ACC mma(FA a, FB b, ACC c,        \
+                                                                  int index) {              \
+      return __builtin_amdgcn_smfmac_##INSTR(a, b, c, index, 0, ABID);                       \
+    }                                                                                        \
+  }
+MAT_DENSE(MAT_F64_16, double, double, f64x4, double, 16, 4, f64_16x16x4f64);
+MAT_DENSE(MAT_F32_16, float, float, f32x4, float, 16, 4, f32_16x16x4f32);
+MAT_DENSE(MAT_F32_32, float, float, f32x16, float, 32, 2, f32_32x32x2f32);
+MAT_DENSE(MAT_F16_16, _Float16, f16x8, f32x4, float, 16, 32, f32_16x16x32_f16);
+MAT_DENSE(MAT_F16_32, _Float16, f16x8, f32x16, float, 32, 16, f32_32x32x16_f16);
+MAT_DENSE(MAT_BF16_32, short, frag8, f32x16, float, 32, 16, f32_32x32x16_bf16);
+MAT_DENSE(MAT_I8_16, signed char, i32x4, i32x4, int, 16, 64, i32_16x16x64_i8);
+MAT_DENSE(MAT_I8_32, signed char, i32x4, i32x16, int, 32, 32, i32_32x32x32_i8);
+MAT_DENSE(MAT_FP8_32, unsigned char, long, f32x16, float, 32, 16, f32_32x32x16_fp8_fp8);
+MAT_DENSE(MAT_BF8_16, unsigned char, long, f32x4, float, 16, 32, f32_16x16x32_bf8_bf8);
+MAT_DENSE(MAT_FP8BF8_16, unsigned char, long, f32x4, float, 16, 32, f32_16x16x32_fp8_bf8);
+MAT_DENSE(MAT_BF8FP8_16, unsigned char, long, f32x4, float, 16, 32, f32_16x16x32_bf8_fp8);
+MAT_SPARSE(MAT_SP_F16_16, _Float16, f16x8, f16x16, f32x4, float, 16, 64, f32_16x16x64_f16);
+MAT_SPARSE(MAT_SP_F16_32, _Float16, f16x8, f16x16, f32x16, float, 32, 32, f32_32x32x32_f16);
+MAT_SPARSE(MAT_SP_BF16_16, short, frag8, frag16, f32x4, float, 16, 64, f32_16x16x64_bf16);
+MAT_SPARSE(MAT_SP_I8_16, signed char, i32x4, i32x8, i32x4, int, 16, 128, i32_16x16x128_i8);
+#undef MAT_DENSE
+#undef MAT_SPARSE
+
+// the index VGPR of a sparse path from the lane's KA positions (layout above)
+template <int KA>
+__device__ __forceinline__ int mat_pack_index(const unsigned char* __restrict__ pos, int abid) {
+  unsigned own = 0, other = 0;
+#pragma unroll
+  for (int j = 0; j < KA; j += 2) {
+    const unsigned p0 = pos[j] & 3, p1 = pos[j + 1] & 3;
+    own |= (p0 | (p1 << 2)) << (2 * j);
+    other |= ((p0 == 0 && p1 == 1) ? 0xEu : 0x4u) << (2 * j);  // (2,3), else (0,1)
+  }
+  if constexpr (KA == 16) return (int)own;  // all 32 bits are one part
+  return abid == 0 ? (int)(own | (other << 16)) : (int)(other | (own << 16));
+}
+
+// an accumulator element's bits, their fold into the 32-bit checksum, and the
+// element with its lowest bit flipped
+__device__ __forceinline__ unsigned long long mat_bits(double v) {
+  return (unsigned long long)__double_as_longlong(v);
+}
+__device__ __forceinline__ unsigned mat_bits(float v) { return __float_as_uint(v); }
+__device__ __forceinline__ unsigned mat_bits(int v) { return (unsigned)v; }
+__device__ __forceinline__ unsigned mat_fold(unsigned long long b) {
+  return (unsigned)b ^ (unsigned)(b >> 32);
+}
+__device__ __forceinline__ unsigned mat_fold(unsigned b) { return b; }
+__device__ __forceinline__ double mat_flip(double v) {
+  return __longlong_as_double(__double_as_longlong(v) ^ 1LL);
+}
+__device__ __forceinline__ float mat_flip(float v) {
+  return __uint_as_float(__float_as_uint(v) ^ 1u);
+}
+__device__ __forceinline__ int mat_flip(int v) { return v ^ 1; }
+
+template <int PATH, int ABID>
+__global__ void __launch_bounds__(256)
+matrix_tile_kernel(const void* __restrict__ A, const void* __restrict__ B,
+                   const unsigned char* __restrict__ index, void* __restrict__ C) {
+  typedef MatPath<PATH> P;
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int i = lane % P::M, g = lane / P::M;
+  const typename P::frag_a a = P::load_a(A, i, g);
+  const typename P::frag_b b = P::load_b(B, i, g);
+  int idx = 0;
+  if constexpr (P::SPARSE) idx = mat_pack_index<P::KA>(index + i * (P::KA * P::G) + P::KA * g, ABID);
+  typename P::acc acc;
+#pragma unroll
+  for (int r = 0; r < P::NREG; r++) acc[r] = 0;
+  acc = P::template mma<ABID>(a, b, acc, idx);
+  typename P::out* out = static_cast<typename P::out*>(C) + (size_t)wave * (P::M * P::M);
+#pragma unroll
+  for (int r = 0; r < P::NREG; r++) out[P::row(r, g) * P::M + i] = acc[r];
+}
+
+template <int PATH, int ABID>
+__global__ void __launch_bounds__(256)
+matrix_burn_kernel(const void* __restrict__ A, const void* __restrict__ B,
+                   const unsigned char* __restrict__ index, const void* __restrict__ expected,
+                   int4* __restrict__ records, int chain, int rounds, int inject_wave,
+                   int inject_round) {
+  typedef MatPath<PATH> P;
+  typedef decltype(mat_bits(typename P::out())) bits_t;
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int i = lane % P::M, g = lane / P::M;
+  const unsigned place = hw_word();
+
+  typename P::frag_a a[MAT_NACC];
+  int idx[MAT_NACC];
+  bits_t want[MAT_NACC][P::NREG];
+  const typename P::out* tile = static_cast<const typename P::out*>(expected);
+#pragma unroll
+  for (int n = 0; n < MAT_NACC; n++) {
+    const int row = n * P::M + i;
+    a[n] = P::load_a(A, row, g);
+    idx[n] = 0;
+    if constexpr (P::SPARSE)
+      idx[n] = mat_pack_index<P::KA>(index + row * (P::KA * P::G) + P::KA * g, ABID);
+#pragma unroll
+    for (int r = 0; r < P::NREG; r++)
+      want[n][r] = mat_bits(tile[(n * P::M + P::row(r, g)) * P::M + i]);
+  }
+  const typename P::frag_b b = P::load_b(B, i, g);
+
+  const bool inject_here = (wave == inject_wave) && (lane == 0);
+  int mismatched = 0, first_bad = -1;
+  unsigned checksum = 0;
+  for (int round = 0; round < rounds; round++) {
+    typename P::acc acc[MAT_NACC];
+#pragma unroll
+    for (int n = 0; n < MAT_NACC; n++) {
+#pragma unroll
+      for (int r = 0; r < P::NREG; r++) acc[n][r] = 0;
+      // opaque to the optimiser: every round really recomputes its chain
+      asm volatile("" : "+v"(acc[n]));
+    }
+    for (int c = 0; c < chain; c++) {
+#pragma unroll
+      for (int n = 0; n < MAT_NACC; n++) acc[n] = P::template mma<ABID>(a[n], b, acc[n], idx[n]);
+    }
+    if (inject_here && round == inject_round) acc[0][0] = mat_flip(acc[0][0]);
+    int bad = 0;
+#pragma unroll
+    for (int n = 0; n < MAT_NACC; n++) {
+#pragma unroll
+      for (int r = 0; r < P::NREG; r++) {
+        const bits_t bits = mat_bits(acc[n][r]);
+        bad += (bits != want[n][r]);
+        checksum ^= mat_fold(bits);
+      }
+    }
+    for (int off = 32; off > 0; off >>= 1) bad += __shfl_xor(bad, off);
+    mismatched += bad;
+    if (bad && first_bad < 0) first_bad = round;
+  }
+  checksum = wave_xor(checksum);
+  if (lane == 0) records[wave] = make_int4((int)place, mismatched, first_bad, (int)checksum);
+}
+
+// what the host knows of a path; the order is that of the MAT_* ids
+struct MatInfo {
+  const char* name;
+  long M, K;
+  bool sparse;
+  c10::ScalarType in, out;
+};
+static const MatInfo MAT_INFO[MAT_PATHS] = {
+    {"f64_16x16x4", 16, 4, false, torch::kFloat64, torch::kFloat64},
+    {"f32_16x16x4", 16, 4, false, torch::kFloat32, torch::kFloat32},
+    {"f32_32x32x2", 32, 2, false, torch::kFloat32, torch::kFloat32},
+    {"f16_16x16x32", 16, 32, false, torch::kFloat16, torch::kFloat32},
+    {"f16_32x32x16", 32, 16, false, torch::kFloat16, torch::kFloat32},
+    {"bf16_32x32x16", 32, 16, false, torch::kBFloat16, torch::kFloat32},
+    {"i8_16x16x64", 16, 64, false, torch::kInt8, torch::kInt32},
+    {"i8_32x32x32", 32, 32, false, torch::kInt8, torch::kInt32},
+    {"fp8_32x32x16", 32, 16, false, torch::kUInt8, torch::kFloat32},
+    {"bf8_16x16x32", 16, 32, false, torch::kUInt8, torch::kFloat32},
+    {"fp8bf8_16x16x32", 16, 32, false, torch::kUInt8, torch::kFloat32},
+    {"bf8fp8_16x16x32", 16, 32, false, torch::kUInt8, torch::kFloat32},
+    {"sp_f16_16x16x64", 16, 64, true, torch::kFloat16, torch::kFloat32},
+    {"sp_f16_32x32x32", 32, 32, true, torch::kFloat16, torch::kFloat32},
+    {"sp_bf16_16x16x64", 16, 64, true, torch::kBFloat16, torch::kFloat32},
+    {"sp_i8_16x16x128", 16, 128, true, torch::kInt8, torch::kInt32},
+};
+// the paths the burn kernel is instantiated for
+constexpr int MAT_BURN_PATHS = 6;
+constexpr int MAT_BURN_PATH[MAT_BURN_PATHS] = {MAT_F64_16, MAT_F32_32, MAT_F16_16,
+                                               MAT_I8_16,  MAT_BF8_16, MAT_SP_F16_16};
+
+// The path's id after checking what both entry points require: a known path,
+// A [tiles*M, K] (sparse: [tiles*M, K/2] values and as many uint8 positions,
+// each below 4 and increasing within a pair) and B [K, M] of the path's type
+// on one GPU, abid 0 or 1 and only for a sparse path, blocks in range.
+static int mat_check_operands(const std::string& path, const torch::Tensor& A,
+                              const torch::Tensor& B,
+                              const c10::optional<torch::Tensor>& index, long abid, long blocks,
+                              long tiles) {
+  int id = -1;
+  for (int p = 0; p < MAT_PATHS; p++)
+    if (path == MAT_INFO[p].name) id = p;
+  TORCH_CHECK(id >= 0, "unknown matrix path ", path);
+  const MatInfo& info = MAT_INFO[id];
+  const long ka = info.sparse ? info.K / 2 : info.K;
+  TORCH_CHECK(A.is_cuda() && B.is_cuda() && A.device() == B.device(),
+              "A and B must be on one GPU");
+  TORCH_CHECK(A.scalar_type() == info.in && B.scalar_type() == info.in, path,
+              ": A and B must be ", c10::toString(info.in));
+  TORCH_CHECK(A.sizes() == torch::IntArrayRef({tiles * info.M, ka}) &&
+                  B.sizes() == torch::IntArrayRef({info.K, info.M}),
+              path, ": shapes must be A [", tiles * info.M, ",", ka, "], B [", info.K, ",",
+              info.M, "]");
+  TORCH_CHECK(index.has_value() == info.sparse, path,
+              info.sparse ? ": a sparse path needs `index`" : ": a dense path takes no `index`");
+  if (info.sparse) {
+    const torch::Tensor& ix = *index;
+    TORCH_CHECK(ix.is_cuda() && ix.device() == A.device() && ix.scalar_type() == torch::kUInt8 &&
+                    ix.sizes() == A.sizes(),
+                path, ": index must be uint8 of A's shape on A's GPU");
+    TORCH_CHECK(ix.max().item<int>() < 4 &&
+                    ix.slice(1, 0, ka, 2).lt(ix.slice(1, 1, ka, 2)).all().item<bool>(),
+                path, ": index holds positions 0..3, increasing within each pair");
+  }
+  TORCH_CHECK(abid == 0 || (info.sparse && abid == 1), path,
+              ": abid must be 0, or 1 on a sparse path");
+  TORCH_CHECK(blocks >= 1 && blocks <= (1L << 16), "blocks must be in [1, 2^16]");
+  return id;
+}
+
+// largest exact `chain` of a path's burn: 4*K*chain within the accumulator's
+// integers, and at most the 2^22 MFMAs of a bounded run
+static long mat_chain_limit(const MatInfo& info) {
+  const long bound = info.out == torch::kFloat64 ? (1L << 53)
+                     : info.out == torch::kFloat32 ? (1L << 24) : (1L << 31);
+  return std::min(bound / (4 * info.K), 1L << 22);
+}
+
+static const unsigned char* mat_index_ptr(const c10::optional<torch::Tensor>& index) {
+  return index.has_value() ? index->data_ptr<unsigned char>() : nullptr;
+}
+
+// A: [M,K] (sparse [M,K/2] with index [M,K/2] uint8), B: [K,M].
+// Returns [waves, M, M] tiles in the accumulator's type.
+torch::Tensor matrix_tile(const std::string& path, torch::Tensor A, torch::Tensor B, long blocks,
+                          c10::optional<torch::Tensor> index, long abid) {
+  const int id = mat_check_operands(path, A, B, index, abid, blocks, 1);
+  const MatInfo& info = MAT_INFO[id];
+  A = A.contiguous();
+  B = B.contiguous();
+  if (index.has_value()) index = index->contiguous();
+  auto C = torch::empty({blocks * 4, info.M, info.M},
+                        torch::TensorOptions().dtype(info.out).device(A.device()));
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  dispatch_int<MAT_PATHS>(id, [&](auto path_c) {
+    constexpr int PATH = decltype(path_c)::value;
+    dispatch_int<MatPath<PATH>::SPARSE ? 2 : 1>((int)abid, [&](auto abid_c) {
+      hipLaunchKernelGGL((matrix_tile_kernel<PATH, decltype(abid_c)::value>), dim3(blocks),
+                         dim3(256), 0, stream, A.data_ptr(), B.data_ptr(), mat_index_ptr(index),
+                         C.data_ptr());
+    });
+  });
+  HIP_CHECK(hipGetLastError());
+  return C;
+}
+
+// A: [4M,K] (sparse [4M,K/2] with index), B: [K,M], expected: [4,M,M] in the
+// accumulator's type (= chain * A_n @ B), operands integers of magnitude <= 2.
+// One untimed warm-up launch, then one timed launch (warm_then_timed_ms).
+// Returns (records [waves,4] int32, elapsed_ms of the timed launch).
+std::tuple<torch::Tensor, double> matrix_burn(const std::string& path, torch::Tensor A,
+                                              torch::Tensor B, torch::Tensor expected, long blocks,
+                                              long chain, long rounds, long inject_wave,
+                                              long inject_round,
+                                              c10::optional<torch::Tensor> index, long abid) {
+  const int id = mat_check_operands(path, A, B, index, abid, blocks, MAT_NACC);
+  const MatInfo& info = MAT_INFO[id];
+  int which = -1;
+  for (int k = 0; k < MAT_BURN_PATHS; k++)
+    if (MAT_BURN_PATH[k] == id) which = k;
+  TORCH_CHECK(which >= 0, "no burn kernel for the path ", path);
+  TORCH_CHECK(expected.is_cuda() && expected.device() == A.device() &&
+                  expected.scalar_type() == info.out &&
+                  expected.sizes() == torch::IntArrayRef({MAT_NACC, info.M, info.M}),
+              path, ": expected must be ", c10::toString(info.out), " [4,", info.M, ",", info.M,
+              "] on the operands' GPU");
+  TORCH_CHECK(chain >= 1 && rounds >= 1, "chain and rounds must be >= 1");
+  TORCH_CHECK(chain <= mat_chain_limit(info), "chain ", chain, " breaks exactness for ", path,
+              " (limit ", mat_chain_limit(info), ")");
+  TORCH_CHECK(rounds <= (1L << 22) && chain * rounds <= (1L << 22),
+              "chain*rounds must be <= 2^22");
+  TORCH_CHECK(inject_wave >= -1 && inject_wave < blocks * 4 && inject_round >= -1 &&
+                  inject_round < rounds,
+              "inject_wave/inject_round out of range");
+  A = A.contiguous();
+  B = B.contiguous();
+  expected = expected.contiguous();
+  if (index.has_value()) index = index->contiguous();
+  auto records = zero_records(blocks * 4, 4, A.device());
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  const double ms = warm_then_timed_ms(stream, [&]() {
+    dispatch_int<MAT_BURN_PATHS>(which, [&](auto which_c) {
+      constexpr int PATH = MAT_BURN_PATH[decltype(which_c)::value];
+      dispatch_int<MatPath<PATH>::SPARSE ? 2 : 1>((int)abid, [&](auto abid_c) {
+        hipLaunchKernelGGL((matrix_burn_kernel<PATH, decltype(abid_c)::value>), dim3(blocks),
+                           dim3(256), 0, stream, A.data_ptr(), B.data_ptr(), mat_index_ptr(index),
+                           expected.data_ptr(), reinterpret_cast<int4*>(records.data_ptr<int>()),
+                           (int)chain, (int)rounds, (int)inject_wave, (int)inject_round);
+      });
     });
   });
   return std::make_tuple(records, ms);
@@ -4853,6 +5277,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Sustained MX block-scaled MFMA burn (fmt 0|2|4, shape 0|1) with per-lane scales and the "
         "scale byte select rotating every step, verified bitwise; returns (per-wave records "
         "[waves,4], ms)");
+  m.def("matrix_tile", &matrix_tile, py::arg("path"), py::arg("A"), py::arg("B"),
+        py::arg("blocks") = 2048, py::arg("index") = py::none(), py::arg("abid") = 0,
+        "Per-wave tile of one matrix path (f64, f32, f16, bf16, i8, fp8/bf8 MFMA shapes and the "
+        "2:4 sparse smfmac forms, named as in ops.MATRIX_PATHS); sparse paths take A compressed "
+        "with `index` (positions 0..3) and the index part select `abid`; returns [waves, M, M] "
+        "in the accumulator's type");
+  m.def("matrix_burn", &matrix_burn, py::arg("path"), py::arg("A"), py::arg("B"),
+        py::arg("expected"), py::arg("blocks") = 2048, py::arg("chain") = 256,
+        py::arg("rounds") = 64, py::arg("inject_wave") = -1, py::arg("inject_round") = -1,
+        py::arg("index") = py::none(), py::arg("abid") = 0,
+        "Sustained burn of one matrix path: rounds x chain dependent MFMAs on 4 accumulators per "
+        "wave, verified bitwise; returns (per-wave records [waves,4], ms)");
   m.def("p2p_gbps", &p2p_gbps, py::arg("src_dev"), py::arg("dst_dev"), py::arg("size_mb") = 256,
         py::arg("iters") = 10, "xGMI peer-to-peer copy bandwidth in GB/s");
   m.def("hbm_sweep", &hbm_sweep, py::arg("max_gib") = 16, py::arg("chunk_gib") = 4,
