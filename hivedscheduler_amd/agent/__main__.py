@@ -75,6 +75,12 @@ def main() -> None:
                          "sweeps); 0 = never")
     ap.add_argument("--matrix-probe", action="store_true",
                     help="with --local: also run the matrix-path probe")
+    ap.add_argument("--cvt-probe-every", type=int, default=0,
+                    help="conversion probe (fp8 / fp6 / fp4 / bf16 convert instructions, scaled, "
+                         "unscaled and stochastic rounding, exact sweep and a burn, per SIMD) every "
+                         "N sweeps (on deep sweeps); 0 = never")
+    ap.add_argument("--cvt-probe", action="store_true",
+                    help="with --local: also run the conversion probe")
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
@@ -94,7 +100,8 @@ def main() -> None:
                                      atomic_probe=args.atomic_probe,
                                      mx_scale_probe=args.mx_scale_probe,
                                      mempath_probe=args.mempath_probe,
-                                     matrix_probe=args.matrix_probe)
+                                     matrix_probe=args.matrix_probe,
+                                     cvt_probe=args.cvt_probe)
         if args.p2p_matrix:
             try:
                 m = p2p_link_matrix()
@@ -121,7 +128,8 @@ def main() -> None:
                             atomic_probe_every=args.atomic_probe_every,
                             mx_scale_probe_every=args.mx_scale_probe_every,
                             mempath_probe_every=args.mempath_probe_every,
-                            matrix_probe_every=args.matrix_probe_every)
+                            matrix_probe_every=args.matrix_probe_every,
+                            cvt_probe_every=args.cvt_probe_every)
     if args.once:
         import json
 

@@ -64,6 +64,7 @@ def collect_node_health(
     mx_scale_probe: bool = False,
     mempath_probe: bool = False,
     matrix_probe: bool = False,
+    cvt_probe: bool = False,
 ) -> dict:
     """One health sweep over all visible GPUs. deep=True also runs the HIP
     kernels (HBM + MFMA); sweep=True adds the 16 GiB HBM stuck-bit pattern
@@ -139,6 +140,14 @@ def collect_node_health(
     `matrix_bad_cus` (the CUs of any wave whose burn result was wrong, as xcc,
     se, sh, cu), and a failed probe marks the leaf bad.
 
+    cvt_probe=True (with deep) adds the conversion probe (every fp8 / fp6 /
+    fp4 / bf16 convert form over its operand table, exact and stochastic
+    rounding, and a burn): per GPU it records `cvt_probe_ok`, `cvt_sweep_ok`,
+    `cvt_burn_ok`, `cvt_gcvt_per_s` ({section: 1e9 conversions per second},
+    reported, not judged) and `cvt_bad_simds` (the SIMDs of any wave whose
+    result was wrong, as xcc, se, sh, cu, simd), and a failed probe marks the
+    leaf bad.
+
     The stuck-bit scan transiently holds up to 16 GiB of HBM; on a GPU
     running tenant jobs this can make the tenant's own allocations fail.
     Keep sweep on the low-frequency cadence and prefer idle GPUs (the
@@ -162,7 +171,8 @@ def collect_node_health(
         kwargs = _set_flags(burn=burn, lds_march=lds_march, hbm_march=hbm_march,
                             simd_probe=simd_probe, scalar_probe=scalar_probe,
                             atomic_probe=atomic_probe, mx_scale_probe=mx_scale_probe,
-                            mempath_probe=mempath_probe, matrix_probe=matrix_probe)
+                            mempath_probe=mempath_probe, matrix_probe=matrix_probe,
+                            cvt_probe=cvt_probe)
         for i in range(n):
             gpu = report["gpus"][str(i)]
             try:
@@ -287,6 +297,18 @@ def collect_node_health(
                     )
                     if not p["ok"] or p["bad_cus"]:
                         gpu["healthy"] = False
+                if cvt_probe:
+                    p = rep["cvt_probe"]
+                    gpu.update(
+                        cvt_probe_ok=bool(p["ok"]),
+                        cvt_sweep_ok=bool(p["sweep"]["ok"]),
+                        cvt_burn_ok=bool(p["burn"]["ok"]),
+                        cvt_gcvt_per_s={name: round(s["gcvt_per_s"], 1)
+                                        for name, s in p["burn"]["sections"].items()},
+                        cvt_bad_simds=p["bad_simds"],
+                    )
+                    if not p["ok"] or p["bad_simds"]:
+                        gpu["healthy"] = False
             except Exception as e:
                 gpu.update(healthy=False, error=str(e)[:200])
     if probe_pairs and n >= 2:
@@ -363,7 +385,8 @@ class NodeHealthAgent:
                  hbm_march_every: int = 0, min_xcd_ratio: Optional[float] = None,
                  simd_probe_every: int = 0, scalar_probe_every: int = 0,
                  atomic_probe_every: int = 0, mx_scale_probe_every: int = 0,
-                 mempath_probe_every: int = 0, matrix_probe_every: int = 0):
+                 mempath_probe_every: int = 0, matrix_probe_every: int = 0,
+                 cvt_probe_every: int = 0):
         self.scheduler_url = scheduler_url.rstrip("/")
         self.node_name = node_name or socket.gethostname()
         self.interval_s = interval_s
@@ -414,6 +437,9 @@ class NodeHealthAgent:
         # matrix instructions), same pattern; 0 = never (about 0.1 s of
         # matrix-core time per GPU, on cores a tenant may be using)
         self.matrix_probe_every = matrix_probe_every
+        # conversion probe cadence (fp8 / fp6 / fp4 / bf16 converters, per
+        # SIMD), same pattern; 0 = never
+        self.cvt_probe_every = cvt_probe_every
         self._rounds = 0
 
     def post_report(self, report: dict) -> bool:
@@ -474,7 +500,8 @@ class NodeHealthAgent:
                             atomic_probe=deep and self._due(self.atomic_probe_every),
                             mx_scale_probe=deep and self._due(self.mx_scale_probe_every),
                             mempath_probe=deep and self._due(self.mempath_probe_every),
-                            matrix_probe=deep and self._due(self.matrix_probe_every))
+                            matrix_probe=deep and self._due(self.matrix_probe_every),
+                            cvt_probe=deep and self._due(self.cvt_probe_every))
         self._rounds += 1
         if "burn" in kwargs:
             kwargs["min_mfma_tflops"] = self.min_mfma_tflops

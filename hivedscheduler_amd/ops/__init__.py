@@ -5,7 +5,8 @@ extension is REQUIRED: failure to load raises (no silent eager fallback).
 
 Here: the loader, `gpu_health_report` and the single-tile MFMA checks. Each
 opt-in probe has a module of its own (mfma_burn, lds_march, hbm_march,
-simd_probe, scalar_probe, atomic_probe, mx_scale, mempath_probe, matrix_paths)
+simd_probe, scalar_probe, atomic_probe, mx_scale, mempath_probe, matrix_paths,
+cvt_probe)
 on top of `records`, and the
 single-tile checks' operands and verdict are in mfma_tiles; their public names
 are re-exported here, and their report functions reach the extension through
@@ -23,6 +24,12 @@ from .atomic_probe import (ATOMIC_CELLS, ATOMIC_FP_OPS, ATOMIC_INT_OPS,  # noqa:
                            atomic_reduce_contributions, atomic_reduce_expected,
                            contend_lanes_on_cell, summarize_atomic_burn,
                            summarize_atomic_contend)
+from .cvt_probe import (CVT_BURN_SECTIONS, CVT_FORMATS, CVT_PATHS, CVT_SCALE_EXPS,  # noqa: F401
+                        CVT_SCALE_EXPS_F16, CVT_SR_PATHS, cvt_scale_exps, cvt_burn_expected, cvt_burn_report, cvt_decode_expected,
+                        cvt_decode_value, cvt_elements, cvt_encode_expected, cvt_finite_codes,
+                        cvt_max_normal, cvt_old, cvt_operands, cvt_pack6, cvt_path_info,
+                        cvt_probe_report, cvt_sr_bracket, cvt_sweep_report, cvt_unpack6,
+                        summarize_cvt_burn, summarize_cvt_sweep)
 from .hbm_march import (HBM_MARCH_TILE_BYTES, hbm_march_pattern, hbm_march_report,  # noqa: F401
                         hbm_slow_xcds, summarize_hbm_march)
 from .lds_march import (LDS_MARCH_WORDS, lds_march_block_checksum, lds_march_pattern,  # noqa: F401
@@ -93,7 +100,7 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
                       hbm_march: bool = False, simd_probe: bool = False,
                       scalar_probe: bool = False, atomic_probe: bool = False,
                       mx_scale_probe: bool = False, mempath_probe: bool = False,
-                      matrix_probe: bool = False) -> dict:
+                      matrix_probe: bool = False, cvt_probe: bool = False) -> dict:
     """Run the health-probe kernels on one GPU and return measured facts.
 
     Feeds leaf-cell healthiness: HBM bandwidth deficit, MFMA mismatch, or
@@ -159,6 +166,12 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     forms, as exact tiles and as a burn of tens of milliseconds per burn
     path) as report["matrix_probe"] and ANDs its verdict into `healthy`. Off
     by default, and the report is then unchanged.
+
+    cvt_probe=True adds the conversion probe (`cvt_probe_report`: every
+    fp8 / fp6 / fp4 / bf16 convert form over its whole operand table, exact and
+    stochastic rounding, and a burn of tens of milliseconds per section, per
+    SIMD) as report["cvt_probe"] and ANDs its verdict into `healthy`. Off by
+    default, and the report is then unchanged.
     """
     ops = _ops_on(device)
     size_mb = 256 if quick else 2048
@@ -231,6 +244,9 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     if matrix_probe:
         report["matrix_probe"] = matrix_probe_report(device)
         report["healthy"] = bool(report["healthy"] and report["matrix_probe"]["ok"])
+    if cvt_probe:
+        report["cvt_probe"] = cvt_probe_report(device)
+        report["healthy"] = bool(report["healthy"] and report["cvt_probe"]["ok"])
     return report
 
 

@@ -43,6 +43,9 @@
 //                bounds check at sharp lengths, direct-to-LDS loads and the
 //                sub-dword, d16 and wide forms, every value verified bitwise;
 //                the CU and instruction form of any mismatch
+//  - cvt_sweep / cvt_burn: the fp8 / fp6 / fp4 / bf16 conversion instructions,
+//                scaled, unscaled and stochastic rounding, every select, bitwise
+//                against a host mirror; the SIMD of any wave that was wrong
 //  - p2p copy:   xGMI link bandwidth between two GPUs (expected ~153 GB/s per
 //                link per direction); a degraded link marks the PAIR cell bad
 //
@@ -5224,6 +5227,725 @@ std::tuple<torch::Tensor, double> mempath_probe(const std::string& section, long
   return std::make_tuple(records, ms);
 }
 
+// ---------------------------------------------------------------------------
+// Conversion probe: the gfx950 narrow-format converters, which quantise to
+// fp8 / fp6 / fp4 on the way into the MFMA and dequantise on the way out and
+// which no probe above issues. Two kernels: cvt_sweep walks a host-built table
+// of operands through one instruction form and compares every result bitwise;
+// cvt_burn is the sustained register-only run in the VALU burn's shape. The
+// host mirror is ops/cvt_probe.py.
+//
+// A path is one instruction form (CVT_PATH_NAMES, index-aligned with
+// CvtPathTypes). Formats are OCP: fp8 = e4m3, bf8 = e5m2, fp6 = e2m3,
+// bf6 = e3m2, fp4 = e2m1. What the instructions do, measured on an MI355X
+// (BENCHMARKS.md "Conversion probe"):
+//   scale   an f32 operand of which only the exponent is used; an encode
+//           converts src / 2^s, a decode returns value * 2^s
+//   pk 8    v_cvt_scalef32_pk_{fp8,bf8}_{f32,f16,bf16}, v_cvt_pk_{fp8,bf8}_f32:
+//           two codes, src0 in the low byte, into the half of the destination
+//           the word select names; the other half keeps `old`
+//   pk 4    v_cvt_scalef32_pk_fp4_*: two codes, src0 in the low nibble, into
+//           the byte the select names; the other three bytes keep `old`
+//   fp6     v_cvt_scalef32_2xpk16_{fp6,bf6}_f32 takes two 16-element sources
+//           and INTERLEAVES them: code 2i is src0[i], code 2i+1 is src1[i], six
+//           bits apiece from bit 0 of the first dword, the packing mx_pack feeds
+//           the MFMA. The kernel passes elements 0,2,4.. as src0 and 1,3,5.. as
+//           src1, so a table entry's 32 values come out in their own order.
+//           v_cvt_scalef32_pk32_f32_{fp6,bf6} and the sr_pk32 forms take one
+//           32-element operand in plain order.
+//   decode  pk forms read the half (8-bit) or byte (fp4) the select names, the
+//           low code first; the byte-select forms read one byte
+//   sr      v_cvt_scalef32_sr_* and v_cvt_sr_*_f32 round to one of the two
+//           neighbours by a random word: an exactly representable input gives
+//           its own code whatever the word. They keep `old` outside the byte
+//           they write and that is checked (sr_pk_fp4 through assembly, see
+//           CvtSr4)
+// Every value of every select is its own `if constexpr` arm and every entry
+// runs through all of them. `old` is fmix32(entry * 0x9E3779B1 + 0x85EBCA6B);
+// an exact path's expected dword holds old's bits outside the written field,
+// so a converter that disturbs the preserved part mismatches like a wrong code.
+//
+// Table: `entries` packs. Entry e is IN dwords of `inputs` (wide values for an
+// encode, packed codes for a decode), scales[e] and WANT dwords of `expected`;
+// the path produces GOT dwords and dword k is compared with expected dword
+// k % WANT. For a stochastic-rounding path a produced dword is one code (bit
+// 16 set if the preserved part of the destination changed) and the expected
+// dword holds the two bracket codes, low byte and next byte; it matches
+// either. The random word advances once per entry with v_prng_b32 from
+// fmix32(seed + lane * 0x85EBCA6B) | 1.
+//
+// Work split: 256 threads, one wave per SIMD. The block stages the three
+// arrays from global memory into LDS once, 16 B per lane, then every wave
+// walks the WHOLE table out of LDS, lane l taking entries l, l + 64, ..: each
+// SIMD of the CU converts every operand. Nothing touches global memory between
+// the staging and the record.
+//
+// Lane 0 of each wave writes one record of eight int32 (store_record8):
+//   [0] placement word (hw_word; the SIMD is HW_ID[5:4])
+//   [1] mismatched entries
+//   [2] lowest bad entry (-1 if none)
+//   [3] [4] the first mismatching produced dword of that entry and what was
+//       expected there
+//   [5] [6] checksum of every produced dword: xor, and xor of the dword times
+//       (2 * position + 1)
+//   [7] 0
+// A stochastic-rounding path's checksum depends on which neighbour each entry
+// took; it is the same in every healthy wave (same seed, same entries) and the
+// host compares it by consensus, which names a SIMD that disagrees and cannot
+// see a fault common to all.
+// ---------------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(2))) short cvt_s2;
+typedef __attribute__((ext_vector_type(2))) _Float16 cvt_h2;
+typedef __attribute__((ext_vector_type(2))) __bf16 cvt_y2;
+typedef __attribute__((ext_vector_type(32))) float f32x32;
+typedef __attribute__((ext_vector_type(6))) unsigned u32x6;
+
+constexpr int CVT_LDS_DWORDS = 32768;  // 128 KiB staging area
+enum { CVT_FP8, CVT_BF8, CVT_FP6, CVT_BF6, CVT_FP4 };
+enum { CVT_F32, CVT_F16, CVT_BF16 };
+
+template <typename T> __device__ __forceinline__ unsigned cvt_bits(T v) {
+  static_assert(sizeof(T) == 4, "one dword");
+  return __builtin_bit_cast(unsigned, v);
+}
+
+template <int IN_, int WANT_, int GOT_, bool SR_ = false> struct CvtShape {
+  static constexpr int IN = IN_, WANT = WANT_, GOT = GOT_;
+  static constexpr bool SR = SR_;
+};
+
+// f32 / f16 / bf16 to two 8-bit codes, scaled; both word selects
+template <int FMT, int W> struct CvtEnc8 : CvtShape<(W == CVT_F32 ? 2 : 1), 2, 2> {
+  template <bool HI>
+  static __device__ __forceinline__ unsigned one(const unsigned* in, float sc, cvt_s2 o) {
+    if constexpr (W == CVT_F32) {
+      const float a = __uint_as_float(in[0]), b = __uint_as_float(in[1]);
+      if constexpr (FMT == CVT_FP8)
+        return cvt_bits(__builtin_amdgcn_cvt_scalef32_pk_fp8_f32(o, a, b, sc, HI));
+      else
+        return cvt_bits(__builtin_amdgcn_cvt_scalef32_pk_bf8_f32(o, a, b, sc, HI));
+    } else if constexpr (W == CVT_F16) {
+      const cvt_h2 h = __builtin_bit_cast(cvt_h2, in[0]);
+      if constexpr (FMT == CVT_FP8)
+        return cvt_bits(__builtin_amdgcn_cvt_scalef32_pk_fp8_f16(o, h, sc, HI));
+      else
+        return cvt_bits(__builtin_amdgcn_cvt_scalef32_pk_bf8_f16(o, h, sc, HI));
+    } else {
+      const cvt_y2 y = __builtin_bit_cast(cvt_y2, in[0]);
+      if constexpr (FMT == CVT_FP8)
+        return cvt_bits(__builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(o, y, sc, HI));
+      else
+        return cvt_bits(__builtin_amdgcn_cvt_scalef32_pk_bf8_bf16(o, y, sc, HI));
+    }
+  }
+  static __device__ __forceinline__ void run(const unsigned* in, float sc, unsigned old,
+                                             unsigned rnd, unsigned* got) {
+    const cvt_s2 o = __builtin_bit_cast(cvt_s2, old);
+    got[0] = one<false>(in, sc, o);
+    got[1] = one<true>(in, sc, o);
+  }
+};
+
+// to two fp4 codes in the byte SEL names; all four byte selects
+template <int W> struct CvtEnc4 : CvtShape<(W == CVT_F32 ? 2 : 1), 4, 4> {
+  template <int SEL>
+  static __device__ __forceinline__ unsigned one(const unsigned* in, float sc, unsigned old) {
+    if constexpr (W == CVT_F32)
+      return __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(old, __uint_as_float(in[0]),
+                                                      __uint_as_float(in[1]), sc, SEL);
+    else if constexpr (W == CVT_F16)
+      return __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(old, __builtin_bit_cast(cvt_h2, in[0]), sc,
+                                                      SEL);
+    else
+      return __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(old, __builtin_bit_cast(cvt_y2, in[0]), sc,
+                                                       SEL);
+  }
+  static __device__ __forceinline__ void run(const unsigned* in, float sc, unsigned old,
+                                             unsigned rnd, unsigned* got) {
+    got[0] = one<0>(in, sc, old);
+    got[1] = one<1>(in, sc, old);
+    got[2] = one<2>(in, sc, old);
+    got[3] = one<3>(in, sc, old);
+  }
+};
+
+// The 32-element converters write 6 or 32 VGPRs in several passes, and the
+// compiler does not mark their destination early-clobber: in cvt_burn's fp6
+// step it allocated `v_cvt_scalef32_2xpk16_fp6_f32 v[38:43], v[0:15],
+// v[16:31], v38`, the scale in the first destination register, and every wave
+// then produced the same wrong codes (BENCHMARKS.md "Conversion probe"). An
+// operand that is still live after the instruction cannot share a register
+// with its result, so each wrapper below keeps its operands alive past it.
+template <typename T> __device__ __forceinline__ void cvt_keep(const T& v) {
+  asm volatile("" : : "v"(v));
+}
+
+// 32 f32 to 32 six-bit codes in six dwords (the interleave: see above)
+template <int FMT>
+__device__ __forceinline__ u32x6 cvt_enc6(const unsigned* in, float sc) {
+  f32x16 a, b;
+#pragma unroll
+  for (int i = 0; i < 16; i++) {
+    a[i] = __uint_as_float(in[2 * i]);
+    b[i] = __uint_as_float(in[2 * i + 1]);
+  }
+  u32x6 p;
+  if constexpr (FMT == CVT_FP6) p = __builtin_amdgcn_cvt_scalef32_2xpk16_fp6_f32(a, b, sc);
+  else p = __builtin_amdgcn_cvt_scalef32_2xpk16_bf6_f32(a, b, sc);
+  cvt_keep(a);
+  cvt_keep(b);
+  cvt_keep(sc);
+  return p;
+}
+template <int FMT> __device__ __forceinline__ f32x32 cvt_dec6(u32x6 p, float sc) {
+  f32x32 q;
+  if constexpr (FMT == CVT_FP6) q = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(p, sc);
+  else q = __builtin_amdgcn_cvt_scalef32_pk32_f32_bf6(p, sc);
+  cvt_keep(p);
+  cvt_keep(sc);
+  return q;
+}
+template <int FMT> struct CvtEnc6 : CvtShape<32, 6, 6> {
+  static __device__ __forceinline__ void run(const unsigned* in, float sc, unsigned old,
+                                             unsigned rnd, unsigned* got) {
+    const u32x6 p = cvt_enc6<FMT>(in, sc);
+#pragma unroll
+    for (int i = 0; i < 6; i++) got[i] = p[i];
+  }
+};
+template <int FMT> struct CvtDec6 : CvtShape<6, 32, 32> {
+  static __device__ __forceinline__ void run(const unsigned* in, float sc, unsigned old,
+                                             unsigned rnd, unsigned* got) {
+    const u32x6 p = {in[0], in[1], in[2], in[3], in[4], in[5]};
+    const f32x32 q = cvt_dec6<FMT>(p, sc);
+#pragma unroll
+    for (int i = 0; i < 32; i++) got[i] = __float_as_uint(q[i]);
+  }
+};
+
+// four 8-bit codes to f32 (four dwords) or f16 / bf16 (two), scaled, through
+// the packed form: both word selects
+template <int FMT, int W> struct CvtDec8 : CvtShape<1, (W == CVT_F32 ? 4 : 2), (W == CVT_F32 ? 4 : 2)> {
+  template <bool HI>
+  static __device__ __forceinline__ void one(unsigned src, float sc, unsigned* got) {
+    if constexpr (W == CVT_F32) {
+      f32x2 d;
+      if constexpr (FMT == CVT_FP8) d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(src, sc, HI);
+      else d = __builtin_amdgcn_cvt_scalef32_pk_f32_bf8(src, sc, HI);
+      got[2 * HI] = __float_as_uint(d[0]);
+      got[2 * HI + 1] = __float_as_uint(d[1]);
+    } else if constexpr (W == CVT_F16) {
+      if constexpr (FMT == CVT_FP8)
+        got[HI] = cvt_bits(__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(src, sc, HI));
+      else
+        got[HI] = cvt_bits(__builtin_amdgcn_cvt_scalef32_pk_f16_bf8(src, sc, HI));
+    } else {
+      if constexpr (FMT == CVT_FP8)
+        got[HI] = cvt_bits(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(src, sc, HI));
+      else
+        got[HI] = cvt_bits(__builtin_amdgcn_cvt_scalef32_pk_bf16_bf8(src, sc, HI));
+    }
+  }
+  static __device__ __forceinline__ void run(const unsigned* in, float sc, unsigned old,
+                                             unsigned rnd, unsigned* got) {
+    one<false>(in[0], sc, got);
+    one<true>(in[0], sc, got);
+  }
+};
+
+// four 8-bit codes to f32 through the byte-select form, scaled or not
+template <int FMT, bool SCALED> struct CvtDecB8 : CvtShape<1, 4, 4> {
+  template <int SEL> static __device__ __forceinline__ unsigned one(unsigned src, float sc) {
+    if constexpr (SCALED) {
+      if constexpr (FMT == CVT_FP8)
+        return __float_as_uint(__builtin_amdgcn_cvt_scalef32_f32_fp8(src, sc, SEL));
+      else
+        return __float_as_uint(__builtin_amdgcn_cvt_scalef32_f32_bf8(src, sc, SEL));
+    } else {
+      if constexpr (FMT == CVT_FP8) return __float_as_uint(__builtin_amdgcn_cvt_f32_fp8(src, SEL));
+      else return __float_as_uint(__builtin_amdgcn_cvt_f32_bf8(src, SEL));
+    }
+  }
+  static __device__ __forceinline__ void run(const unsigned* in, float sc, unsigned old,
+                                             unsigned rnd, unsigned* got) {
+    got[0] = one<0>(in[0], sc);
+    got[1] = one<1>(in[0], sc);
+    got[2] = one<2>(in[0], sc);
+    got[3] = one<3>(in[0], sc);
+  }
+};
+
+// eight fp4 codes to f32 (eight dwords) or f16 / bf16 (four): all byte selects
+template <int W> struct CvtDec4 : CvtShape<1, (W == CVT_F32 ? 8 : 4), (W == CVT_F32 ? 8 : 4)> {
+  template <int SEL>
+  static __device__ __forceinline__ void one(unsigned src, float sc, unsigned* got) {
+    if constexpr (W == CVT_F32) {
+      const f32x2 d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(src, sc, SEL);
+      got[2 * SEL] = __float_as_uint(d[0]);
+      got[2 * SEL + 1] = __float_as_uint(d[1]);
+    } else if constexpr (W == CVT_F16) {
+      got[SEL] = cvt_bits(__builtin_amdgcn_cvt_scalef32_pk_f16_fp4(src, sc, SEL));
+    } else {
+      got[SEL] = cvt_bits(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(src, sc, SEL));
+    }
+  }
+  static __device__ __forceinline__ void run(const unsigned* in, float sc, unsigned old,
+                                             unsigned rnd, unsigned* got) {
+    one<0>(in[0], sc, got);
+    one<1>(in[0], sc, got);
+    one<2>(in[0], sc, got);
+    one<3>(in[0], sc, got);
+  }
+};
+
+// the unscaled v_cvt_pk_{fp8,bf8}_f32 and v_cvt_pk_f32_{fp8,bf8}
+template <int FMT> struct CvtEncU8 : CvtShape<2, 2, 2> {
+  template <bool HI> static __device__ __forceinline__ unsigned one(float a, float b, int old) {
+    if constexpr (FMT == CVT_FP8) return (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, old, HI);
+    else return (unsigned)__builtin_amdgcn_cvt_pk_bf8_f32(a, b, old, HI);
+  }
+  static __device__ __forceinline__ void run(const unsigned* in, float sc, unsigned old,
+                                             unsigned rnd, unsigned* got) {
+    const float a = __uint_as_float(in[0]), b = __uint_as_float(in[1]);
+    got[0] = one<false>(a, b, (int)old);
+    got[1] = one<true>(a, b, (int)old);
+  }
+};
+template <int FMT> struct CvtDecU8 : CvtShape<1, 4, 4> {
+  template <bool HI> static __device__ __forceinline__ void one(unsigned src, unsigned* got) {
+    f32x2 d;
+    if constexpr (FMT == CVT_FP8) d = __builtin_amdgcn_cvt_pk_f32_fp8((int)src, HI);
+    else d = __builtin_amdgcn_cvt_pk_f32_bf8((int)src, HI);
+    got[2 * HI] = __float_as_uint(d[0]);
+    got[2 * HI + 1] = __float_as_uint(d[1]);
+  }
+  static __device__ __forceinline__ void run(const unsigned* in, float sc, unsigned old,
+                                             unsigned rnd, unsigned* got) {
+    one<false>(in[0], got);
+    one<true>(in[0], got);
+  }
+};
+
+// two f32 to a bf16 pair: the plain cast pair is v_cvt_pk_bf16_f32
+struct CvtEncBf16 : CvtShape<2, 1, 1> {
+  static __device__ __forceinline__ void run(const unsigned* in, float sc, unsigned old,
+                                             unsigned rnd, unsigned* got) {
+    const cvt_y2 c = {(__bf16)__uint_as_float(in[0]), (__bf16)__uint_as_float(in[1])};
+    got[0] = cvt_bits(c);
+  }
+};
+
+// stochastic rounding. A produced dword is the code, with bit 16 set when the
+// destination outside the written field no longer equals `old`.
+__device__ __forceinline__ unsigned cvt_sr_field(unsigned d, unsigned old, int shift,
+                                                 unsigned field) {
+  return ((d >> shift) & field) | ((((d ^ old) & ~(field << shift)) != 0) ? 0x10000u : 0u);
+}
+template <int FMT, bool SCALED> struct CvtSr8 : CvtShape<1, 1, 4, true> {
+  template <int SEL>
+  static __device__ __forceinline__ unsigned one(float x, float sc, unsigned old, unsigned rnd) {
+    unsigned d;
+    if constexpr (SCALED) {
+      if constexpr (FMT == CVT_FP8)
+        d = (unsigned)__builtin_amdgcn_cvt_scalef32_sr_fp8_f32((int)old, x, rnd, sc, SEL);
+      else
+        d = (unsigned)__builtin_amdgcn_cvt_scalef32_sr_bf8_f32((int)old, x, rnd, sc, SEL);
+    } else {
+      if constexpr (FMT == CVT_FP8)
+        d = (unsigned)__builtin_amdgcn_cvt_sr_fp8_f32(x, (int)rnd, (int)old, SEL);
+      else
+        d = (unsigned)__builtin_amdgcn_cvt_sr_bf8_f32(x, (int)rnd, (int)old, SEL);
+    }
+    return cvt_sr_field(d, old, 8 * SEL, 0xFFu);
+  }
+  static __device__ __forceinline__ void run(const unsigned* in, float sc, unsigned old,
+                                             unsigned rnd, unsigned* got) {
+    const float x = __uint_as_float(in[0]);
+    got[0] = one<0>(x, sc, old, rnd);
+    got[1] = one<1>(x, sc, old, rnd);
+    got[2] = one<2>(x, sc, old, rnd);
+    got[3] = one<3>(x, sc, old, rnd);
+  }
+};
+struct CvtSr4 : CvtShape<2, 2, 8, true> {
+  template <int SEL>
+  static __device__ __forceinline__ void one(f32x2 x, float sc, unsigned old, unsigned rnd,
+                                             unsigned* got) {
+    // Issued as assembly: the compiler does not tie the `old` operand of
+    // __builtin_amdgcn_cvt_scalef32_sr_pk_fp4_f32 to the destination (it emits
+    // the instruction into a fresh, uninitialised register), so through the
+    // builtin the three bytes the instruction leaves alone are undefined. Here
+    // the destination is a "+v" register that holds `old`. The byte select is
+    // op_sel[2] (bit 0) and op_sel[3] (bit 1), as the builtin encodes it.
+    unsigned d = old;
+    if constexpr (SEL == 0)
+      asm volatile("v_cvt_scalef32_sr_pk_fp4_f32 %0, %1, %2, %3"
+                   : "+v"(d) : "v"(x), "v"(rnd), "v"(sc));
+    else if constexpr (SEL == 1)
+      asm volatile("v_cvt_scalef32_sr_pk_fp4_f32 %0, %1, %2, %3 op_sel:[0,0,1,0]"
+                   : "+v"(d) : "v"(x), "v"(rnd), "v"(sc));
+    else if constexpr (SEL == 2)
+      asm volatile("v_cvt_scalef32_sr_pk_fp4_f32 %0, %1, %2, %3 op_sel:[0,0,0,1]"
+                   : "+v"(d) : "v"(x), "v"(rnd), "v"(sc));
+    else
+      asm volatile("v_cvt_scalef32_sr_pk_fp4_f32 %0, %1, %2, %3 op_sel:[0,0,1,1]"
+                   : "+v"(d) : "v"(x), "v"(rnd), "v"(sc));
+    const unsigned byte = cvt_sr_field(d, old, 8 * SEL, 0xFFu);  // both codes and the flag
+    got[2 * SEL] = byte & 0x1000Fu;
+    got[2 * SEL + 1] = ((byte >> 4) & 0xFu) | (byte & 0x10000u);
+  }
+  static __device__ __forceinline__ void run(const unsigned* in, float sc, unsigned old,
+                                             unsigned rnd, unsigned* got) {
+    const f32x2 x = {__uint_as_float(in[0]), __uint_as_float(in[1])};
+    one<0>(x, sc, old, rnd, got);
+    one<1>(x, sc, old, rnd, got);
+    one<2>(x, sc, old, rnd, got);
+    one<3>(x, sc, old, rnd, got);
+  }
+};
+template <int FMT> struct CvtSr6 : CvtShape<32, 32, 32, true> {
+  static __device__ __forceinline__ void run(const unsigned* in, float sc, unsigned old,
+                                             unsigned rnd, unsigned* got) {
+    f32x32 v;
+#pragma unroll
+    for (int i = 0; i < 32; i++) v[i] = __uint_as_float(in[i]);
+    u32x6 p;
+    if constexpr (FMT == CVT_FP6) p = __builtin_amdgcn_cvt_scalef32_sr_pk32_fp6_f32(v, rnd, sc);
+    else p = __builtin_amdgcn_cvt_scalef32_sr_pk32_bf6_f32(v, rnd, sc);
+    cvt_keep(v);
+    cvt_keep(rnd);
+    cvt_keep(sc);
+#pragma unroll
+    for (int j = 0; j < 32; j++) {
+      const int bit = 6 * j, word = bit >> 5, at = bit & 31;
+      unsigned code = p[word] >> at;
+      if (at + 6 > 32) code |= p[word + 1] << (32 - at);
+      got[j] = code & 63u;
+    }
+  }
+};
+
+// index-aligned with CVT_PATH_NAMES
+typedef std::tuple<
+    CvtEnc8<CVT_FP8, CVT_F32>, CvtEnc8<CVT_BF8, CVT_F32>, CvtEnc8<CVT_FP8, CVT_F16>,
+    CvtEnc8<CVT_BF8, CVT_F16>, CvtEnc8<CVT_FP8, CVT_BF16>, CvtEnc8<CVT_BF8, CVT_BF16>,
+    CvtEnc4<CVT_F32>, CvtEnc4<CVT_F16>, CvtEnc4<CVT_BF16>, CvtEnc6<CVT_FP6>, CvtEnc6<CVT_BF6>,
+    CvtDec8<CVT_FP8, CVT_F32>, CvtDec8<CVT_BF8, CVT_F32>, CvtDec8<CVT_FP8, CVT_F16>,
+    CvtDec8<CVT_BF8, CVT_F16>, CvtDec8<CVT_FP8, CVT_BF16>, CvtDec8<CVT_BF8, CVT_BF16>,
+    CvtDecB8<CVT_FP8, true>, CvtDecB8<CVT_BF8, true>, CvtDec4<CVT_F32>, CvtDec4<CVT_F16>,
+    CvtDec4<CVT_BF16>, CvtDec6<CVT_FP6>, CvtDec6<CVT_BF6>, CvtEncU8<CVT_FP8>, CvtEncU8<CVT_BF8>,
+    CvtDecU8<CVT_FP8>, CvtDecU8<CVT_BF8>, CvtDecB8<CVT_FP8, false>, CvtDecB8<CVT_BF8, false>,
+    CvtEncBf16, CvtSr8<CVT_FP8, true>, CvtSr8<CVT_BF8, true>, CvtSr4, CvtSr6<CVT_FP6>,
+    CvtSr6<CVT_BF6>, CvtSr8<CVT_FP8, false>, CvtSr8<CVT_BF8, false>>
+    CvtPathTypes;
+constexpr int CVT_PATHS = std::tuple_size<CvtPathTypes>::value;
+static const char* const CVT_PATH_NAMES[CVT_PATHS] = {
+    "enc_fp8_f32",  "enc_bf8_f32",  "enc_fp8_f16",   "enc_bf8_f16",   "enc_fp8_bf16",
+    "enc_bf8_bf16", "enc_fp4_f32",  "enc_fp4_f16",   "enc_fp4_bf16",  "enc_fp6_f32",
+    "enc_bf6_f32",  "dec_f32_fp8",  "dec_f32_bf8",   "dec_f16_fp8",   "dec_f16_bf8",
+    "dec_bf16_fp8", "dec_bf16_bf8", "decb_f32_fp8",  "decb_f32_bf8",  "dec_f32_fp4",
+    "dec_f16_fp4",  "dec_bf16_fp4", "dec_f32_fp6",   "dec_f32_bf6",   "encu_fp8_f32",
+    "encu_bf8_f32", "decu_f32_fp8", "decu_f32_bf8",  "decub_f32_fp8", "decub_f32_bf8",
+    "enc_bf16_f32", "sr_fp8_f32",   "sr_bf8_f32",    "sr_fp4_f32",    "sr_fp6_f32",
+    "sr_bf6_f32",   "sru_fp8_f32",  "sru_bf8_f32"};
+
+// where the scales and the expected dwords start in the staging area: each
+// array begins on a 16 B boundary
+__host__ __device__ constexpr int cvt_round4(int n) { return (n + 3) & ~3; }
+
+// n dwords from 16 B aligned global memory into 16 B aligned LDS, 16 B per lane
+__device__ __forceinline__ void cvt_stage(unsigned* __restrict__ dst,
+                                          const unsigned* __restrict__ src, int n) {
+  const uint4* src4 = reinterpret_cast<const uint4*>(src);
+  uint4* dst4 = reinterpret_cast<uint4*>(dst);
+  for (int i = threadIdx.x; i < (n >> 2); i += blockDim.x) dst4[i] = src4[i];
+  for (int i = (n & ~3) + threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
+}
+
+template <typename P>
+__global__ void __launch_bounds__(256)
+cvt_sweep_kernel(const unsigned* __restrict__ inputs, const unsigned* __restrict__ scales,
+                 const unsigned* __restrict__ expected, int4* __restrict__ records, int entries,
+                 unsigned seed) {
+  __shared__ uint4 staged[CVT_LDS_DWORDS / 4];
+  unsigned* lds = reinterpret_cast<unsigned*>(staged);
+  const int off_scale = cvt_round4(entries * P::IN);
+  const int off_want = off_scale + cvt_round4(entries);
+  cvt_stage(lds, inputs, entries * P::IN);
+  cvt_stage(lds + off_scale, scales, entries);
+  cvt_stage(lds + off_want, expected, entries * P::WANT);
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const unsigned place = hw_word();
+  unsigned rnd = fmix32(seed + (unsigned)lane * 0x85EBCA6Bu) | 1u;
+  unsigned mismatched = 0, first = 0x7FFFFFFFu, first_got = 0, first_want = 0;
+  unsigned sum_lo = 0, sum_hi = 0;
+  for (int e = lane; e < entries; e += 64) {
+    unsigned in[P::IN], want[P::WANT], got[P::GOT];
+#pragma unroll
+    for (int j = 0; j < P::IN; j++) in[j] = lds[e * P::IN + j];
+#pragma unroll
+    for (int j = 0; j < P::WANT; j++) want[j] = lds[off_want + e * P::WANT + j];
+    const float sc = __uint_as_float(lds[off_scale + e]);
+    const unsigned old = fmix32((unsigned)e * 0x9E3779B1u + 0x85EBCA6Bu);
+    if constexpr (P::SR) rnd = __builtin_amdgcn_prng_b32(rnd);
+    P::run(in, sc, old, rnd, got);
+    bool bad = false;
+    unsigned bad_got = 0, bad_want = 0;
+#pragma unroll
+    for (int k = P::GOT - 1; k >= 0; k--) {  // downwards: the first bad dword is kept
+      const unsigned w = want[k % P::WANT];
+      bool same = got[k] == w;
+      if constexpr (P::SR) same = got[k] == (w & 0xFFu) || got[k] == ((w >> 8) & 0xFFu);
+      if (!same) {
+        bad = true;
+        bad_got = got[k];
+        bad_want = w;
+      }
+      sum_lo ^= got[k];
+      sum_hi ^= got[k] * (2u * (unsigned)(e * P::GOT + k) + 1u);
+    }
+    if (bad) {
+      mismatched++;
+      if (first == 0x7FFFFFFFu) {  // a lane's entries ascend
+        first = (unsigned)e;
+        first_got = bad_got;
+        first_want = bad_want;
+      }
+    }
+  }
+  mismatched = wave_add(mismatched);
+  const unsigned lowest = wave_min(first);
+  const int owner = (int)(lowest & 63u);  // entry e belongs to lane e % 64
+  first_got = (unsigned)__shfl((int)first_got, owner);
+  first_want = (unsigned)__shfl((int)first_want, owner);
+  sum_lo = wave_xor(sum_lo);
+  sum_hi = wave_xor(sum_hi);
+  if (lane == 0)
+    store_record8(records, wave, (int)place, (int)mismatched,
+                  lowest == 0x7FFFFFFFu ? -1 : (int)lowest, (int)first_got, (int)first_want,
+                  (int)sum_lo, (int)sum_hi, 0);
+}
+
+// a 1-D contiguous tensor of `dtype` on `device` whose storage starts on 16 B
+static void cvt_check_table(const torch::Tensor& t, const char* name, c10::ScalarType dtype,
+                            torch::Device device) {
+  TORCH_CHECK(t.is_cuda() && t.device() == device, name, " must be on the GPU of `inputs`");
+  TORCH_CHECK(t.scalar_type() == dtype, name, " must be ", c10::toString(dtype));
+  TORCH_CHECK(t.dim() == 1 && t.is_contiguous(), name, " must be 1-D and contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
+              " must start on a 16 B boundary");
+}
+
+// inputs: int32 [entries * IN], scales: float32 [entries], expected: int32
+// [entries * WANT] for the path's IN and WANT (ops/cvt_probe.py builds them).
+// Returns (records [blocks*4, 8] int32, elapsed_ms of the one launch).
+std::tuple<torch::Tensor, double> cvt_sweep(const std::string& path, torch::Tensor inputs,
+                                            torch::Tensor scales, torch::Tensor expected,
+                                            long blocks, long seed) {
+  int id = -1;
+  for (int p = 0; p < CVT_PATHS; p++)
+    if (path == CVT_PATH_NAMES[p]) id = p;
+  TORCH_CHECK(id >= 0, "unknown conversion path ", path);
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  TORCH_CHECK(inputs.is_cuda() && inputs.get_device() == dev,
+              "inputs must be on the current GPU");
+  cvt_check_table(inputs, "inputs", torch::kInt32, inputs.device());
+  cvt_check_table(scales, "scales", torch::kFloat32, inputs.device());
+  cvt_check_table(expected, "expected", torch::kInt32, inputs.device());
+  TORCH_CHECK(blocks >= 1 && blocks <= (1L << 16), "blocks must be in [1, 2^16]");
+  const long entries = scales.numel();
+  TORCH_CHECK(entries >= 1 && entries <= CVT_LDS_DWORDS, "the table needs 1 to ", CVT_LDS_DWORDS,
+              " entries");
+  auto records = zero_records(blocks * 4, 8, inputs.device());
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  double ms = 0;
+  dispatch_int<CVT_PATHS>(id, [&](auto id_c) {
+    typedef std::tuple_element_t<decltype(id_c)::value, CvtPathTypes> P;
+    TORCH_CHECK(inputs.numel() == entries * P::IN && expected.numel() == entries * P::WANT, path,
+                ": ", entries, " scales need ", entries * P::IN, " input and ", entries * P::WANT,
+                " expected dwords");
+    const long need = cvt_round4(entries * P::IN) + cvt_round4(entries) + entries * P::WANT;
+    TORCH_CHECK(need <= CVT_LDS_DWORDS, path, ": the table takes ", need,
+                " dwords, the LDS staging area holds ", CVT_LDS_DWORDS);
+    ms = timed_ms(stream, [&]() {
+      hipLaunchKernelGGL((cvt_sweep_kernel<P>), dim3(blocks), dim3(256), 0, stream,
+                         reinterpret_cast<const unsigned*>(inputs.data_ptr<int>()),
+                         reinterpret_cast<const unsigned*>(scales.data_ptr<float>()),
+                         reinterpret_cast<const unsigned*>(expected.data_ptr<int>()),
+                         reinterpret_cast<int4*>(records.data_ptr<int>()), (int)entries,
+                         (unsigned)seed);
+    });
+  });
+  return std::make_tuple(records, ms);
+}
+
+// ---------------------------------------------------------------------------
+// Conversion burn: the VALU burn's contract (a u32 state per lane seeded from
+// (seed, section, lane) only, `chain` dependent steps per round, a bitwise
+// compare against expected[lane] each round, the same record and the same
+// register-only inject) with a step made of converters. A step
+//   1. carves wide values out of the state: a hash of the state gives sign
+//      and 23 mantissa bits, and the exponent is e + k with e inside the
+//      format's normal range below its top binade (so rounding up stays within
+//      max normal) and k in [-8, 7] the encode scale, also from the state
+//   2. encodes them with the scale 2^k
+//   3. decodes the codes with a second scale 2^k2
+//   4. folds the code bits and the decoded floats' bits into the state with a
+//      multiply-xor
+// Sections: fp8, bf8 (v_cvt_scalef32_pk_{fp8,bf8}_f32 and pk_f32_{fp8,bf8}),
+// fp4 (pk_fp4_f32, pk_f32_fp4), fp6 (32 values per lane through 2xpk16_fp6_f32
+// and pk32_f32_fp6), bf16 (v_cvt_pk_bf16_f32; a bf16's f32 value is its bits
+// shifted, so the decode is no instruction). ops.cvt_burn_expected reproduces
+// every section bit for bit from the sweep's encode and decode functions. The
+// hot loop has no memory traffic. Record: as valu_burn.
+// ---------------------------------------------------------------------------
+enum { CVTB_FP8, CVTB_BF8, CVTB_FP6, CVTB_FP4, CVTB_BF16, CVTB_SECTIONS };
+static const char* const CVTB_NAMES[CVTB_SECTIONS] = {"fp8", "bf8", "fp6", "fp4", "bf16"};
+
+// sign and mantissa from h[31] and h[22:0]; exponent EMIN + (h[30:23] * NEXP >> 8) + k
+template <int EMIN, int NEXP> __device__ __forceinline__ float cvt_carve(unsigned h, int k) {
+  const int e = EMIN + (int)((((h >> 23) & 0xFFu) * NEXP) >> 8);
+  return __uint_as_float((h & 0x807FFFFFu) | ((unsigned)(127 + e + k) << 23));
+}
+__device__ __forceinline__ unsigned cvt_hash(unsigned x, unsigned mul) {
+  x *= mul;
+  return x ^ (x >> 15);
+}
+__device__ __forceinline__ float cvt_pow2(int k) {
+  return __uint_as_float((unsigned)(127 + k) << 23);
+}
+
+template <int SEC> struct CvtBurnStep {
+  static __device__ __forceinline__ unsigned step(unsigned s) {
+    const int k = (int)((s >> 3) & 15u) - 8, k2 = (int)((s >> 9) & 15u) - 8;
+    const float sc = cvt_pow2(k), sc2 = cvt_pow2(k2);
+    const unsigned next = s * 0x9E3779B1u + 0x7F4A7C15u;
+    const unsigned h0 = cvt_hash(s, 0x85EBCA6Bu), h1 = cvt_hash(s ^ 0xC2B2AE35u, 0x27D4EB2Fu);
+    if constexpr (SEC == CVTB_FP8) {
+      const cvt_s2 zero = {0, 0};
+      const unsigned w = cvt_bits(__builtin_amdgcn_cvt_scalef32_pk_fp8_f32(
+          zero, cvt_carve<-6, 14>(h0, k), cvt_carve<-6, 14>(h1, k), sc, false));
+      const f32x2 d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w, sc2, false);
+      return next ^ w ^ rotl32(__float_as_uint(d[0]), 7) ^ rotl32(__float_as_uint(d[1]), 19);
+    } else if constexpr (SEC == CVTB_BF8) {
+      const cvt_s2 zero = {0, 0};
+      const unsigned w = cvt_bits(__builtin_amdgcn_cvt_scalef32_pk_bf8_f32(
+          zero, cvt_carve<-14, 29>(h0, k), cvt_carve<-14, 29>(h1, k), sc, false));
+      const f32x2 d = __builtin_amdgcn_cvt_scalef32_pk_f32_bf8(w, sc2, false);
+      return next ^ w ^ rotl32(__float_as_uint(d[0]), 7) ^ rotl32(__float_as_uint(d[1]), 19);
+    } else if constexpr (SEC == CVTB_FP4) {
+      const unsigned w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(
+          0u, cvt_carve<0, 2>(h0, k), cvt_carve<0, 2>(h1, k), sc, 0);
+      const f32x2 d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sc2, 0);
+      return next ^ w ^ rotl32(__float_as_uint(d[0]), 7) ^ rotl32(__float_as_uint(d[1]), 19);
+    } else if constexpr (SEC == CVTB_FP6) {
+      unsigned in[32];
+#pragma unroll
+      for (int j = 0; j < 32; j++)
+        in[j] = __float_as_uint(
+            cvt_carve<0, 2>(cvt_hash(s ^ ((unsigned)j * 0x85EBCA6Bu), 0x9E3779B1u), k));
+      const u32x6 p = cvt_enc6<CVT_FP6>(in, sc);
+      const f32x32 q = cvt_dec6<CVT_FP6>(p, sc2);
+      unsigned x = next;
+#pragma unroll
+      for (int i = 0; i < 6; i++) x ^= rotl32(p[i], 5 * i + 1);
+#pragma unroll
+      for (int j = 0; j < 32; j++) x ^= rotl32(__float_as_uint(q[j]), j % 31 + 1);
+      return x;
+    } else {
+      const cvt_y2 c = {(__bf16)cvt_carve<-100, 200>(h0, k), (__bf16)cvt_carve<-100, 200>(h1, k)};
+      const unsigned w = cvt_bits(c);
+      return next ^ w ^ rotl32(w << 16, 7) ^ rotl32(w & 0xFFFF0000u, 19);
+    }
+  }
+};
+
+template <int SEC>
+__global__ void __launch_bounds__(256)
+cvt_burn_kernel(const unsigned* __restrict__ expected, int4* __restrict__ records, unsigned seed,
+                int chain, int rounds, int inject_wave, int inject_round, int inject_lane,
+                int inject_bit) {
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const unsigned place = hw_word();
+  const unsigned seeded =
+      fmix32(seed + (unsigned)(SEC + 16) * 0x9E3779B9u + (unsigned)lane * 0x85EBCA6Bu);
+  const unsigned want = expected[lane];
+  const unsigned flip = (wave == inject_wave && lane == inject_lane) ? 1u << (inject_bit & 31) : 0u;
+  int mismatched = 0, first_round = -1, first_lane = -1;
+  unsigned checksum = 0;
+  for (int round = 0; round < rounds; round++) {
+    unsigned s = seeded;
+    // opaque to the optimiser: every round really recomputes its chain
+    asm volatile("" : "+v"(s));
+    for (int c = 0; c < chain; c++) s = CvtBurnStep<SEC>::step(s);
+    if (round == inject_round) s ^= flip;
+    checksum ^= s;
+    const unsigned long long bad = __ballot(s != want);  // wave-uniform
+    if (bad) {
+      mismatched += __popcll(bad);
+      if (first_round < 0) {
+        first_round = round;
+        first_lane = __ffsll((long long)bad) - 1;
+      }
+    }
+  }
+  checksum = wave_xor(checksum);
+  if (lane == 0)
+    store_record8(records, wave, (int)place, mismatched, first_round, first_lane, (int)checksum, 0,
+                  0, 0);
+}
+
+// expected: 64 int32 on the current device, the state every lane must reach
+// after `chain` steps (ops.cvt_burn_expected). One untimed warm-up launch,
+// then one timed launch (warm_then_timed_ms).
+// Returns (records [waves,8] int32, elapsed_ms of the timed launch).
+std::tuple<torch::Tensor, double> cvt_burn(const std::string& section, torch::Tensor expected,
+                                           long seed, long blocks, long chain, long rounds,
+                                           long inject_wave, long inject_round, long inject_lane,
+                                           long inject_bit) {
+  int sec = -1;
+  for (int s = 0; s < CVTB_SECTIONS; s++)
+    if (section == CVTB_NAMES[s]) sec = s;
+  TORCH_CHECK(sec >= 0, "section must be one of fp8, bf8, fp6, fp4, bf16; got ", section);
+  TORCH_CHECK(blocks >= 1 && blocks <= (1L << 20), "blocks must be in [1, 2^20]");
+  TORCH_CHECK(chain >= 1 && rounds >= 1, "chain and rounds must be >= 1");
+  // every round ends in the same state: the xor checksum of an even number
+  // of rounds is zero whatever the hardware computed
+  TORCH_CHECK(rounds % 2 == 1, "rounds must be odd (the xor checksum cancels over an even number)");
+  TORCH_CHECK(chain <= (1L << 22) && rounds <= (1L << 22) && chain * rounds <= (1L << 22),
+              "chain*rounds must be <= 2^22");
+  TORCH_CHECK(inject_wave >= -1 && inject_wave < blocks * 4 && inject_round >= -1 &&
+                  inject_round < rounds && inject_lane >= -1 && inject_lane < 64 &&
+                  inject_bit >= -1 && inject_bit < 32,
+              "inject_wave/inject_round/inject_lane/inject_bit out of range");
+  TORCH_CHECK(inject_wave < 0 || (inject_round >= 0 && inject_lane >= 0 && inject_bit >= 0),
+              "an injection needs inject_round, inject_lane and inject_bit");
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  TORCH_CHECK(expected.is_cuda() && expected.get_device() == dev,
+              "expected must be on the current GPU");
+  TORCH_CHECK(expected.dtype() == torch::kInt32 && expected.numel() == 64 &&
+                  expected.is_contiguous(),
+              "expected must hold 64 contiguous int32 values (one state per lane)");
+  auto records = zero_records(blocks * 4, 8);
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  const double ms = warm_then_timed_ms(stream, [&]() {
+    dispatch_int<CVTB_SECTIONS>(sec, [&](auto sec_c) {
+      hipLaunchKernelGGL((cvt_burn_kernel<decltype(sec_c)::value>), dim3(blocks), dim3(256), 0,
+                         stream, reinterpret_cast<const unsigned*>(expected.data_ptr<int>()),
+                         reinterpret_cast<int4*>(records.data_ptr<int>()), (unsigned)seed,
+                         (int)chain, (int)rounds, (int)inject_wave, (int)inject_round,
+                         (int)inject_lane, (int)inject_bit);
+    });
+  });
+  return std::make_tuple(records, ms);
+}
+
 py::dict device_info(int dev) {
   hipDeviceProp_t prop;
   HIP_CHECK(hipGetDeviceProperties(&prop, dev));
@@ -5351,6 +6073,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Memory-path probe (section buf|oob|lds|forms): buffer addressing in every width, the "
         "descriptor's bounds check, direct-to-LDS loads, sub-dword, d16 and wide forms, verified "
         "bitwise; returns (per-wave records [blocks*4,8], ms)");
+  m.def("cvt_sweep", &cvt_sweep, py::arg("path"), py::arg("inputs"), py::arg("scales"),
+        py::arg("expected"), py::arg("blocks") = 2048, py::arg("seed") = 1,
+        "Conversion sweep of one path (ops.CVT_PATHS): every wave walks the whole operand table "
+        "out of LDS through one fp8/fp6/fp4/bf16 convert form, every select, compared bitwise "
+        "(stochastic-rounding paths: against the two bracket codes); returns (per-wave records "
+        "[blocks*4,8], ms)");
+  m.def("cvt_burn", &cvt_burn, py::arg("section"), py::arg("expected"), py::arg("seed") = 1,
+        py::arg("blocks") = 2048, py::arg("chain") = 1024, py::arg("rounds") = 33,
+        py::arg("inject_wave") = -1, py::arg("inject_round") = -1, py::arg("inject_lane") = -1,
+        py::arg("inject_bit") = -1,
+        "Sustained conversion burn (section fp8|bf8|fp6|fp4|bf16): rounds x chain dependent "
+        "encode-decode steps per lane, verified bitwise against expected; returns (per-wave "
+        "records [waves,8], ms)");
   m.def("cu_coverage", &cu_coverage, py::arg("blocks") = 4096,
         "Per-wave (XCC_ID<<16 | HW_ID) placement words for CU-coverage checks");
   m.def("device_info", &device_info, py::arg("dev") = 0);
