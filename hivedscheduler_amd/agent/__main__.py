@@ -81,6 +81,12 @@ def main() -> None:
                          "N sweeps (on deep sweeps); 0 = never")
     ap.add_argument("--cvt-probe", action="store_true",
                     help="with --local: also run the conversion probe")
+    ap.add_argument("--gemm-probe-every", type=int, default=0,
+                    help="GEMM probe (tiled bf16 / fp8 GEMM: direct-to-LDS loads, LDS transpose "
+                         "reads and MFMAs together, exact, per CU) every N sweeps (on deep "
+                         "sweeps); 0 = never")
+    ap.add_argument("--gemm-probe", action="store_true",
+                    help="with --local: also run the GEMM probe")
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
@@ -101,7 +107,8 @@ def main() -> None:
                                      mx_scale_probe=args.mx_scale_probe,
                                      mempath_probe=args.mempath_probe,
                                      matrix_probe=args.matrix_probe,
-                                     cvt_probe=args.cvt_probe)
+                                     cvt_probe=args.cvt_probe,
+                                     gemm_probe=args.gemm_probe)
         if args.p2p_matrix:
             try:
                 m = p2p_link_matrix()
@@ -129,7 +136,8 @@ def main() -> None:
                             mx_scale_probe_every=args.mx_scale_probe_every,
                             mempath_probe_every=args.mempath_probe_every,
                             matrix_probe_every=args.matrix_probe_every,
-                            cvt_probe_every=args.cvt_probe_every)
+                            cvt_probe_every=args.cvt_probe_every,
+                            gemm_probe_every=args.gemm_probe_every)
     if args.once:
         import json
 

@@ -6,7 +6,7 @@ extension is REQUIRED: failure to load raises (no silent eager fallback).
 Here: the loader, `gpu_health_report` and the single-tile MFMA checks. Each
 opt-in probe has a module of its own (mfma_burn, lds_march, hbm_march,
 simd_probe, scalar_probe, atomic_probe, mx_scale, mempath_probe, matrix_paths,
-cvt_probe)
+cvt_probe, gemm_probe)
 on top of `records`, and the
 single-tile checks' operands and verdict are in mfma_tiles; their public names
 are re-exported here, and their report functions reach the extension through
@@ -30,6 +30,11 @@ from .cvt_probe import (CVT_BURN_SECTIONS, CVT_FORMATS, CVT_PATHS, CVT_SCALE_EXP
                         cvt_max_normal, cvt_old, cvt_operands, cvt_pack6, cvt_path_info,
                         cvt_probe_report, cvt_sr_bracket, cvt_sweep_report, cvt_unpack6,
                         summarize_cvt_burn, summarize_cvt_sweep)
+from .gemm_probe import (GEMM_PROBE_CASES, GEMM_PROBE_FORMATS, GEMM_PROBE_LAYOUTS,  # noqa: F401
+                         LDS_TR_WIDTHS, gemm_probe_bk, gemm_probe_encode, gemm_probe_operands,
+                         gemm_probe_period, gemm_probe_report, gemm_probe_wave_checksums,
+                         lds_tr_expected, lds_tr_image, lds_tr_map_report, lds_tr_span,
+                         lds_tr_tile_addrs, summarize_gemm_probe)
 from .hbm_march import (HBM_MARCH_TILE_BYTES, hbm_march_pattern, hbm_march_report,  # noqa: F401
                         hbm_slow_xcds, summarize_hbm_march)
 from .lds_march import (LDS_MARCH_WORDS, lds_march_block_checksum, lds_march_pattern,  # noqa: F401
@@ -100,7 +105,8 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
                       hbm_march: bool = False, simd_probe: bool = False,
                       scalar_probe: bool = False, atomic_probe: bool = False,
                       mx_scale_probe: bool = False, mempath_probe: bool = False,
-                      matrix_probe: bool = False, cvt_probe: bool = False) -> dict:
+                      matrix_probe: bool = False, cvt_probe: bool = False,
+                      gemm_probe: bool = False) -> dict:
     """Run the health-probe kernels on one GPU and return measured facts.
 
     Feeds leaf-cell healthiness: HBM bandwidth deficit, MFMA mismatch, or
@@ -172,6 +178,13 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     stochastic rounding, and a burn of tens of milliseconds per section, per
     SIMD) as report["cvt_probe"] and ANDs its verdict into `healthy`. Off by
     default, and the report is then unchanged.
+
+    gemm_probe=True adds the GEMM probe (`gemm_probe_report`: a tiled bf16 and
+    fp8 GEMM in both B layouts that keeps direct-to-LDS loads, LDS fragment
+    reads, the LDS transpose reads and MFMAs busy together, every tile compared
+    bitwise in registers, tens of milliseconds per case, and the transpose-read
+    map in four widths) as report["gemm_probe"] and ANDs its verdict into
+    `healthy`. Off by default, and the report is then unchanged.
     """
     ops = _ops_on(device)
     size_mb = 256 if quick else 2048
@@ -247,6 +260,9 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     if cvt_probe:
         report["cvt_probe"] = cvt_probe_report(device)
         report["healthy"] = bool(report["healthy"] and report["cvt_probe"]["ok"])
+    if gemm_probe:
+        report["gemm_probe"] = gemm_probe_report(device)
+        report["healthy"] = bool(report["healthy"] and report["gemm_probe"]["ok"])
     return report
 
 
