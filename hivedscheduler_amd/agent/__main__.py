@@ -87,6 +87,12 @@ def main() -> None:
                          "sweeps); 0 = never")
     ap.add_argument("--gemm-probe", action="store_true",
                     help="with --local: also run the GEMM probe")
+    ap.add_argument("--mx-gemm-probe-every", type=int, default=0,
+                    help="MX GEMM probe (tiled MXFP8 / MXFP4 GEMM: the GEMM probe's pipeline "
+                         "through the block-scaled MFMA with E8M0 scales streamed from memory, "
+                         "exact, per CU) every N sweeps (on deep sweeps); 0 = never")
+    ap.add_argument("--mx-gemm-probe", action="store_true",
+                    help="with --local: also run the MX GEMM probe")
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
@@ -108,7 +114,8 @@ def main() -> None:
                                      mempath_probe=args.mempath_probe,
                                      matrix_probe=args.matrix_probe,
                                      cvt_probe=args.cvt_probe,
-                                     gemm_probe=args.gemm_probe)
+                                     gemm_probe=args.gemm_probe,
+                                     mx_gemm_probe=args.mx_gemm_probe)
         if args.p2p_matrix:
             try:
                 m = p2p_link_matrix()
@@ -137,7 +144,8 @@ def main() -> None:
                             mempath_probe_every=args.mempath_probe_every,
                             matrix_probe_every=args.matrix_probe_every,
                             cvt_probe_every=args.cvt_probe_every,
-                            gemm_probe_every=args.gemm_probe_every)
+                            gemm_probe_every=args.gemm_probe_every,
+                            mx_gemm_probe_every=args.mx_gemm_probe_every)
     if args.once:
         import json
 

@@ -66,6 +66,7 @@ def collect_node_health(
     matrix_probe: bool = False,
     cvt_probe: bool = False,
     gemm_probe: bool = False,
+    mx_gemm_probe: bool = False,
 ) -> dict:
     """One health sweep over all visible GPUs. deep=True also runs the HIP
     kernels (HBM + MFMA); sweep=True adds the 16 GiB HBM stuck-bit pattern
@@ -156,6 +157,13 @@ def collect_node_health(
     judged) and `gemm_bad_cus` (the CUs of any wave whose tile was wrong, as
     xcc, se, sh, cu), and a failed probe marks the leaf bad.
 
+    mx_gemm_probe=True (with deep) adds the MX GEMM probe (a tiled MXFP8 /
+    MXFP4 GEMM in both B layouts through the block-scaled MFMA, its scale bytes
+    streamed from memory, exact and compared bitwise): per GPU it records
+    `mx_gemm_probe_ok`, `mx_gemm_tflops` ({case: TFLOP/s}, reported, not
+    judged) and `mx_gemm_bad_cus` (the CUs of any wave whose tile was wrong, as
+    xcc, se, sh, cu), and a failed probe marks the leaf bad.
+
     The stuck-bit scan transiently holds up to 16 GiB of HBM; on a GPU
     running tenant jobs this can make the tenant's own allocations fail.
     Keep sweep on the low-frequency cadence and prefer idle GPUs (the
@@ -180,7 +188,8 @@ def collect_node_health(
                             simd_probe=simd_probe, scalar_probe=scalar_probe,
                             atomic_probe=atomic_probe, mx_scale_probe=mx_scale_probe,
                             mempath_probe=mempath_probe, matrix_probe=matrix_probe,
-                            cvt_probe=cvt_probe, gemm_probe=gemm_probe)
+                            cvt_probe=cvt_probe, gemm_probe=gemm_probe,
+                            mx_gemm_probe=mx_gemm_probe)
         for i in range(n):
             gpu = report["gpus"][str(i)]
             try:
@@ -327,6 +336,16 @@ def collect_node_health(
                     )
                     if not p["ok"] or p["bad_cus"]:
                         gpu["healthy"] = False
+                if mx_gemm_probe:
+                    p = rep["mx_gemm_probe"]
+                    gpu.update(
+                        mx_gemm_probe_ok=bool(p["ok"]),
+                        mx_gemm_tflops={name: round(s["tflops"], 1)
+                                        for name, s in p["cases"].items()},
+                        mx_gemm_bad_cus=p["bad_cus"],
+                    )
+                    if not p["ok"] or p["bad_cus"]:
+                        gpu["healthy"] = False
             except Exception as e:
                 gpu.update(healthy=False, error=str(e)[:200])
     if probe_pairs and n >= 2:
@@ -404,7 +423,8 @@ class NodeHealthAgent:
                  simd_probe_every: int = 0, scalar_probe_every: int = 0,
                  atomic_probe_every: int = 0, mx_scale_probe_every: int = 0,
                  mempath_probe_every: int = 0, matrix_probe_every: int = 0,
-                 cvt_probe_every: int = 0, gemm_probe_every: int = 0):
+                 cvt_probe_every: int = 0, gemm_probe_every: int = 0,
+                 mx_gemm_probe_every: int = 0):
         self.scheduler_url = scheduler_url.rstrip("/")
         self.node_name = node_name or socket.gethostname()
         self.interval_s = interval_s
@@ -461,6 +481,9 @@ class NodeHealthAgent:
         # GEMM probe cadence (loads, LDS reads and MFMAs together, per CU), same
         # pattern; 0 = never (about 0.1 s of every CU per GPU)
         self.gemm_probe_every = gemm_probe_every
+        # MX GEMM probe cadence (the same pipeline through the block-scaled
+        # MFMA with streamed scales), same pattern; 0 = never
+        self.mx_gemm_probe_every = mx_gemm_probe_every
         self._rounds = 0
 
     def post_report(self, report: dict) -> bool:
@@ -523,7 +546,8 @@ class NodeHealthAgent:
                             mempath_probe=deep and self._due(self.mempath_probe_every),
                             matrix_probe=deep and self._due(self.matrix_probe_every),
                             cvt_probe=deep and self._due(self.cvt_probe_every),
-                            gemm_probe=deep and self._due(self.gemm_probe_every))
+                            gemm_probe=deep and self._due(self.gemm_probe_every),
+                            mx_gemm_probe=deep and self._due(self.mx_gemm_probe_every))
         self._rounds += 1
         if "burn" in kwargs:
             kwargs["min_mfma_tflops"] = self.min_mfma_tflops

@@ -6,7 +6,7 @@ extension is REQUIRED: failure to load raises (no silent eager fallback).
 Here: the loader, `gpu_health_report` and the single-tile MFMA checks. Each
 opt-in probe has a module of its own (mfma_burn, lds_march, hbm_march,
 simd_probe, scalar_probe, atomic_probe, mx_scale, mempath_probe, matrix_paths,
-cvt_probe, gemm_probe)
+cvt_probe, gemm_probe, mx_gemm_probe)
 on top of `records`, and the
 single-tile checks' operands and verdict are in mfma_tiles; their public names
 are re-exported here, and their report functions reach the extension through
@@ -56,6 +56,11 @@ from .mfma_tiles import (E4M3_GROUP_WINDOW_BITS, E4M3_NAN_CODES, TILE_FORMATS,  
                          tile_operand_invariants, tile_product)
 from .mfma_burn import (BURN_FORMATS, _burn_integers, burn_chain_limit, burn_operands,  # noqa: F401
                         mfma_burn_report, summarize_burn)
+from .mx_gemm_probe import (MX_GEMM_CASES, MX_GEMM_FORMATS, MX_GEMM_LAYOUTS,  # noqa: F401
+                            MX_GEMM_MAX_K, mx_gemm_bk, mx_gemm_encode, mx_gemm_layout,
+                            mx_gemm_operands, mx_gemm_pack, mx_gemm_period,
+                            mx_gemm_probe_report, mx_gemm_reference, mx_gemm_unpack,
+                            summarize_mx_gemm_probe)
 from .mx_scale import (MX_BURN_FORMATS, MX_FORMATS, MX_FULL_WIDTH_DELTAS,  # noqa: F401
                        MX_SCALE_PAIRS, MX_SCALE_SPREAD, MX_SHAPE_NAMES, MX_SHAPES, e8m0_value,
                        mx_code_count, mx_decode, mx_decode_sweep_case, mx_encode, mx_exactness,
@@ -106,7 +111,7 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
                       scalar_probe: bool = False, atomic_probe: bool = False,
                       mx_scale_probe: bool = False, mempath_probe: bool = False,
                       matrix_probe: bool = False, cvt_probe: bool = False,
-                      gemm_probe: bool = False) -> dict:
+                      gemm_probe: bool = False, mx_gemm_probe: bool = False) -> dict:
     """Run the health-probe kernels on one GPU and return measured facts.
 
     Feeds leaf-cell healthiness: HBM bandwidth deficit, MFMA mismatch, or
@@ -185,6 +190,13 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     bitwise in registers, tens of milliseconds per case, and the transpose-read
     map in four widths) as report["gemm_probe"] and ANDs its verdict into
     `healthy`. Off by default, and the report is then unchanged.
+
+    mx_gemm_probe=True adds the MX GEMM probe (`mx_gemm_probe_report`: a tiled
+    MXFP8 and MXFP4 GEMM in both B layouts through the block-scaled MFMA, its
+    E8M0 scale bytes streamed from memory beside the direct-to-LDS loads, every
+    tile compared bitwise in registers, tens of milliseconds per case) as
+    report["mx_gemm_probe"] and ANDs its verdict into `healthy`. Off by
+    default, and the report is then unchanged.
     """
     ops = _ops_on(device)
     size_mb = 256 if quick else 2048
@@ -263,6 +275,9 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     if gemm_probe:
         report["gemm_probe"] = gemm_probe_report(device)
         report["healthy"] = bool(report["healthy"] and report["gemm_probe"]["ok"])
+    if mx_gemm_probe:
+        report["mx_gemm_probe"] = mx_gemm_probe_report(device)
+        report["healthy"] = bool(report["healthy"] and report["mx_gemm_probe"]["ok"])
     return report
 
 

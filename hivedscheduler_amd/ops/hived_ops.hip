@@ -50,7 +50,10 @@
 //                tiled bf16 / fp8 GEMM (direct-to-LDS loads in flight, LDS
 //                fragment reads and MFMAs in the same cycles), exact and
 //                compared bitwise in registers; the CU of any wave that was wrong
-//  - p2p copy:   xGMI link bandwidth between two GPUs (expected ~153 GB/s per
+//  - mx_gemm_pipe: the same pipeline through the block-scaled MFMA: a tiled
+//                MXFP8 / MXFP4 GEMM whose E8M0 scale bytes are streamed from
+//                memory beside the operands, exact and compared bitwise
+//  - p2p copy:  xGMI link bandwidth between two GPUs (expected ~153 GB/s per
 //                link per direction); a degraded link marks the PAIR cell bad
 //
 // Written CDNA4-native: 64-wide wavefronts, float4 coalesced loads,
@@ -6486,6 +6489,665 @@ std::tuple<torch::Tensor, torch::Tensor, double> gemm_pipe(
   return std::make_tuple(records, C, ms);
 }
 
+// ---------------------------------------------------------------------------
+// MX GEMM probe: gemm_pipe's pipeline feeding v_mfma_scale_f32_16x16x128_f8f6f4,
+// the GEMM an MXFP8 / MXFP4 tenant runs: C = (A o scales).(B o scales), fp32
+// accumulate, every 32 elements of K of a row of A or a column of B under one
+// E8M0 byte that is streamed from memory next to the operands. The MX scale
+// probe above runs this instruction from registers only; here the scaled pipe,
+// the direct-to-LDS loads, the LDS fragment reads (4-bit and 8-bit transpose
+// reads for B kn) and the scale loads are busy in the same cycles, and every
+// tile is compared bitwise in registers (operands: ops/mx_gemm_probe.py).
+//
+// FMT mxfp8: e4m3 both sides, one code per byte. mxfp4: e2m1 both sides, two
+// codes per byte, the even element in the low nibble; the packed dimension is
+// K for A [M,K] and B nk [N,K], N for B kn [K,N]. scale_a [M,K/32]; scale_b
+// [N,K/32] (nk) or [K/32,N] (kn): plain row-major bytes, not pre-shuffled.
+//
+// Same shape as gemm_pipe_kernel, to be read side by side with it: one
+// workgroup of 256 threads per 128x128 tile of C, waves 2x2, 4x4 MFMA tiles
+// per wave, 64 accumulator registers held for the whole K loop, two LDS stages
+// of 32 KiB (A tile at 0, B tile at 16 KiB), eight global_load_lds_dwordx4 per
+// wave and K step with the swizzle on the source side, barrier 1 / issue step
+// k+1 / wait / barrier 2 / read / MFMA. A K step is 128 bytes per row: 128
+// e4m3 elements, one scaled MFMA deep, or 256 e2m1 elements, two deep (K
+// chunk 0 is bytes 0..63 of the row, chunk 1 bytes 64..127).
+//
+// Fragments. Lane (i, g) of a 16x16x128 tile holds, 4-bit: the 16 bytes with
+// k = 32g..32g+31 of its K chunk (VGPRs 0-3; the operand's upper four are not
+// read); 8-bit: k = 16g..16g+15 in VGPRs 0-3 and k = 64+16g.. in VGPRs 4-7
+// (the measured walk, see "MX scale probe"). For A and B nk that is, in both
+// formats, the 16-byte chunks g and g+4 of the row: gemm_pipe's ds_read_b128
+// addressing and key, chunk g+4 at address ^ 64. fp4 uses them as two MFMAs,
+// fp8 as the two halves of one operand.
+//   B kn fp8: the tile is 128 k rows of 128 bytes; ds_read_b64_tr_b8 gives 8 k
+//     per read, two reads 16 consecutive k, the second half 64 rows on:
+//     gemm_pipe's fp8 kn map and key, the four reads forming one operand.
+//   B kn fp4: the tile is 256 k rows of 64 bytes (128 nibbles of n). A load of
+//     1 KiB lands 16 rows of four 16-byte slots. ds_read_b64_tr_b4: a group of
+//     16 lanes addresses 16 k rows, lane i the 8 bytes (16 nibbles, one 16x16
+//     tile's columns) of row 128c + 32g + 16h + i for read h of chunk c, and
+//     receives column i, 16 consecutive k, lowest first; two reads are the
+//     lane's 32 k. Tile t of wave column wn is 8-byte unit 4 wn + t of the
+//     row: slot (2 wn + (t>>1)) ^ key, half t & 1.
+//   fp4 kn key = (k>>2) & 3. Rows of 64 bytes: four rows fill the 64 banks, so
+//     rows k and k+4 collide. Every lane of one read takes the same half of its
+//     16-byte slot (the load lands 16 bytes whole, so the source-side swizzle
+//     cannot move a half), hence 32 lanes reach at most 32 banks: the degree
+//     is 2 at best. Assuming one LDS pass serves 32 consecutive lanes of a b64
+//     read (rows 32g..32g+15 and 32g+32..32g+47): the eight rows that share
+//     k & 3 fall on the four slots by (k>>2) & 3, two each. Conflict degree 2
+//     by construction under that assumption; not measured with counters.
+//
+// Scales. Block b of a tile's K chunk is scaled by the byte lane group b
+// supplies, in every format, so lane (i, g) supplies per K chunk the byte of
+// (row 16 t + i, block g) for each of its four A tiles t and four B tiles.
+// They are fetched with global_load_ubyte (inline assembly, so that their
+// number and place in the vmcnt order are the source's, not the compiler's):
+// four A and four B loads per chunk, 8 (fp8) or 16 (fp4) per step, a step
+// ahead of use, gathered after the wait into the four bytes of one VGPR per
+// side and chunk (shifts and ors); the MFMA of tile (t_a, t_b) selects its
+// bytes with op_sel = t_a and t_b, immediates in the unrolled tile loop. No
+// LDS is spent on scales. Nothing is indexed by a loaded value.
+//
+// vmcnt, from the loads in flight, oldest first. Before the loop: LDS(0) [8],
+// scales(0) [S]. Step k: after barrier 1, LDS(k+1) [8] is issued; in flight
+// are LDS(k), scales(k), LDS(k+1), and s_waitcnt vmcnt(8) leaves exactly
+// LDS(k+1) in flight: step k's operands have landed and its scale bytes are
+// in registers. They are gathered, and only then scales(k+1) [S] is issued
+// into the same registers, behind LDS(k+1), which restores the order for step
+// k+1. The last step issues nothing and waits vmcnt(0). There is no other
+// vmcnt wait in the K loop, and every step loads its own scale bytes.
+//
+// lgkmcnt. fp4: as gemm_pipe, the two K chunks are two halves: all reads are
+// issued, lgkmcnt(8) (kn: 12) before chunk 0's 16 MFMAs, lgkmcnt(0) before
+// chunk 1's. fp8: one MFMA consumes both pieces, so the step is split by
+// tiles: B's reads (nk 8, kn 16) and A tiles 0-1 (4) are issued, then A tiles
+// 2-3 (4); lgkmcnt(4) before the 8 MFMAs of A tiles 0-1, lgkmcnt(0) before the
+// 8 of A tiles 2-3.
+//
+// Verification, records, store_c and inject are gemm_pipe's. Race and bounds:
+// no wave waits for another workgroup; every loop bound is a launch argument;
+// the wrapper fixes every shape the offsets are computed from. Build for
+// gfx950 (register counts in BENCHMARKS.md "MX GEMM probe"): no scratch,
+// 64 KiB of LDS, two workgroups per CU.
+// ---------------------------------------------------------------------------
+enum { MXG_FP8 = 0, MXG_FP4 = 1 };
+
+__device__ __forceinline__ int mxg_key_tr4(int k) { return (k >> 2) & 3; }
+
+#define MXG_READ(INSN, DST, AT, OFF) \
+  asm volatile(INSN " %0, %1 offset:" #OFF : "=v"(DST) : "v"(AT) : "memory")
+// one scale byte: base (wave-uniform) + off (per lane) + OFF; tied, so the
+// next step's byte returns into the register the last one was gathered from
+#define MXG_LOAD_SCALE(DST, VOFF, BASE, OFF)                           \
+  asm volatile("global_load_ubyte %0, %1, %2 offset:" #OFF             \
+               : "+v"(DST)                                             \
+               : "v"(VOFF), "s"(BASE)                                  \
+               : "memory")
+
+// the lane's scale loads of one step. sa, sb: the step's first scale byte of
+// the workgroup's rows (columns); a_off, b_off: this lane's (row i, block g) of
+// tile 0 from there. A, B nk: tile t is 16 rows = `stride` bytes on (added to
+// the wave-uniform base), K chunk 1 four blocks = 4 bytes on. B kn: the tiles
+// are 16 columns apart in one row of scale_b, chunk 1 four rows = `stride` on.
+template <int FMT, int BL>
+__device__ __forceinline__ void mxg_load_scales(unsigned (&ra)[2][4], unsigned (&rb)[2][4],
+                                                const unsigned char* sa, const unsigned char* sb,
+                                                unsigned a_off, unsigned b_off, size_t a_stride,
+                                                size_t b_stride) {
+  const unsigned char* sa1 = sa + a_stride;
+  const unsigned char* sa2 = sa1 + a_stride;
+  const unsigned char* sa3 = sa2 + a_stride;
+  const unsigned char* sb1 = sb + b_stride;
+  MXG_LOAD_SCALE(ra[0][0], a_off, sa, 0);
+  MXG_LOAD_SCALE(ra[0][1], a_off, sa1, 0);
+  MXG_LOAD_SCALE(ra[0][2], a_off, sa2, 0);
+  MXG_LOAD_SCALE(ra[0][3], a_off, sa3, 0);
+  if constexpr (FMT == MXG_FP4) {
+    MXG_LOAD_SCALE(ra[1][0], a_off, sa, 4);
+    MXG_LOAD_SCALE(ra[1][1], a_off, sa1, 4);
+    MXG_LOAD_SCALE(ra[1][2], a_off, sa2, 4);
+    MXG_LOAD_SCALE(ra[1][3], a_off, sa3, 4);
+  }
+  if constexpr (BL == GP_NK) {
+    const unsigned char* sb2 = sb1 + b_stride;
+    const unsigned char* sb3 = sb2 + b_stride;
+    MXG_LOAD_SCALE(rb[0][0], b_off, sb, 0);
+    MXG_LOAD_SCALE(rb[0][1], b_off, sb1, 0);
+    MXG_LOAD_SCALE(rb[0][2], b_off, sb2, 0);
+    MXG_LOAD_SCALE(rb[0][3], b_off, sb3, 0);
+    if constexpr (FMT == MXG_FP4) {
+      MXG_LOAD_SCALE(rb[1][0], b_off, sb, 4);
+      MXG_LOAD_SCALE(rb[1][1], b_off, sb1, 4);
+      MXG_LOAD_SCALE(rb[1][2], b_off, sb2, 4);
+      MXG_LOAD_SCALE(rb[1][3], b_off, sb3, 4);
+    }
+  } else {
+    MXG_LOAD_SCALE(rb[0][0], b_off, sb, 0);
+    MXG_LOAD_SCALE(rb[0][1], b_off, sb, 16);
+    MXG_LOAD_SCALE(rb[0][2], b_off, sb, 32);
+    MXG_LOAD_SCALE(rb[0][3], b_off, sb, 48);
+    if constexpr (FMT == MXG_FP4) {
+      MXG_LOAD_SCALE(rb[1][0], b_off, sb1, 0);
+      MXG_LOAD_SCALE(rb[1][1], b_off, sb1, 16);
+      MXG_LOAD_SCALE(rb[1][2], b_off, sb1, 32);
+      MXG_LOAD_SCALE(rb[1][3], b_off, sb1, 48);
+    }
+  }
+}
+#undef MXG_LOAD_SCALE
+
+// the step's vmcnt wait; names the scale registers it makes valid. MORE: step
+// k+1's eight direct loads were issued after them and stay in flight
+template <int FMT, bool MORE>
+__device__ __forceinline__ void mxg_wait_vm(unsigned (&ra)[2][4], unsigned (&rb)[2][4]) {
+#define MXG_WAIT_VM(CNT)                                                                    \
+  if constexpr (FMT == MXG_FP8)                                                             \
+    asm volatile("s_waitcnt vmcnt(" CNT ")"                                                 \
+                 : "+v"(ra[0][0]), "+v"(ra[0][1]), "+v"(ra[0][2]), "+v"(ra[0][3]),          \
+                   "+v"(rb[0][0]), "+v"(rb[0][1]), "+v"(rb[0][2]), "+v"(rb[0][3])::"memory"); \
+  else                                                                                      \
+    asm volatile("s_waitcnt vmcnt(" CNT ")"                                                 \
+                 : "+v"(ra[0][0]), "+v"(ra[0][1]), "+v"(ra[0][2]), "+v"(ra[0][3]),          \
+                   "+v"(rb[0][0]), "+v"(rb[0][1]), "+v"(rb[0][2]), "+v"(rb[0][3]),          \
+                   "+v"(ra[1][0]), "+v"(ra[1][1]), "+v"(ra[1][2]), "+v"(ra[1][3]),          \
+                   "+v"(rb[1][0]), "+v"(rb[1][1]), "+v"(rb[1][2]), "+v"(rb[1][3])::"memory")
+  if constexpr (MORE) { MXG_WAIT_VM("8"); }
+  else { MXG_WAIT_VM("0"); }
+#undef MXG_WAIT_VM
+}
+__device__ __forceinline__ int mxg_gather(const unsigned (&r)[4]) {
+  return (int)(r[0] | (r[1] << 8) | (r[2] << 16) | (r[3] << 24));
+}
+
+// the 16 MFMAs of A tiles I0.. x all B tiles; op_sel must be an immediate
+#define MXG_MMA(FMT_CODE, I, J)                                                          \
+  acc[I][J] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[I], b[J], acc[I][J],    \
+                                                               FMT_CODE, FMT_CODE, I, sa, J, sb)
+#define MXG_MMA_ROW(FMT_CODE, I) \
+  MXG_MMA(FMT_CODE, I, 0); MXG_MMA(FMT_CODE, I, 1); MXG_MMA(FMT_CODE, I, 2); MXG_MMA(FMT_CODE, I, 3)
+
+// fp4: one K chunk = one half of the step, as gp_read_half / gp_wait_half
+template <int BL> struct MxgFrags4 {
+  gp_i4 a[4];
+  gp_i4 b[4];            // nk
+  gp_i2 lo[4], hi[4];    // kn: k 0..15 and 16..31 of the lane's 32
+};
+template <int BL, int HS>
+__device__ __forceinline__ void mxg_read_half4(MxgFrags4<BL>& f, unsigned a_at,
+                                               const unsigned (&b_at)[4]) {
+  MXG_READ("ds_read_b128", f.a[0], a_at, 0);
+  MXG_READ("ds_read_b128", f.a[1], a_at, 2048);
+  MXG_READ("ds_read_b128", f.a[2], a_at, 4096);
+  MXG_READ("ds_read_b128", f.a[3], a_at, 6144);
+  if constexpr (BL == GP_NK) {
+    MXG_READ("ds_read_b128", f.b[0], b_at[0], 16384);
+    MXG_READ("ds_read_b128", f.b[1], b_at[0], 18432);
+    MXG_READ("ds_read_b128", f.b[2], b_at[0], 20480);
+    MXG_READ("ds_read_b128", f.b[3], b_at[0], 22528);
+  } else {
+    // chunk 1 is 128 k rows = 8192 bytes on; hi is 16 rows = 1024 on
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+      if constexpr (HS == 0) {
+        MXG_READ("ds_read_b64_tr_b4", f.lo[t], b_at[t], 16384);
+        MXG_READ("ds_read_b64_tr_b4", f.hi[t], b_at[t], 17408);
+      } else {
+        MXG_READ("ds_read_b64_tr_b4", f.lo[t], b_at[t], 24576);
+        MXG_READ("ds_read_b64_tr_b4", f.hi[t], b_at[t], 25600);
+      }
+    }
+  }
+}
+template <int BL, bool OTHERS>
+__device__ __forceinline__ void mxg_wait_half4(MxgFrags4<BL>& f) {
+  if constexpr (BL == GP_NK) {
+#define MXG_WAIT_NK(CNT)                                                                    \
+  asm volatile("s_waitcnt lgkmcnt(" CNT ")"                                                 \
+               : "+v"(f.a[0]), "+v"(f.a[1]), "+v"(f.a[2]), "+v"(f.a[3]), "+v"(f.b[0]),      \
+                 "+v"(f.b[1]), "+v"(f.b[2]), "+v"(f.b[3])::"memory")
+    if constexpr (OTHERS) MXG_WAIT_NK("8");
+    else MXG_WAIT_NK("0");
+#undef MXG_WAIT_NK
+  } else {
+#define MXG_WAIT_KN(CNT)                                                                    \
+  asm volatile("s_waitcnt lgkmcnt(" CNT ")"                                                 \
+               : "+v"(f.a[0]), "+v"(f.a[1]), "+v"(f.a[2]), "+v"(f.a[3]), "+v"(f.lo[0]),     \
+                 "+v"(f.lo[1]), "+v"(f.lo[2]), "+v"(f.lo[3]), "+v"(f.hi[0]), "+v"(f.hi[1]), \
+                 "+v"(f.hi[2]), "+v"(f.hi[3])::"memory")
+    if constexpr (OTHERS) MXG_WAIT_KN("12");
+    else MXG_WAIT_KN("0");
+#undef MXG_WAIT_KN
+  }
+}
+template <int BL>
+__device__ __forceinline__ void mxg_mma_half4(const MxgFrags4<BL>& f, f32x4 (&acc)[4][4], int sa,
+                                              int sb) {
+  const gp_i4 zero = {0, 0, 0, 0};  // the 4-bit form reads VGPRs 0-3 only
+  i32x8 a[4], b[4];
+#pragma unroll
+  for (int t = 0; t < 4; t++) {
+    a[t] = __builtin_shufflevector(f.a[t], zero, 0, 1, 2, 3, 4, 5, 6, 7);
+    if constexpr (BL == GP_NK)
+      b[t] = __builtin_shufflevector(f.b[t], zero, 0, 1, 2, 3, 4, 5, 6, 7);
+    else
+      b[t] = __builtin_shufflevector(__builtin_shufflevector(f.lo[t], f.hi[t], 0, 1, 2, 3), zero,
+                                     0, 1, 2, 3, 4, 5, 6, 7);
+  }
+  MXG_MMA_ROW(4, 0);
+  MXG_MMA_ROW(4, 1);
+  MXG_MMA_ROW(4, 2);
+  MXG_MMA_ROW(4, 3);
+}
+
+// fp8: the whole step's fragments, split by A tiles
+template <int BL> struct MxgFrags8 {
+  gp_i4 a[4][2];         // chunks g and g+4
+  gp_i4 b[4][2];         // nk
+  gp_i2 tr[4][4];        // kn: k 16g.., 16g+8.., 64+16g.., 64+16g+8..
+};
+template <int BL>
+// a_at: the lane's chunks g and g+4 of A tile 0; nk: b_at[0], b_hi[0] likewise
+// of B tile 0; kn: b_at[t] tile t's first read
+__device__ __forceinline__ void mxg_read_step8(MxgFrags8<BL>& f, const unsigned (&a_at)[2],
+                                               const unsigned (&b_at)[4],
+                                               const unsigned (&b_hi)[4]) {
+  if constexpr (BL == GP_NK) {
+    MXG_READ("ds_read_b128", f.b[0][0], b_at[0], 16384);
+    MXG_READ("ds_read_b128", f.b[0][1], b_hi[0], 16384);
+    MXG_READ("ds_read_b128", f.b[1][0], b_at[0], 18432);
+    MXG_READ("ds_read_b128", f.b[1][1], b_hi[0], 18432);
+    MXG_READ("ds_read_b128", f.b[2][0], b_at[0], 20480);
+    MXG_READ("ds_read_b128", f.b[2][1], b_hi[0], 20480);
+    MXG_READ("ds_read_b128", f.b[3][0], b_at[0], 22528);
+    MXG_READ("ds_read_b128", f.b[3][1], b_hi[0], 22528);
+  } else {
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+      MXG_READ("ds_read_b64_tr_b8", f.tr[t][0], b_at[t], 16384);
+      MXG_READ("ds_read_b64_tr_b8", f.tr[t][1], b_at[t], 17408);
+      MXG_READ("ds_read_b64_tr_b8", f.tr[t][2], b_at[t], 24576);
+      MXG_READ("ds_read_b64_tr_b8", f.tr[t][3], b_at[t], 25600);
+    }
+  }
+  MXG_READ("ds_read_b128", f.a[0][0], a_at[0], 0);
+  MXG_READ("ds_read_b128", f.a[0][1], a_at[1], 0);
+  MXG_READ("ds_read_b128", f.a[1][0], a_at[0], 2048);
+  MXG_READ("ds_read_b128", f.a[1][1], a_at[1], 2048);
+  MXG_READ("ds_read_b128", f.a[2][0], a_at[0], 4096);
+  MXG_READ("ds_read_b128", f.a[2][1], a_at[1], 4096);
+  MXG_READ("ds_read_b128", f.a[3][0], a_at[0], 6144);
+  MXG_READ("ds_read_b128", f.a[3][1], a_at[1], 6144);
+}
+// part 0: B and A tiles 0-1 have returned, the four reads of A tiles 2-3 may
+// stay in flight; part 1: everything has
+template <int BL, int PART>
+__device__ __forceinline__ void mxg_wait_part8(MxgFrags8<BL>& f) {
+  if constexpr (PART == 1) {
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(f.a[2][0]), "+v"(f.a[2][1]), "+v"(f.a[3][0]), "+v"(f.a[3][1])::"memory");
+  } else if constexpr (BL == GP_NK) {
+    asm volatile("s_waitcnt lgkmcnt(4)"
+                 : "+v"(f.a[0][0]), "+v"(f.a[0][1]), "+v"(f.a[1][0]), "+v"(f.a[1][1]),
+                   "+v"(f.b[0][0]), "+v"(f.b[0][1]), "+v"(f.b[1][0]), "+v"(f.b[1][1]),
+                   "+v"(f.b[2][0]), "+v"(f.b[2][1]), "+v"(f.b[3][0]), "+v"(f.b[3][1])::"memory");
+  } else {
+    asm volatile("s_waitcnt lgkmcnt(4)"
+                 : "+v"(f.a[0][0]), "+v"(f.a[0][1]), "+v"(f.a[1][0]), "+v"(f.a[1][1]),
+                   "+v"(f.tr[0][0]), "+v"(f.tr[0][1]), "+v"(f.tr[0][2]), "+v"(f.tr[0][3]),
+                   "+v"(f.tr[1][0]), "+v"(f.tr[1][1]), "+v"(f.tr[1][2]), "+v"(f.tr[1][3]),
+                   "+v"(f.tr[2][0]), "+v"(f.tr[2][1]), "+v"(f.tr[2][2]), "+v"(f.tr[2][3]),
+                   "+v"(f.tr[3][0]), "+v"(f.tr[3][1]), "+v"(f.tr[3][2]), "+v"(f.tr[3][3])::"memory");
+  }
+}
+template <int BL, int PART>
+__device__ __forceinline__ void mxg_mma_part8(const MxgFrags8<BL>& f, f32x4 (&acc)[4][4], int sa,
+                                              int sb) {
+  i32x8 a[4], b[4];
+#pragma unroll
+  for (int t = 0; t < 4; t++) {
+    a[t] = __builtin_shufflevector(f.a[t][0], f.a[t][1], 0, 1, 2, 3, 4, 5, 6, 7);
+    if constexpr (BL == GP_NK)
+      b[t] = __builtin_shufflevector(f.b[t][0], f.b[t][1], 0, 1, 2, 3, 4, 5, 6, 7);
+    else
+      b[t] = __builtin_shufflevector(__builtin_shufflevector(f.tr[t][0], f.tr[t][1], 0, 1, 2, 3),
+                                     __builtin_shufflevector(f.tr[t][2], f.tr[t][3], 0, 1, 2, 3),
+                                     0, 1, 2, 3, 4, 5, 6, 7);
+  }
+  if constexpr (PART == 0) {
+    MXG_MMA_ROW(0, 0);
+    MXG_MMA_ROW(0, 1);
+  } else {
+    MXG_MMA_ROW(0, 2);
+    MXG_MMA_ROW(0, 3);
+  }
+}
+#undef MXG_READ
+#undef MXG_MMA_ROW
+#undef MXG_MMA
+
+template <int FMT, int BL>
+__global__ void __launch_bounds__(256, 2)
+mx_gemm_pipe_kernel(const char* __restrict__ A, const char* __restrict__ B,
+                    const unsigned char* __restrict__ scale_a,
+                    const unsigned char* __restrict__ scale_b, const float* __restrict__ expected,
+                    int4* __restrict__ records, float* __restrict__ C, int N, int K, int tiles_n,
+                    int rounds, int store_c, int inject_block, int inject_round) {
+  __shared__ __attribute__((aligned(1024))) char mxg_lds[GP_STAGES * GP_STAGE_BYTES];
+  constexpr int BK = FMT == MXG_FP8 ? GP_STEP_BYTES : 2 * GP_STEP_BYTES;  // elements per step
+  constexpr int STEP_BLOCKS = BK / 32;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int i16 = lane & 15, g = lane >> 4;
+  const int m0 = (blockIdx.x / tiles_n) * GP_TILE, n0 = (blockIdx.x % tiles_n) * GP_TILE;
+  const unsigned place = hw_word();
+  const int steps = K / BK;
+  const unsigned row_bytes = FMT == MXG_FP8 ? (unsigned)K : (unsigned)K >> 1;  // A, B nk
+  const unsigned n_bytes = FMT == MXG_FP8 ? (unsigned)N : (unsigned)N >> 1;    // B kn
+  const unsigned kblocks = (unsigned)K >> 5;
+
+  // where this lane's 16 bytes of each load come from, relative to the tile's
+  // first byte of the step
+  unsigned aoff[4], boff[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const int t = wave * 4 + i;
+    const int r = 8 * t + (lane >> 3), s = lane & 7;
+    aoff[i] = (unsigned)r * row_bytes + ((s ^ gp_key_b128(r)) << 4);
+    if constexpr (BL == GP_NK) {
+      boff[i] = aoff[i];
+    } else if constexpr (FMT == MXG_FP8) {
+      boff[i] = (unsigned)r * n_bytes + ((s ^ gp_key_tr8(r)) << 4);
+    } else {
+      const int k = 16 * t + (lane >> 2), s4 = lane & 3;
+      boff[i] = (unsigned)k * n_bytes + ((s4 ^ mxg_key_tr4(k)) << 4);
+    }
+  }
+  const char* a_tile = A + (size_t)m0 * row_bytes;
+  const char* b_tile = BL == GP_NK ? B + (size_t)n0 * row_bytes
+                                   : B + (FMT == MXG_FP8 ? n0 : n0 >> 1);
+  const size_t a_step = GP_STEP_BYTES;
+  const size_t b_step = BL == GP_NK ? (size_t)GP_STEP_BYTES : (size_t)BK * n_bytes;
+
+  // the lane's scale bytes of a step, relative to the step's first byte of the
+  // workgroup's rows (columns); a step is STEP_BLOCKS bytes (kn: rows) on
+  // (tile 0; the other tiles and K chunk 1 are wave-uniform strides on)
+  const unsigned sa_off = (unsigned)(wm * 64 + i16) * kblocks + g;
+  const unsigned sb_off = BL == GP_NK ? (unsigned)(wn * 64 + i16) * kblocks + g
+                                      : (unsigned)g * (unsigned)N + wn * 64 + i16;
+  const size_t sa_stride = (size_t)16 * kblocks;
+  const size_t sb_stride = BL == GP_NK ? (size_t)16 * kblocks : (size_t)4 * N;
+  const unsigned char* sa_tile = scale_a + (size_t)m0 * kblocks;
+  const unsigned char* sb_tile = BL == GP_NK ? scale_b + (size_t)n0 * kblocks : scale_b + n0;
+  const size_t sa_step = STEP_BLOCKS;
+  const size_t sb_step = BL == GP_NK ? (size_t)STEP_BLOCKS : (size_t)STEP_BLOCKS * N;
+
+  // LDS byte offsets of this lane's fragment reads inside a stage, as in
+  // gemm_pipe_kernel; fp4 kn: per tile, the chunk and the read are immediates
+  unsigned a_at[2], b_at[4];
+  {
+    const int ra = wm * 64 + i16;
+    a_at[0] = ra * 128 + ((g ^ gp_key_b128(ra)) << 4);
+    a_at[1] = a_at[0] ^ 64;
+  }
+  if constexpr (BL == GP_NK) {
+    const int rb = wn * 64 + i16;
+    b_at[0] = rb * 128 + ((g ^ gp_key_b128(rb)) << 4);
+    b_at[1] = b_at[0] ^ 64;
+    b_at[2] = b_at[3] = 0;
+  } else {
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+      if constexpr (FMT == MXG_FP8) {
+        const int nb = wn * 64 + t * 16;
+        const int k = g * 16 + (i16 >> 1);
+        b_at[t] = k * 128 + (((nb >> 4) ^ gp_key_tr8(k)) << 4) + (i16 & 1) * 8;
+      } else {
+        const int k = g * 32 + i16;
+        b_at[t] = k * 64 + (((wn * 2 + (t >> 1)) ^ mxg_key_tr4(k)) << 4) + (t & 1) * 8;
+      }
+    }
+  }
+
+  GP_LDS_AS char* lds = (GP_LDS_AS char*)mxg_lds;
+  const unsigned lds_base = (unsigned)reinterpret_cast<__UINTPTR_TYPE__>(lds);
+  const bool inject_here = (int)blockIdx.x == inject_block && threadIdx.x == 0;
+  int mismatched = 0, first_round = -1;
+  unsigned first_index = 0xFFFFFFFFu, checksum = 0;
+  unsigned raw_a[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, raw_b[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+  f32x4 acc[4][4];
+  for (int round = 0; round < rounds; round++) {
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        // opaque to the optimiser: every round really recomputes its tile
+        asm volatile("" : "+v"(acc[i][j]));
+      }
+    const char* a_src = a_tile;
+    const char* b_src = b_tile;
+    const unsigned char* sa_src = sa_tile;
+    const unsigned char* sb_src = sb_tile;
+    // stage 0 may still be read by a wave that is finishing the last round
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    gp_issue(a_src, b_src, aoff, boff, lds, wave);
+    mxg_load_scales<FMT, BL>(raw_a, raw_b, sa_src, sb_src, sa_off, sb_off, sa_stride,
+                             sb_stride);
+    // one K step. MORE: not the last one. The last step is peeled off the loop
+    // so that the loop body has no branch: the scale registers then form one
+    // chain of tied operands (load, wait, load, ...) that the compiler keeps in
+    // place; a copy of a register with a load in flight would read stale bytes
+    auto step = [&](auto more_c, int k) {
+      constexpr bool MORE = decltype(more_c)::value;
+      // barrier 1: the other stage has been read for the last time
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      if constexpr (MORE) {
+        a_src += a_step;
+        b_src += b_step;
+        gp_issue(a_src, b_src, aoff, boff, lds + ((k + 1) & 1) * GP_STAGE_BYTES, wave);
+      }
+      // step k's operands and scales are in; step k+1's eight stay in flight
+      mxg_wait_vm<FMT, MORE>(raw_a, raw_b);
+      const int sa0 = mxg_gather(raw_a[0]), sb0 = mxg_gather(raw_b[0]);
+      [[maybe_unused]] int sa1 = 0, sb1 = 0;
+      if constexpr (FMT == MXG_FP4) {
+        sa1 = mxg_gather(raw_a[1]);
+        sb1 = mxg_gather(raw_b[1]);
+      }
+      if constexpr (MORE) {
+        // the gathered values exist before their registers are loaded again
+        asm volatile("" : : "v"(sa0), "v"(sb0));
+        if constexpr (FMT == MXG_FP4) asm volatile("" : : "v"(sa1), "v"(sb1));
+        sa_src += sa_step;
+        sb_src += sb_step;
+        mxg_load_scales<FMT, BL>(raw_a, raw_b, sa_src, sb_src, sa_off, sb_off, sa_stride,
+                                 sb_stride);
+      }
+      // barrier 2: every wave's part of step k has landed
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      const unsigned st = lds_base + (k & 1) * GP_STAGE_BYTES;
+      unsigned b0[4], b1[4];
+#pragma unroll
+      for (int t = 0; t < 4; t++) {
+        b0[t] = st + b_at[BL == GP_NK ? 0 : t];
+        b1[t] = st + b_at[BL == GP_NK ? 1 : t];
+      }
+      if constexpr (FMT == MXG_FP4) {
+        MxgFrags4<BL> f0, f1;
+        mxg_read_half4<BL, 0>(f0, st + a_at[0], b0);
+        mxg_read_half4<BL, 1>(f1, st + a_at[1], b1);
+        mxg_wait_half4<BL, true>(f0);  // chunk 1's reads stay in flight
+        mxg_mma_half4<BL>(f0, acc, sa0, sb0);
+        __builtin_amdgcn_sched_barrier(0);  // chunk 0's MFMAs stay above the wait
+        mxg_wait_half4<BL, false>(f1);
+        mxg_mma_half4<BL>(f1, acc, sa1, sb1);
+      } else {
+        MxgFrags8<BL> f;
+        const unsigned a2[2] = {st + a_at[0], st + a_at[1]};
+        mxg_read_step8<BL>(f, a2, b0, b1);
+        mxg_wait_part8<BL, 0>(f);  // A tiles 2-3 stay in flight
+        mxg_mma_part8<BL, 0>(f, acc, sa0, sb0);
+        __builtin_amdgcn_sched_barrier(0);  // part 0's MFMAs stay above the wait
+        mxg_wait_part8<BL, 1>(f);
+        mxg_mma_part8<BL, 1>(f, acc, sa0, sb0);
+      }
+    };
+    for (int k = 0; k + 1 < steps; k++) step(std::true_type{}, k);
+    step(std::false_type{}, steps - 1);
+    if (inject_here && round == inject_round)
+      acc[0][0][0] = __uint_as_float(__float_as_uint(acc[0][0][0]) ^ 1u);
+    // expected is read again every round, and the lane's place in it is worked
+    // out again: both are opaque to the optimiser, which would otherwise keep
+    // the addresses of the compare and of the store in registers over the K loop
+    int again = 0, lane_v = lane;
+    asm volatile("" : "+s"(again), "+v"(lane_v));
+    const int i16v = lane_v & 15, gv = lane_v >> 4;
+    const float* want_lane = expected + (wm * 64 + gv * 4) * GP_TILE + wn * 64 + i16v;
+    const float* want = want_lane + again;
+    unsigned bad = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const unsigned bits = __float_as_uint(acc[i][j][r]);
+          bad += bits != __float_as_uint(want[(i * 16 + r) * GP_TILE + j * 16]);
+          checksum ^= bits;
+        }
+      asm volatile("" ::: "memory");  // 16 expected values in registers at a time, not 64
+    }
+    bad = wave_add(bad);
+    if (bad) {  // wave-uniform, and rare
+      if (first_round < 0) {
+        first_round = round;
+        asm volatile("" : "+s"(again));  // a second read, not the first one's compare masks
+        want = want_lane + again;
+        unsigned index = 0xFFFFFFFFu;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+          for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+              if (__float_as_uint(acc[i][j][r]) !=
+                  __float_as_uint(want[(i * 16 + r) * GP_TILE + j * 16]))
+                index = min(index, (unsigned)((i * 16 + gv * 4 + r) * 64 + j * 16 + i16v));
+        first_index = wave_min(index);
+      }
+      mismatched += (int)bad;
+    }
+  }
+  if (store_c) {
+    int lane_v = lane;
+    asm volatile("" : "+v"(lane_v));  // as above
+    const int i16v = lane_v & 15, gv = lane_v >> 4;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+          C[(size_t)(m0 + wm * 64 + i * 16 + gv * 4 + r) * N + n0 + wn * 64 + j * 16 + i16v] =
+              acc[i][j][r];
+  }
+  checksum = wave_xor(checksum);
+  if (lane == 0)
+    store_record8(records, blockIdx.x * 4 + wave, (int)place, mismatched, first_round,
+                  (int)first_index, (int)checksum, 0, 0, 0);
+}
+
+// fmt "mxfp8": e4m3, one code per byte; "mxfp4": e2m1, two codes per byte along
+// K (A, B nk) or N (B kn), the even element in the low nibble. A [M,K]; B
+// [N,K] ("nk") or [K,N] ("kn"); scale_a [M,K/32]; scale_b [N,K/32] or [K/32,N];
+// all uint8, row-major. expected [128,128] fp32, the tile every workgroup must
+// compute. One untimed warm-up launch, then one timed launch. Returns (records
+// [grid*4,8] int32, C [M,N] fp32 when store_c else an empty tensor, elapsed_ms).
+// The wrapper does not judge exactness: any finite operands give a correct GEMM.
+std::tuple<torch::Tensor, torch::Tensor, double> mx_gemm_pipe(
+    torch::Tensor A, torch::Tensor B, torch::Tensor scale_a, torch::Tensor scale_b,
+    torch::Tensor expected, const std::string& fmt, const std::string& b_layout, long rounds,
+    bool store_c, long inject_block, long inject_round) {
+  const int f = fmt == "mxfp8" ? MXG_FP8 : fmt == "mxfp4" ? MXG_FP4 : -1;
+  TORCH_CHECK(f >= 0, "fmt must be one of mxfp8, mxfp4; got ", fmt);
+  const int bl = b_layout == "kn" ? GP_KN : b_layout == "nk" ? GP_NK : -1;
+  TORCH_CHECK(bl >= 0, "b_layout must be one of kn, nk; got ", b_layout);
+  for (const torch::Tensor* t : {&A, &B, &scale_a, &scale_b, &expected}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == A.device(),
+                "A, B, the scales and expected must be on one GPU");
+    TORCH_CHECK(t->dim() == 2, "A, B, the scales and expected must be 2-D");
+  }
+  TORCH_CHECK(A.dtype() == torch::kUInt8 && B.dtype() == torch::kUInt8 &&
+                  scale_a.dtype() == torch::kUInt8 && scale_b.dtype() == torch::kUInt8,
+              "A, B and the scales must be uint8");
+  TORCH_CHECK(expected.dtype() == torch::kFloat32 &&
+                  expected.sizes() == torch::IntArrayRef({GP_TILE, GP_TILE}),
+              "expected must be float32 [128,128]");
+  const long pack = f == MXG_FP4 ? 2 : 1;  // codes per byte
+  const long BK = f == MXG_FP4 ? 256 : 128;
+  const long M = A.size(0), K = A.size(1) * pack;
+  const long N = bl == GP_NK ? B.size(0) : B.size(1) * pack;
+  TORCH_CHECK(M >= GP_TILE && N >= GP_TILE && M % GP_TILE == 0 && N % GP_TILE == 0,
+              "M and N must be positive multiples of 128; got ", M, ", ", N);
+  TORCH_CHECK(K >= BK && K % BK == 0, "K must be a positive multiple of ", BK, "; got ", K);
+  // the kernel's per-lane offsets into a tile's rows are 32-bit
+  TORCH_CHECK(M <= (1L << 22) && N <= (1L << 22) && K <= (1L << 22),
+              "M, N and K must be <= 2^22");
+  if (bl == GP_NK) {
+    TORCH_CHECK(B.size(1) * pack == K, "B must be [N,K] in ", K / pack, " bytes per row");
+    TORCH_CHECK(scale_b.sizes() == torch::IntArrayRef({N, K / 32}), "scale_b must be [", N, ",",
+                K / 32, "]");
+  } else {
+    TORCH_CHECK(B.size(0) == K, "B must be [K,N] with K=", K);
+    TORCH_CHECK(scale_b.sizes() == torch::IntArrayRef({K / 32, N}), "scale_b must be [", K / 32,
+                ",", N, "]");
+  }
+  TORCH_CHECK(scale_a.sizes() == torch::IntArrayRef({M, K / 32}), "scale_a must be [", M, ",",
+              K / 32, "]");
+  const long tiles_n = N / GP_TILE, grid = (M / GP_TILE) * tiles_n;
+  TORCH_CHECK(rounds >= 1, "rounds must be >= 1");
+  // bounded run, as for gemm_pipe
+  TORCH_CHECK(grid <= (1L << 20) && rounds <= (1L << 22) && rounds * K * grid <= (1L << 33),
+              "rounds*K*grid must be <= 2^33; got ", rounds, "*", K, "*", grid);
+  TORCH_CHECK(inject_block >= -1 && inject_block < grid && inject_round >= -1 &&
+                  inject_round < rounds,
+              "inject_block/inject_round out of range");
+  A = A.contiguous();
+  B = B.contiguous();
+  scale_a = scale_a.contiguous();
+  scale_b = scale_b.contiguous();
+  expected = expected.contiguous();
+  // a direct-to-LDS load fetches 16 aligned bytes
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(A.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(B.data_ptr()) % 16 == 0,
+              "A and B must be 16-byte aligned");
+  auto records = zero_records(grid * 4, 8, A.device());
+  auto C = store_c ? torch::zeros({M, N}, expected.options())
+                   : torch::empty({0}, expected.options());
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  const double ms = warm_then_timed_ms(stream, [&]() {
+    dispatch_int<4>(2 * f + bl, [&](auto case_c) {
+      constexpr int c = decltype(case_c)::value;
+      hipLaunchKernelGGL((mx_gemm_pipe_kernel<c / 2, c % 2>), dim3(grid), dim3(256), 0, stream,
+                         static_cast<const char*>(A.data_ptr()),
+                         static_cast<const char*>(B.data_ptr()),
+                         scale_a.data_ptr<unsigned char>(), scale_b.data_ptr<unsigned char>(),
+                         expected.data_ptr<float>(),
+                         reinterpret_cast<int4*>(records.data_ptr<int>()),
+                         store_c ? C.data_ptr<float>() : nullptr, (int)N, (int)K, (int)tiles_n,
+                         (int)rounds, (int)store_c, (int)inject_block, (int)inject_round);
+    });
+  });
+  return std::make_tuple(records, C, ms);
+}
+
 py::dict device_info(int dev) {
   hipDeviceProp_t prop;
   HIP_CHECK(hipGetDeviceProperties(&prop, dev));
@@ -6634,6 +7296,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("inject_block") = -1, py::arg("inject_round") = -1,
         "Tiled GEMM pipeline (fmt bf16|fp8, b_layout kn|nk): direct-to-LDS loads, LDS fragment "
         "reads (transpose reads for kn) and MFMAs, every 128x128 tile compared bitwise with "
+        "expected each round; returns (per-wave records [grid*4,8], C or empty, ms)");
+  m.def("mx_gemm_pipe", &mx_gemm_pipe, py::arg("A"), py::arg("B"), py::arg("scale_a"),
+        py::arg("scale_b"), py::arg("expected"), py::arg("fmt"), py::arg("b_layout"),
+        py::arg("rounds") = 1, py::arg("store_c") = false, py::arg("inject_block") = -1,
+        py::arg("inject_round") = -1,
+        "Block-scaled tiled GEMM pipeline (fmt mxfp8|mxfp4, b_layout kn|nk): direct-to-LDS loads, "
+        "LDS fragment reads (8- and 4-bit transpose reads for kn), per-block E8M0 scales streamed "
+        "from memory and the scaled 16x16x128 MFMA, every 128x128 tile compared bitwise with "
         "expected each round; returns (per-wave records [grid*4,8], C or empty, ms)");
   m.def("cu_coverage", &cu_coverage, py::arg("blocks") = 4096,
         "Per-wave (XCC_ID<<16 | HW_ID) placement words for CU-coverage checks");
