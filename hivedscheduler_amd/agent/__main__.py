@@ -93,6 +93,12 @@ def main() -> None:
                          "exact, per CU) every N sweeps (on deep sweeps); 0 = never")
     ap.add_argument("--mx-gemm-probe", action="store_true",
                     help="with --local: also run the MX GEMM probe")
+    ap.add_argument("--mx6-gemm-probe-every", type=int, default=0,
+                    help="MX6 GEMM probe (tiled MXFP6 / MXBF6 GEMM and MXFP8 against MXFP6 / "
+                         "MXFP4 weights: the MX GEMM probe's pipeline for 96- and 64-byte rows, "
+                         "exact, per CU) every N sweeps (on deep sweeps); 0 = never")
+    ap.add_argument("--mx6-gemm-probe", action="store_true",
+                    help="with --local: also run the MX6 GEMM probe")
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
@@ -115,7 +121,8 @@ def main() -> None:
                                      matrix_probe=args.matrix_probe,
                                      cvt_probe=args.cvt_probe,
                                      gemm_probe=args.gemm_probe,
-                                     mx_gemm_probe=args.mx_gemm_probe)
+                                     mx_gemm_probe=args.mx_gemm_probe,
+                                     mx6_gemm_probe=args.mx6_gemm_probe)
         if args.p2p_matrix:
             try:
                 m = p2p_link_matrix()
@@ -145,7 +152,8 @@ def main() -> None:
                             matrix_probe_every=args.matrix_probe_every,
                             cvt_probe_every=args.cvt_probe_every,
                             gemm_probe_every=args.gemm_probe_every,
-                            mx_gemm_probe_every=args.mx_gemm_probe_every)
+                            mx_gemm_probe_every=args.mx_gemm_probe_every,
+                            mx6_gemm_probe_every=args.mx6_gemm_probe_every)
     if args.once:
         import json
 

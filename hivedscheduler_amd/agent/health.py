@@ -67,6 +67,7 @@ def collect_node_health(
     cvt_probe: bool = False,
     gemm_probe: bool = False,
     mx_gemm_probe: bool = False,
+    mx6_gemm_probe: bool = False,
 ) -> dict:
     """One health sweep over all visible GPUs. deep=True also runs the HIP
     kernels (HBM + MFMA); sweep=True adds the 16 GiB HBM stuck-bit pattern
@@ -164,6 +165,14 @@ def collect_node_health(
     judged) and `mx_gemm_bad_cus` (the CUs of any wave whose tile was wrong, as
     xcc, se, sh, cu), and a failed probe marks the leaf bad.
 
+    mx6_gemm_probe=True (with deep) adds the MX6 GEMM probe (that pipeline for
+    MXFP6 / MXBF6 in both B layouts and an MXFP8 A against MXFP6 / MXFP4
+    weights: 96- and 64-byte rows, the 6-bit transpose read, two row pitches
+    into one scaled MFMA, exact and compared bitwise): per GPU it records
+    `mx6_gemm_probe_ok`, `mx6_gemm_tflops` ({case: TFLOP/s}, reported, not
+    judged) and `mx6_gemm_bad_cus` (the CUs of any wave whose tile was wrong,
+    as xcc, se, sh, cu), and a failed probe marks the leaf bad.
+
     The stuck-bit scan transiently holds up to 16 GiB of HBM; on a GPU
     running tenant jobs this can make the tenant's own allocations fail.
     Keep sweep on the low-frequency cadence and prefer idle GPUs (the
@@ -189,7 +198,7 @@ def collect_node_health(
                             atomic_probe=atomic_probe, mx_scale_probe=mx_scale_probe,
                             mempath_probe=mempath_probe, matrix_probe=matrix_probe,
                             cvt_probe=cvt_probe, gemm_probe=gemm_probe,
-                            mx_gemm_probe=mx_gemm_probe)
+                            mx_gemm_probe=mx_gemm_probe, mx6_gemm_probe=mx6_gemm_probe)
         for i in range(n):
             gpu = report["gpus"][str(i)]
             try:
@@ -346,6 +355,16 @@ def collect_node_health(
                     )
                     if not p["ok"] or p["bad_cus"]:
                         gpu["healthy"] = False
+                if mx6_gemm_probe:
+                    p = rep["mx6_gemm_probe"]
+                    gpu.update(
+                        mx6_gemm_probe_ok=bool(p["ok"]),
+                        mx6_gemm_tflops={name: round(s["tflops"], 1)
+                                         for name, s in p["cases"].items()},
+                        mx6_gemm_bad_cus=p["bad_cus"],
+                    )
+                    if not p["ok"] or p["bad_cus"]:
+                        gpu["healthy"] = False
             except Exception as e:
                 gpu.update(healthy=False, error=str(e)[:200])
     if probe_pairs and n >= 2:
@@ -424,7 +443,7 @@ class NodeHealthAgent:
                  atomic_probe_every: int = 0, mx_scale_probe_every: int = 0,
                  mempath_probe_every: int = 0, matrix_probe_every: int = 0,
                  cvt_probe_every: int = 0, gemm_probe_every: int = 0,
-                 mx_gemm_probe_every: int = 0):
+                 mx_gemm_probe_every: int = 0, mx6_gemm_probe_every: int = 0):
         self.scheduler_url = scheduler_url.rstrip("/")
         self.node_name = node_name or socket.gethostname()
         self.interval_s = interval_s
@@ -484,6 +503,9 @@ class NodeHealthAgent:
         # MX GEMM probe cadence (the same pipeline through the block-scaled
         # MFMA with streamed scales), same pattern; 0 = never
         self.mx_gemm_probe_every = mx_gemm_probe_every
+        # MX6 GEMM probe cadence (that pipeline for 6-bit and mixed-width
+        # operands), same pattern; 0 = never
+        self.mx6_gemm_probe_every = mx6_gemm_probe_every
         self._rounds = 0
 
     def post_report(self, report: dict) -> bool:
@@ -547,7 +569,8 @@ class NodeHealthAgent:
                             matrix_probe=deep and self._due(self.matrix_probe_every),
                             cvt_probe=deep and self._due(self.cvt_probe_every),
                             gemm_probe=deep and self._due(self.gemm_probe_every),
-                            mx_gemm_probe=deep and self._due(self.mx_gemm_probe_every))
+                            mx_gemm_probe=deep and self._due(self.mx_gemm_probe_every),
+                            mx6_gemm_probe=deep and self._due(self.mx6_gemm_probe_every))
         self._rounds += 1
         if "burn" in kwargs:
             kwargs["min_mfma_tflops"] = self.min_mfma_tflops

@@ -6,7 +6,7 @@ extension is REQUIRED: failure to load raises (no silent eager fallback).
 Here: the loader, `gpu_health_report` and the single-tile MFMA checks. Each
 opt-in probe has a module of its own (mfma_burn, lds_march, hbm_march,
 simd_probe, scalar_probe, atomic_probe, mx_scale, mempath_probe, matrix_paths,
-cvt_probe, gemm_probe, mx_gemm_probe)
+cvt_probe, gemm_probe, mx_gemm_probe, mx6_gemm_probe)
 on top of `records`, and the
 single-tile checks' operands and verdict are in mfma_tiles; their public names
 are re-exported here, and their report functions reach the extension through
@@ -56,6 +56,10 @@ from .mfma_tiles import (E4M3_GROUP_WINDOW_BITS, E4M3_NAN_CODES, TILE_FORMATS,  
                          tile_operand_invariants, tile_product)
 from .mfma_burn import (BURN_FORMATS, _burn_integers, burn_chain_limit, burn_operands,  # noqa: F401
                         mfma_burn_report, summarize_burn)
+from .mx6_gemm_probe import (MX6_GEMM_BK, MX6_GEMM_CASES, MX6_GEMM_PERIOD,  # noqa: F401
+                             mx6_gemm_case_name, mx6_gemm_layout, mx6_gemm_operands,
+                             mx6_gemm_probe_report, mx6_gemm_reference, mx6_gemm_step_bytes,
+                             mx6_pack6, mx6_unpack6, summarize_mx6_gemm_probe)
 from .mx_gemm_probe import (MX_GEMM_CASES, MX_GEMM_FORMATS, MX_GEMM_LAYOUTS,  # noqa: F401
                             MX_GEMM_MAX_K, mx_gemm_bk, mx_gemm_encode, mx_gemm_layout,
                             mx_gemm_operands, mx_gemm_pack, mx_gemm_period,
@@ -111,7 +115,8 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
                       scalar_probe: bool = False, atomic_probe: bool = False,
                       mx_scale_probe: bool = False, mempath_probe: bool = False,
                       matrix_probe: bool = False, cvt_probe: bool = False,
-                      gemm_probe: bool = False, mx_gemm_probe: bool = False) -> dict:
+                      gemm_probe: bool = False, mx_gemm_probe: bool = False,
+                      mx6_gemm_probe: bool = False) -> dict:
     """Run the health-probe kernels on one GPU and return measured facts.
 
     Feeds leaf-cell healthiness: HBM bandwidth deficit, MFMA mismatch, or
@@ -197,6 +202,13 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     tile compared bitwise in registers, tens of milliseconds per case) as
     report["mx_gemm_probe"] and ANDs its verdict into `healthy`. Off by
     default, and the report is then unchanged.
+
+    mx6_gemm_probe=True adds the MX6 GEMM probe (`mx6_gemm_probe_report`: that
+    pipeline for MXFP6 and MXBF6 in both B layouts and for an MXFP8 A against
+    MXFP6 and MXFP4 weights, 96- and 64-byte rows and the 6-bit transpose
+    read, every tile compared bitwise in registers, tens of milliseconds per
+    case) as report["mx6_gemm_probe"] and ANDs its verdict into `healthy`. Off
+    by default, and the report is then unchanged.
     """
     ops = _ops_on(device)
     size_mb = 256 if quick else 2048
@@ -278,6 +290,9 @@ def gpu_health_report(device: int = 0, quick: bool = True, deep: bool = False,
     if mx_gemm_probe:
         report["mx_gemm_probe"] = mx_gemm_probe_report(device)
         report["healthy"] = bool(report["healthy"] and report["mx_gemm_probe"]["ok"])
+    if mx6_gemm_probe:
+        report["mx6_gemm_probe"] = mx6_gemm_probe_report(device)
+        report["healthy"] = bool(report["healthy"] and report["mx6_gemm_probe"]["ok"])
     return report
 
 

@@ -53,6 +53,9 @@
 //  - mx_gemm_pipe: the same pipeline through the block-scaled MFMA: a tiled
 //                MXFP8 / MXFP4 GEMM whose E8M0 scale bytes are streamed from
 //                memory beside the operands, exact and compared bitwise
+//  - mx6_gemm_pipe: that pipeline for rows that are not 128 bytes: MXFP6 / MXBF6
+//                (96-byte rows, ds_read_b96_tr_b6 for B kn) and an MXFP8 A against
+//                MXFP6 / MXFP4 weights, exact and compared bitwise
 //  - p2p copy:  xGMI link bandwidth between two GPUs (expected ~153 GB/s per
 //                link per direction); a degraded link marks the PAIR cell bad
 //
@@ -7148,6 +7151,647 @@ std::tuple<torch::Tensor, torch::Tensor, double> mx_gemm_pipe(
   return std::make_tuple(records, C, ms);
 }
 
+// ---------------------------------------------------------------------------
+// MX6 GEMM probe: mx_gemm_pipe's pipeline for the operands whose rows are not
+// 128 bytes: MXFP6 (e2m3) and MXBF6 (e3m2), four codes in three bytes, and an
+// MXFP8 A against MXFP6 or MXFP4 weights (W6A8, W4A8: cbsz != blgp).
+// C = (A o scales).(B o scales) through v_mfma_scale_f32_16x16x128_f8f6f4.
+//
+// Kept as in mx_gemm_pipe_kernel, to be read side by side with it: 256 threads
+// per 128x128 tile of C, waves 2x2, 4x4 MFMA tiles per wave, 64 accumulators
+// held over the K loop; two LDS stages of 32 KiB (A region at 0, B region at
+// 16 KiB); barrier 1 / issue step k+1 / wait / barrier 2 / read / MFMA; the
+// scale bytes (one K chunk of four blocks per step: 4 A and 4 B
+// global_load_ubyte per lane, mx6_load_scales) a step ahead, gathered into one VGPR per
+// side and selected with op_sel; the last step peeled; verification, records,
+// store_c and inject.
+//
+// New: a K step is 128 *elements* in every case, one scaled MFMA deep, so a
+// side's tile of a step is 128 rows of 128 (8-bit), 96 (6-bit) or 64 (4-bit)
+// bytes. A side is one of four kinds (AW, BW, BL choose them):
+//
+//   K8  8-bit, K-contiguous (A e4m3). As mx_gemm_pipe: 4 global_load_lds_dwordx4
+//       per wave, two ds_read_b128 (chunks g and g+4: k = 16g.. and 64+16g..,
+//       the 8-bit K walk), key (r>>1)&7.
+//   K6  6-bit, K-contiguous (A, B nk). The tile is 768 16-byte chunks, 3 loads
+//       per wave; chunk c lands at 16 c = row c/6, slot c%6, and fetches global
+//       chunk slot ^ key(row) of the row's 96 bytes of this step. Lane (i, g)
+//       holds k = 32g.., bits [6j, 6j+6) of six VGPRs: bytes 24g..24g+23 of
+//       its row, the 8-byte units u = 3g, 3g+1, 3g+2 of the row's twelve, read
+//       with three ds_read_b64 at 96 r + 16 ((u>>1) ^ key) + 8 (u&1): 8-byte
+//       aligned, each inside one chunk.
+//       key = (r>>3) & 1 (slots 0<->1, 2<->3, 4<->5). A row is 24 banks, so
+//       the rows start on banks 24r mod 64 = 0, 24, 48, 8, 32, 56, 16, 40 and
+//       rows r, r+8 on the same one. Assuming one LDS pass serves 32
+//       consecutive lanes of a b64 read (groups g, g+1, 16 rows each, the same
+//       read of each): with c0 = 2u mod 8, group g's rows 0-7 take banks
+//       8m + c0 (+1), its rows 8-15, moved one slot = 4 banks by the key,
+//       8m + c0 + 4 (+1); group g+1 wants unit u + 3, 6 banks on: 8m + c0 + 6
+//       and 8m + c0 + 2. The four sets are disjoint and fill the 64 banks:
+//       conflict degree 1 by construction under that assumption (2 without
+//       the key); not measured with counters.
+//   K4  4-bit, K-contiguous (B nk e2m1), 64-byte rows: 512 chunks, 2 loads per
+//       wave, row c/4, slot c%4; lane (i, g) holds k = 32g.. = chunk g, one
+//       ds_read_b128 at 64 r + 16 (g ^ key). Four rows fill the 64 banks, rows
+//       r, r+4 start on the same one: key = (r>>2) & 3 puts the 16 rows of a
+//       pass (16 lanes of a b128 read, as in gemm_pipe) on 16 different
+//       4-bank spans: degree 1 by construction under that assumption.
+//   T6  6-bit B kn: B [K, N 3/4], four codes of consecutive n in three bytes.
+//       The fragment comes through ds_read_b96_tr_b6 (map: lds_tr_read above):
+//       a group's 16 lanes address the k rows 32g + 16h + i for read h, lane i
+//       the 12 bytes = 16 codes = one MFMA tile's columns of its row, and
+//       receives column i, the lowest k in the lowest bits; the two reads are
+//       the lane's 32 k in six VGPRs. The instruction is issued at 16-byte
+//       aligned addresses only (what lds_tr_read enforces; less is not tried),
+//       so the 12-byte units lie at a 16-byte pitch: a tile row (one k) is
+//       eight units = 128 bytes, the tile 16 KiB.
+//       They get there with global_load_lds_dword (lane l's dword lands at
+//       M0 + 4 l, as the memory-path probe established): one instruction
+//       fills two rows, lane l row l>>5, unit slot (l>>2)&7, word l&3; word 3
+//       is the padding and fetches word 2 again, an address inside the tile
+//       in any case. 16 instructions per wave and step. Chosen over a staged
+//       global_load_dwordx3 / ds_write_b96 path because it keeps the pipeline
+//       of the other kinds unchanged: no registers held over the MFMAs, no
+//       lgkmcnt accounting for writes, one vmcnt wait. The direct dwordx3
+//       form is not used: its lane-to-LDS map is not established here.
+//       The dword loads move 16 KiB per step for 12 KiB of operands.
+//       key = (k>>1) & 7 on the unit slot: a row is 32 banks, rows k, k+2
+//       collide; the 16 rows of one read fall, per parity of k, on eight
+//       different slots. Degree 1 by construction assuming one pass serves
+//       the 16 lanes of a group, as for b128; if a pass serves 32 lanes, 96
+//       banks are wanted and the degree is 2 at best. Not measured.
+//       Row 2 (16 w + j) + (l>>5) of wave w's load j has key j & 7, a constant
+//       per load: a lane keeps its row-and-word offset and its slot, and the
+//       source unit slot ^ (j & 7) is one xor and one multiply-add per load.
+//
+// The 8-bit side walks K in two halves and the narrow side as 32g + j; the
+// instruction pairs them by k, and lane group b's scale byte covers k in
+// [32b, 32b+32) on both sides, so the scale loads do not depend on the kind.
+//
+// vmcnt, oldest first, with L = A loads + B loads per wave and step (K8 4, K6
+// 3, K4 2, T6 16). Before the loop: LDS(0) [L], scales(0) [8]. Step k: after
+// barrier 1, LDS(k+1) [L] is issued; in flight are LDS(k), scales(k),
+// LDS(k+1), and s_waitcnt vmcnt(L) leaves exactly LDS(k+1): step k's operands
+// have landed and its scale bytes are in registers. They are gathered, then
+// scales(k+1) [8] is issued behind LDS(k+1). L = 7 for 8x6, 6 for 6x6 nk and
+// 8x4, 19 for 6x6 kn; at most 2 L + 8 = 46 loads in flight, below the
+// counter's 63. The last step waits vmcnt(0).
+//
+// lgkmcnt: B's four tiles and A tiles 0-1 are read, then A tiles 2-3 (R reads:
+// K8 4, K6 6); lgkmcnt(R) before the 8 MFMAs of A tiles 0-1, lgkmcnt(0) before
+// the other 8. The waits are followed by empty asm statements that name the
+// fragment registers: volatile asm keeps its order, so no use moves above.
+//
+// Race and bounds: no wave waits for another workgroup; every loop bound is a
+// launch argument; nothing is indexed by a loaded value; the wrapper fixes
+// every shape the offsets are computed from; vector stores only. Build for
+// gfx950: no scratch, 64 KiB of LDS (register counts in BENCHMARKS.md "MX6
+// GEMM probe").
+// ---------------------------------------------------------------------------
+enum { MX6_K8 = 0, MX6_K6 = 1, MX6_K4 = 2, MX6_T6 = 3 };
+constexpr int MX6_BK = 128;  // elements of K per step
+
+template <int KIND> struct Mx6Side {  // K8, K6, K4
+  static constexpr int ROW = KIND == MX6_K8 ? 128 : KIND == MX6_K6 ? 96 : 64;  // bytes in LDS
+  static constexpr int CHUNKS = ROW / 16, LOADS = ROW / 32, OFFS = LOADS;
+  static constexpr int READS = KIND == MX6_K8 ? 2 : KIND == MX6_K6 ? 3 : 1;  // per tile
+};
+template <> struct Mx6Side<MX6_T6> {
+  static constexpr int ROW = 128, LOADS = 16, OFFS = 2, READS = 2;
+};
+
+template <int KIND> __device__ __forceinline__ int mx6_key(int r) {
+  if constexpr (KIND == MX6_K6) return (r >> 3) & 1;
+  else if constexpr (KIND == MX6_K4) return (r >> 2) & 3;
+  else return (r >> 1) & 7;
+}
+
+// where this lane's bytes of each load come from, relative to the tile's first
+// byte of the step; `pitch`: bytes from one row of the operand to the next
+template <int KIND>
+__device__ __forceinline__ void mx6_offsets(unsigned (&off)[Mx6Side<KIND>::OFFS], unsigned pitch,
+                                            int wave, int lane) {
+  typedef Mx6Side<KIND> S;
+  if constexpr (KIND == MX6_T6) {
+    off[0] = (unsigned)(lane >> 5) * pitch + 4 * min(lane & 3, 2);  // row and word
+    off[1] = (lane >> 2) & 7;                                       // unit slot
+  } else {
+#pragma unroll
+    for (int i = 0; i < S::LOADS; i++) {
+      const int c = 64 * (wave * S::LOADS + i) + lane;
+      const int r = c / S::CHUNKS, s = c % S::CHUNKS;
+      off[i] = (unsigned)r * pitch + ((s ^ mx6_key<KIND>(r)) << 4);
+    }
+  }
+}
+
+// one side's direct-to-LDS loads of one wave for one K step into `region`
+template <int KIND>
+__device__ __forceinline__ void mx6_issue(const char* src,
+                                          const unsigned (&off)[Mx6Side<KIND>::OFFS],
+                                          unsigned pitch, GP_LDS_AS char* region, int wave) {
+  typedef Mx6Side<KIND> S;
+  if constexpr (KIND == MX6_T6) {
+    // the eight source units slot ^ key are worked out again every step: held
+    // over the K loop as 64-bit addresses they do not fit the register file
+    unsigned slot = off[1];
+    asm volatile("" : "+v"(slot));
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const int pair = wave * 16 + j;                     // rows 2 pair, 2 pair + 1
+      GP_LDS_AS char* to = region + pair * 256;           // wave-uniform: goes to M0
+      const char* from = src + (size_t)(2 * pair) * pitch + (off[0] + 12 * (slot ^ (j & 7)));
+      __builtin_amdgcn_global_load_lds((GP_GLOBAL_AS const unsigned*)from,
+                                       (GP_LDS_AS unsigned*)to, 4, 0, 0);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < S::LOADS; i++) {
+      GP_LDS_AS char* to = region + (wave * S::LOADS + i) * 1024;
+      __builtin_amdgcn_global_load_lds((GP_GLOBAL_AS const unsigned*)(src + off[i]),
+                                       (GP_LDS_AS unsigned*)to, 16, 0, 0);
+    }
+  }
+}
+
+// LDS byte offsets, inside the side's region, of this lane's fragment reads:
+// K kinds of tile 0 (tile t is 16 rows on, an immediate), T6 of each tile's
+// first read (the second is 16 rows on). w: the wave's row (column) of the 2x2.
+template <int KIND>
+__device__ __forceinline__ void mx6_read_addrs(unsigned (&at)[4], int w, int i16, int g) {
+  const int r = w * 64 + i16;
+  at[0] = at[1] = at[2] = at[3] = 0;
+  if constexpr (KIND == MX6_K8) {
+    at[0] = r * 128 + ((g ^ mx6_key<KIND>(r)) << 4);
+    at[1] = at[0] ^ 64;
+  } else if constexpr (KIND == MX6_K6) {
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      const int u = 3 * g + j;
+      at[j] = r * 96 + (((u >> 1) ^ mx6_key<KIND>(r)) << 4) + ((u & 1) << 3);
+    }
+  } else if constexpr (KIND == MX6_K4) {
+    at[0] = r * 64 + ((g ^ mx6_key<KIND>(r)) << 4);
+  } else {
+    const int k = 32 * g + i16;
+#pragma unroll
+    for (int t = 0; t < 4; t++) at[t] = k * 128 + (((w * 4 + t) ^ mx6_key<KIND>(k)) << 4);
+  }
+}
+
+// one 16-row tile's fragment of a side
+template <int KIND> struct Mx6Frag;
+template <> struct Mx6Frag<MX6_K8> { gp_i4 lo, hi; };
+template <> struct Mx6Frag<MX6_K6> { gp_i2 p[3]; };
+template <> struct Mx6Frag<MX6_K4> { gp_i4 q; };
+template <> struct Mx6Frag<MX6_T6> { gp_i3 lo, hi; };
+
+#define MX6_READ(INSN, DST, AT, OFF) \
+  asm volatile(INSN " %0, %1 offset:%2" : "=v"(DST) : "v"(AT), "n"(OFF) : "memory")
+// tile T of the side whose region starts REGION bytes into the stage; at:
+// mx6_read_addrs plus the stage's LDS address
+template <int KIND, int T, int REGION>
+__device__ __forceinline__ void mx6_read_tile(Mx6Frag<KIND>& f, const unsigned (&at)[4]) {
+  constexpr int O = REGION + T * 16 * Mx6Side<KIND>::ROW;
+  if constexpr (KIND == MX6_K8) {
+    MX6_READ("ds_read_b128", f.lo, at[0], O);
+    MX6_READ("ds_read_b128", f.hi, at[1], O);
+  } else if constexpr (KIND == MX6_K6) {
+    MX6_READ("ds_read_b64", f.p[0], at[0], O);
+    MX6_READ("ds_read_b64", f.p[1], at[1], O);
+    MX6_READ("ds_read_b64", f.p[2], at[2], O);
+  } else if constexpr (KIND == MX6_K4) {
+    MX6_READ("ds_read_b128", f.q, at[0], O);
+  } else {
+    MX6_READ("ds_read_b96_tr_b6", f.lo, at[T], REGION);
+    MX6_READ("ds_read_b96_tr_b6", f.hi, at[T], REGION + 2048);
+  }
+}
+#undef MX6_READ
+template <int KIND, int REGION>
+__device__ __forceinline__ void mx6_read_pair(Mx6Frag<KIND>& f0, Mx6Frag<KIND>& f1,
+                                              const unsigned (&at)[4],
+                                              std::integral_constant<int, 0>) {
+  mx6_read_tile<KIND, 0, REGION>(f0, at);
+  mx6_read_tile<KIND, 1, REGION>(f1, at);
+}
+template <int KIND, int REGION>
+__device__ __forceinline__ void mx6_read_pair(Mx6Frag<KIND>& f2, Mx6Frag<KIND>& f3,
+                                              const unsigned (&at)[4],
+                                              std::integral_constant<int, 1>) {
+  mx6_read_tile<KIND, 2, REGION>(f2, at);
+  mx6_read_tile<KIND, 3, REGION>(f3, at);
+}
+// after an s_waitcnt: the fragment's registers are valid from here on
+template <int KIND> __device__ __forceinline__ void mx6_hold(Mx6Frag<KIND>& f) {
+  if constexpr (KIND == MX6_K8) asm volatile("" : "+v"(f.lo), "+v"(f.hi));
+  else if constexpr (KIND == MX6_K6) asm volatile("" : "+v"(f.p[0]), "+v"(f.p[1]), "+v"(f.p[2]));
+  else if constexpr (KIND == MX6_K4) asm volatile("" : "+v"(f.q));
+  else asm volatile("" : "+v"(f.lo), "+v"(f.hi));
+}
+// the MFMA's operand; the 6- and 4-bit forms read VGPRs 0-5 and 0-3 only
+template <int KIND> __device__ __forceinline__ i32x8 mx6_operand(const Mx6Frag<KIND>& f) {
+  if constexpr (KIND == MX6_K8) {
+    return __builtin_shufflevector(f.lo, f.hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  } else if constexpr (KIND == MX6_K6) {
+    return (i32x8){f.p[0][0], f.p[0][1], f.p[1][0], f.p[1][1], f.p[2][0], f.p[2][1], 0, 0};
+  } else if constexpr (KIND == MX6_K4) {
+    return (i32x8){f.q[0], f.q[1], f.q[2], f.q[3], 0, 0, 0, 0};
+  } else {
+    return (i32x8){f.lo[0], f.lo[1], f.lo[2], f.hi[0], f.hi[1], f.hi[2], 0, 0};
+  }
+}
+
+// the step's vmcnt wait; names the scale registers it makes valid. CNT: the
+// direct loads of step k+1, issued after them, that stay in flight
+template <int CNT>
+__device__ __forceinline__ void mx6_wait_vm(unsigned (&ra)[2][4], unsigned (&rb)[2][4]) {
+  asm volatile("s_waitcnt vmcnt(%8)"
+               : "+v"(ra[0][0]), "+v"(ra[0][1]), "+v"(ra[0][2]), "+v"(ra[0][3]),
+                 "+v"(rb[0][0]), "+v"(rb[0][1]), "+v"(rb[0][2]), "+v"(rb[0][3])
+               : "n"(CNT)
+               : "memory");
+}
+
+// The lane's eight scale loads of one step, the addresses of mxg_load_scales'
+// one K chunk (A, B nk: tile t is `stride` bytes on; B kn: 16 columns on), as
+// one asm statement. mxg_load_scales issues one statement per load; where the
+// compiler reloads a base address from an SGPR it spilled to a VGPR lane
+// (v_readlane) right in front of such a statement, the five wait states a
+// VMEM instruction needs after a VALU write of an SGPR it reads are missing:
+// the hazard recognizer does not look into inline assembly, and the kn
+// instantiation has that register pressure (seen on an MI355X as scale bytes
+// of A tiles 2-3 from a stale address). Here every base is an input of the
+// one statement, so all reloads come before it, and it opens with the wait
+// states.
+template <int BL>
+__device__ __forceinline__ void mx6_load_scales(unsigned (&ra)[2][4], unsigned (&rb)[2][4],
+                                                const unsigned char* sa, const unsigned char* sb,
+                                                unsigned a_off, unsigned b_off, size_t a_stride,
+                                                size_t b_stride) {
+  const unsigned char* sa1 = sa + a_stride;
+  const unsigned char* sa2 = sa1 + a_stride;
+  const unsigned char* sa3 = sa2 + a_stride;
+  if constexpr (BL == GP_NK) {
+    const unsigned char* sb1 = sb + b_stride;
+    const unsigned char* sb2 = sb1 + b_stride;
+    const unsigned char* sb3 = sb2 + b_stride;
+    asm volatile("s_nop 4\n\t"
+                 "global_load_ubyte %0, %8, %10\n\t"
+                 "global_load_ubyte %1, %8, %11\n\t"
+                 "global_load_ubyte %2, %8, %12\n\t"
+                 "global_load_ubyte %3, %8, %13\n\t"
+                 "global_load_ubyte %4, %9, %14\n\t"
+                 "global_load_ubyte %5, %9, %15\n\t"
+                 "global_load_ubyte %6, %9, %16\n\t"
+                 "global_load_ubyte %7, %9, %17"
+                 : "+v"(ra[0][0]), "+v"(ra[0][1]), "+v"(ra[0][2]), "+v"(ra[0][3]),
+                   "+v"(rb[0][0]), "+v"(rb[0][1]), "+v"(rb[0][2]), "+v"(rb[0][3])
+                 : "v"(a_off), "v"(b_off), "s"(sa), "s"(sa1), "s"(sa2), "s"(sa3), "s"(sb),
+                   "s"(sb1), "s"(sb2), "s"(sb3)
+                 : "memory");
+  } else {
+    asm volatile("s_nop 4\n\t"
+                 "global_load_ubyte %0, %8, %10\n\t"
+                 "global_load_ubyte %1, %8, %11\n\t"
+                 "global_load_ubyte %2, %8, %12\n\t"
+                 "global_load_ubyte %3, %8, %13\n\t"
+                 "global_load_ubyte %4, %9, %14\n\t"
+                 "global_load_ubyte %5, %9, %14 offset:16\n\t"
+                 "global_load_ubyte %6, %9, %14 offset:32\n\t"
+                 "global_load_ubyte %7, %9, %14 offset:48"
+                 : "+v"(ra[0][0]), "+v"(ra[0][1]), "+v"(ra[0][2]), "+v"(ra[0][3]),
+                   "+v"(rb[0][0]), "+v"(rb[0][1]), "+v"(rb[0][2]), "+v"(rb[0][3])
+                 : "v"(a_off), "v"(b_off), "s"(sa), "s"(sa1), "s"(sa2), "s"(sa3), "s"(sb)
+                 : "memory");
+  }
+}
+
+// op_sel must be an immediate
+#define MX6_MMA(I, J)                                                                       \
+  acc[I][J] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[I], b[J], acc[I][J], FA, FB, \
+                                                               I, sa, J, sb)
+#define MX6_MMA_ROW(I) MX6_MMA(I, 0); MX6_MMA(I, 1); MX6_MMA(I, 2); MX6_MMA(I, 3)
+
+template <int AW, int BW, int BL, int FA, int FB>
+__global__ void __launch_bounds__(256, 2)
+mx6_gemm_pipe_kernel(const char* __restrict__ A, const char* __restrict__ B,
+                     const unsigned char* __restrict__ scale_a,
+                     const unsigned char* __restrict__ scale_b, const float* __restrict__ expected,
+                     int4* __restrict__ records, float* __restrict__ C, int N, int K, int tiles_n,
+                     int rounds, int store_c, int inject_block, int inject_round) {
+  static_assert((AW == 8 || AW == 6) && (BW == 6 || BW == 4) && (BL == GP_NK || (AW == 6 && BW == 6)),
+                "instantiated: 6x6 nk and kn, 8x6 nk, 8x4 nk");
+  __shared__ __attribute__((aligned(1024))) char mx6_lds[GP_STAGES * GP_STAGE_BYTES];
+  constexpr int AK = AW == 8 ? MX6_K8 : MX6_K6;
+  constexpr int BKIND = BL == GP_KN ? MX6_T6 : BW == 6 ? MX6_K6 : MX6_K4;
+  typedef Mx6Side<AK> SA;
+  typedef Mx6Side<BKIND> SB;
+  constexpr int STEP_BLOCKS = MX6_BK / 32;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int i16 = lane & 15, g = lane >> 4;
+  const int m0 = (blockIdx.x / tiles_n) * GP_TILE, n0 = (blockIdx.x % tiles_n) * GP_TILE;
+  const unsigned place = hw_word();
+  const int steps = K / MX6_BK;
+  // bytes from one row to the next: A [M,K], B nk [N,K], B kn [K,N]
+  const unsigned a_pitch = ((unsigned)K >> 3) * AW;
+  const unsigned b_pitch = ((unsigned)(BL == GP_NK ? K : N) >> 3) * BW;
+  const unsigned kblocks = (unsigned)K >> 5;
+
+  unsigned aoff[SA::OFFS], boff[SB::OFFS];
+  mx6_offsets<AK>(aoff, a_pitch, wave, lane);
+  mx6_offsets<BKIND>(boff, b_pitch, wave, lane);
+  const char* a_tile = A + (size_t)m0 * a_pitch;
+  const char* b_tile = BL == GP_NK ? B + (size_t)n0 * b_pitch : B + (n0 >> 3) * BW;
+  const size_t a_step = MX6_BK / 8 * AW;
+  const size_t b_step = BL == GP_NK ? (size_t)(MX6_BK / 8 * BW) : (size_t)MX6_BK * b_pitch;
+
+  // the lane's scale bytes of a step, as in mx_gemm_pipe_kernel
+  const unsigned sa_off = (unsigned)(wm * 64 + i16) * kblocks + g;
+  const unsigned sb_off = BL == GP_NK ? (unsigned)(wn * 64 + i16) * kblocks + g
+                                      : (unsigned)g * (unsigned)N + wn * 64 + i16;
+  const size_t sa_stride = (size_t)16 * kblocks;
+  const size_t sb_stride = BL == GP_NK ? (size_t)16 * kblocks : (size_t)4 * N;
+  const unsigned char* sa_tile = scale_a + (size_t)m0 * kblocks;
+  const unsigned char* sb_tile = BL == GP_NK ? scale_b + (size_t)n0 * kblocks : scale_b + n0;
+  const size_t sa_step = STEP_BLOCKS;
+  const size_t sb_step = BL == GP_NK ? (size_t)STEP_BLOCKS : (size_t)STEP_BLOCKS * N;
+
+  unsigned a_at[4], b_at[4];
+  mx6_read_addrs<AK>(a_at, wm, i16, g);
+  mx6_read_addrs<BKIND>(b_at, wn, i16, g);
+
+  GP_LDS_AS char* lds = (GP_LDS_AS char*)mx6_lds;
+  const unsigned lds_base = (unsigned)reinterpret_cast<__UINTPTR_TYPE__>(lds);
+  const bool inject_here = (int)blockIdx.x == inject_block && threadIdx.x == 0;
+  int mismatched = 0, first_round = -1;
+  unsigned first_index = 0xFFFFFFFFu, checksum = 0;
+  unsigned raw_a[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, raw_b[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+  f32x4 acc[4][4];
+  for (int round = 0; round < rounds; round++) {
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        // opaque to the optimiser: every round really recomputes its tile
+        asm volatile("" : "+v"(acc[i][j]));
+      }
+    const char* a_src = a_tile;
+    const char* b_src = b_tile;
+    const unsigned char* sa_src = sa_tile;
+    const unsigned char* sb_src = sb_tile;
+    // stage 0 may still be read by a wave that is finishing the last round
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    mx6_issue<AK>(a_src, aoff, a_pitch, lds, wave);
+    mx6_issue<BKIND>(b_src, boff, b_pitch, lds + GP_TILE_BYTES, wave);
+    mx6_load_scales<BL>(raw_a, raw_b, sa_src, sb_src, sa_off, sb_off, sa_stride, sb_stride);
+    // one K step; the last one is peeled, for the reason mx_gemm_pipe_kernel gives
+    auto step = [&](auto more_c, int k) {
+      constexpr bool MORE = decltype(more_c)::value;
+      // barrier 1: the other stage has been read for the last time
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      if constexpr (MORE) {
+        a_src += a_step;
+        b_src += b_step;
+        GP_LDS_AS char* next = lds + ((k + 1) & 1) * GP_STAGE_BYTES;
+        mx6_issue<AK>(a_src, aoff, a_pitch, next, wave);
+        mx6_issue<BKIND>(b_src, boff, b_pitch, next + GP_TILE_BYTES, wave);
+      }
+      // step k's operands and scales are in; step k+1's direct loads stay in flight
+      mx6_wait_vm<MORE ? SA::LOADS + SB::LOADS : 0>(raw_a, raw_b);
+      const int sa = mxg_gather(raw_a[0]), sb = mxg_gather(raw_b[0]);
+      if constexpr (MORE) {
+        // the gathered values exist before their registers are loaded again
+        asm volatile("" : : "v"(sa), "v"(sb));
+        sa_src += sa_step;
+        sb_src += sb_step;
+        mx6_load_scales<BL>(raw_a, raw_b, sa_src, sb_src, sa_off, sb_off, sa_stride, sb_stride);
+      }
+      // barrier 2: every wave's part of step k has landed
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      const unsigned st = lds_base + (k & 1) * GP_STAGE_BYTES;
+      unsigned aa[4], bb[4];
+#pragma unroll
+      for (int t = 0; t < 4; t++) {
+        aa[t] = st + a_at[t];
+        bb[t] = st + b_at[t];
+      }
+      Mx6Frag<AK> fa[4];
+      Mx6Frag<BKIND> fb[4];
+      mx6_read_pair<BKIND, GP_TILE_BYTES>(fb[0], fb[1], bb, std::integral_constant<int, 0>{});
+      mx6_read_pair<BKIND, GP_TILE_BYTES>(fb[2], fb[3], bb, std::integral_constant<int, 1>{});
+      mx6_read_pair<AK, 0>(fa[0], fa[1], aa, std::integral_constant<int, 0>{});
+      mx6_read_pair<AK, 0>(fa[2], fa[3], aa, std::integral_constant<int, 1>{});
+      i32x8 a[4], b[4];
+      // A tiles 2-3 stay in flight
+      asm volatile("s_waitcnt lgkmcnt(%0)" : : "n"(2 * SA::READS) : "memory");
+#pragma unroll
+      for (int t = 0; t < 4; t++) {
+        mx6_hold<BKIND>(fb[t]);
+        b[t] = mx6_operand<BKIND>(fb[t]);
+      }
+      mx6_hold<AK>(fa[0]);
+      mx6_hold<AK>(fa[1]);
+      a[0] = mx6_operand<AK>(fa[0]);
+      a[1] = mx6_operand<AK>(fa[1]);
+      MX6_MMA_ROW(0);
+      MX6_MMA_ROW(1);
+      __builtin_amdgcn_sched_barrier(0);  // these MFMAs stay above the wait
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      mx6_hold<AK>(fa[2]);
+      mx6_hold<AK>(fa[3]);
+      a[2] = mx6_operand<AK>(fa[2]);
+      a[3] = mx6_operand<AK>(fa[3]);
+      MX6_MMA_ROW(2);
+      MX6_MMA_ROW(3);
+    };
+    for (int k = 0; k + 1 < steps; k++) step(std::true_type{}, k);
+    step(std::false_type{}, steps - 1);
+    if (inject_here && round == inject_round)
+      acc[0][0][0] = __uint_as_float(__float_as_uint(acc[0][0][0]) ^ 1u);
+    // the compare, as in mx_gemm_pipe_kernel: expected is read again every
+    // round and the lane's place in it worked out again
+    int again = 0, lane_v = lane;
+    asm volatile("" : "+s"(again), "+v"(lane_v));
+    const int i16v = lane_v & 15, gv = lane_v >> 4;
+    const float* want_lane = expected + (wm * 64 + gv * 4) * GP_TILE + wn * 64 + i16v;
+    const float* want = want_lane + again;
+    unsigned bad = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const unsigned bits = __float_as_uint(acc[i][j][r]);
+          bad += bits != __float_as_uint(want[(i * 16 + r) * GP_TILE + j * 16]);
+          checksum ^= bits;
+        }
+      asm volatile("" ::: "memory");  // 16 expected values in registers at a time, not 64
+    }
+    bad = wave_add(bad);
+    if (bad) {  // wave-uniform, and rare
+      if (first_round < 0) {
+        first_round = round;
+        asm volatile("" : "+s"(again));  // a second read, not the first one's compare masks
+        want = want_lane + again;
+        unsigned index = 0xFFFFFFFFu;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+          for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+              if (__float_as_uint(acc[i][j][r]) !=
+                  __float_as_uint(want[(i * 16 + r) * GP_TILE + j * 16]))
+                index = min(index, (unsigned)((i * 16 + gv * 4 + r) * 64 + j * 16 + i16v));
+        first_index = wave_min(index);
+      }
+      mismatched += (int)bad;
+    }
+  }
+  if (store_c) {
+    int lane_v = lane;
+    asm volatile("" : "+v"(lane_v));  // as above
+    const int i16v = lane_v & 15, gv = lane_v >> 4;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+          C[(size_t)(m0 + wm * 64 + i * 16 + gv * 4 + r) * N + n0 + wn * 64 + j * 16 + i16v] =
+              acc[i][j][r];
+  }
+  checksum = wave_xor(checksum);
+  if (lane == 0)
+    store_record8(records, blockIdx.x * 4 + wave, (int)place, mismatched, first_round,
+                  (int)first_index, (int)checksum, 0, 0, 0);
+}
+#undef MX6_MMA_ROW
+#undef MX6_MMA
+
+// the instantiated cases: operand formats by name, bits per code, the
+// instruction's format code
+struct Mx6Format { const char* name; int bits, code; };
+static const Mx6Format MX6_FORMATS[4] = {
+    {"mxfp8", 8, 0}, {"mxfp6", 6, 2}, {"mxbf6", 6, 3}, {"mxfp4", 4, 4}};
+constexpr int MX6_CASES = 6;
+// (a format, b format, b layout) as indices into MX6_FORMATS and GP_KN / GP_NK
+static const int MX6_CASE[MX6_CASES][3] = {{1, 1, GP_NK}, {1, 1, GP_KN}, {2, 2, GP_NK},
+                                           {2, 2, GP_KN}, {0, 1, GP_NK}, {0, 3, GP_NK}};
+
+// a_fmt / b_fmt "mxfp8" (e4m3, one code per byte), "mxfp6" (e2m3) and "mxbf6"
+// (e3m2: four codes in three bytes, a little-endian bit stream), "mxfp4" (e2m1,
+// the even element in the low nibble); the pairs and layouts of MX6_CASE. A
+// [M, K bits/8]; B [N, K bits/8] ("nk") or [K, N 3/4] ("kn", 6-bit); scale_a
+// [M,K/32]; scale_b [N,K/32] or [K/32,N]; all uint8, row-major. expected
+// [128,128] fp32. One untimed warm-up launch, then one timed launch. Returns
+// (records [grid*4,8] int32, C [M,N] fp32 when store_c else empty, elapsed_ms).
+std::tuple<torch::Tensor, torch::Tensor, double> mx6_gemm_pipe(
+    torch::Tensor A, torch::Tensor B, torch::Tensor scale_a, torch::Tensor scale_b,
+    torch::Tensor expected, const std::string& a_fmt, const std::string& b_fmt,
+    const std::string& b_layout, long rounds, bool store_c, long inject_block,
+    long inject_round) {
+  int fa = -1, fb = -1;
+  for (int f = 0; f < 4; f++) {
+    if (a_fmt == MX6_FORMATS[f].name) fa = f;
+    if (b_fmt == MX6_FORMATS[f].name) fb = f;
+  }
+  TORCH_CHECK(fa >= 0 && fb >= 0, "a_fmt and b_fmt must be among mxfp8, mxfp6, mxbf6, mxfp4; got ",
+              a_fmt, ", ", b_fmt);
+  const int bl = b_layout == "kn" ? GP_KN : b_layout == "nk" ? GP_NK : -1;
+  TORCH_CHECK(bl >= 0, "b_layout must be one of kn, nk; got ", b_layout);
+  int which = -1;
+  for (int c = 0; c < MX6_CASES; c++)
+    if (MX6_CASE[c][0] == fa && MX6_CASE[c][1] == fb && MX6_CASE[c][2] == bl) which = c;
+  TORCH_CHECK(which >= 0, "unsupported case ", a_fmt, " x ", b_fmt, " ", b_layout,
+              ": mxfp6 and mxbf6 with themselves (nk, kn), mxfp8 x mxfp6 and mxfp8 x mxfp4 (nk)");
+  for (const torch::Tensor* t : {&A, &B, &scale_a, &scale_b, &expected}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == A.device(),
+                "A, B, the scales and expected must be on one GPU");
+    TORCH_CHECK(t->dim() == 2, "A, B, the scales and expected must be 2-D");
+  }
+  TORCH_CHECK(A.dtype() == torch::kUInt8 && B.dtype() == torch::kUInt8 &&
+                  scale_a.dtype() == torch::kUInt8 && scale_b.dtype() == torch::kUInt8,
+              "A, B and the scales must be uint8");
+  TORCH_CHECK(expected.dtype() == torch::kFloat32 &&
+                  expected.sizes() == torch::IntArrayRef({GP_TILE, GP_TILE}),
+              "expected must be float32 [128,128]");
+  const long abits = MX6_FORMATS[fa].bits, bbits = MX6_FORMATS[fb].bits;
+  const long M = A.size(0), K = A.size(1) * 8 / abits;
+  TORCH_CHECK(K * abits == A.size(1) * 8, "A's ", A.size(1), " bytes per row hold no whole number of ",
+              abits, "-bit codes");
+  const long N = bl == GP_NK ? B.size(0) : B.size(1) * 8 / bbits;
+  TORCH_CHECK(M >= GP_TILE && N >= GP_TILE && M % GP_TILE == 0 && N % GP_TILE == 0,
+              "M and N must be positive multiples of 128; got ", M, ", ", N);
+  TORCH_CHECK(K >= MX6_BK && K % MX6_BK == 0, "K must be a positive multiple of 128; got ", K);
+  // the kernel's per-lane offsets into a tile's rows are 32-bit
+  TORCH_CHECK(M <= (1L << 22) && N <= (1L << 22) && K <= (1L << 22),
+              "M, N and K must be <= 2^22");
+  if (bl == GP_NK) {
+    TORCH_CHECK(B.size(1) * 8 == K * bbits, "B must be [N,K] in ", K * bbits / 8, " bytes per row");
+    TORCH_CHECK(scale_b.sizes() == torch::IntArrayRef({N, K / 32}), "scale_b must be [", N, ",",
+                K / 32, "]");
+  } else {
+    TORCH_CHECK(B.size(0) == K && B.size(1) * 8 == N * bbits, "B must be [K,N] with K=", K,
+                " in ", N * bbits / 8, " bytes per row");
+    TORCH_CHECK(scale_b.sizes() == torch::IntArrayRef({K / 32, N}), "scale_b must be [", K / 32,
+                ",", N, "]");
+  }
+  TORCH_CHECK(scale_a.sizes() == torch::IntArrayRef({M, K / 32}), "scale_a must be [", M, ",",
+              K / 32, "]");
+  const long tiles_n = N / GP_TILE, grid = (M / GP_TILE) * tiles_n;
+  TORCH_CHECK(rounds >= 1, "rounds must be >= 1");
+  // bounded run, as for gemm_pipe
+  TORCH_CHECK(grid <= (1L << 20) && rounds <= (1L << 22) && rounds * K * grid <= (1L << 33),
+              "rounds*K*grid must be <= 2^33; got ", rounds, "*", K, "*", grid);
+  TORCH_CHECK(inject_block >= -1 && inject_block < grid && inject_round >= -1 &&
+                  inject_round < rounds,
+              "inject_block/inject_round out of range");
+  A = A.contiguous();
+  B = B.contiguous();
+  scale_a = scale_a.contiguous();
+  scale_b = scale_b.contiguous();
+  expected = expected.contiguous();
+  // a direct-to-LDS load fetches 16 aligned bytes (B kn: 4); every row pitch
+  // is a multiple of 48
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(A.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(B.data_ptr()) % 16 == 0,
+              "A and B must be 16-byte aligned");
+  auto records = zero_records(grid * 4, 8, A.device());
+  auto C = store_c ? torch::zeros({M, N}, expected.options())
+                   : torch::empty({0}, expected.options());
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream,
+                       static_cast<const char*>(A.data_ptr()),
+                       static_cast<const char*>(B.data_ptr()), scale_a.data_ptr<unsigned char>(),
+                       scale_b.data_ptr<unsigned char>(), expected.data_ptr<float>(),
+                       reinterpret_cast<int4*>(records.data_ptr<int>()),
+                       store_c ? C.data_ptr<float>() : nullptr, (int)N, (int)K, (int)tiles_n,
+                       (int)rounds, (int)store_c, (int)inject_block, (int)inject_round);
+  };
+  const double ms = warm_then_timed_ms(stream, [&]() {
+    switch (which) {  // the order of MX6_CASE
+      case 0: launch(mx6_gemm_pipe_kernel<6, 6, GP_NK, 2, 2>); break;
+      case 1: launch(mx6_gemm_pipe_kernel<6, 6, GP_KN, 2, 2>); break;
+      case 2: launch(mx6_gemm_pipe_kernel<6, 6, GP_NK, 3, 3>); break;
+      case 3: launch(mx6_gemm_pipe_kernel<6, 6, GP_KN, 3, 3>); break;
+      case 4: launch(mx6_gemm_pipe_kernel<8, 6, GP_NK, 0, 2>); break;
+      default: launch(mx6_gemm_pipe_kernel<8, 4, GP_NK, 0, 4>); break;
+    }
+  });
+  return std::make_tuple(records, C, ms);
+}
+
 py::dict device_info(int dev) {
   hipDeviceProp_t prop;
   HIP_CHECK(hipGetDeviceProperties(&prop, dev));
@@ -7305,6 +7949,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "LDS fragment reads (8- and 4-bit transpose reads for kn), per-block E8M0 scales streamed "
         "from memory and the scaled 16x16x128 MFMA, every 128x128 tile compared bitwise with "
         "expected each round; returns (per-wave records [grid*4,8], C or empty, ms)");
+  m.def("mx6_gemm_pipe", &mx6_gemm_pipe, py::arg("A"), py::arg("B"), py::arg("scale_a"),
+        py::arg("scale_b"), py::arg("expected"), py::arg("a_fmt"), py::arg("b_fmt"),
+        py::arg("b_layout"), py::arg("rounds") = 1, py::arg("store_c") = false,
+        py::arg("inject_block") = -1, py::arg("inject_round") = -1,
+        "Block-scaled tiled GEMM pipeline for 6-bit and mixed-width operands (mxfp6 / mxbf6 with "
+        "themselves, nk and kn; mxfp8 x mxfp6 and mxfp8 x mxfp4, nk): 96- and 64-byte rows through "
+        "direct-to-LDS loads, ds_read_b64 / ds_read_b96_tr_b6 fragments, streamed E8M0 scales and "
+        "the scaled 16x16x128 MFMA, every 128x128 tile compared bitwise with expected each round; "
+        "returns (per-wave records [grid*4,8], C or empty, ms)");
   m.def("cu_coverage", &cu_coverage, py::arg("blocks") = 4096,
         "Per-wave (XCC_ID<<16 | HW_ID) placement words for CU-coverage checks");
   m.def("device_info", &device_info, py::arg("dev") = 0);
