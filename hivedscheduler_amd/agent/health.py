@@ -335,34 +335,18 @@ def collect_node_health(
                     )
                     if not p["ok"] or p["bad_simds"]:
                         gpu["healthy"] = False
-                if gemm_probe:
-                    p = rep["gemm_probe"]
-                    gpu.update(
-                        gemm_probe_ok=bool(p["ok"]),
-                        gemm_tflops={name: round(s["tflops"], 1)
-                                     for name, s in p["cases"].items()},
-                        gemm_bad_cus=p["bad_cus"],
-                    )
-                    if not p["ok"] or p["bad_cus"]:
-                        gpu["healthy"] = False
-                if mx_gemm_probe:
-                    p = rep["mx_gemm_probe"]
-                    gpu.update(
-                        mx_gemm_probe_ok=bool(p["ok"]),
-                        mx_gemm_tflops={name: round(s["tflops"], 1)
-                                        for name, s in p["cases"].items()},
-                        mx_gemm_bad_cus=p["bad_cus"],
-                    )
-                    if not p["ok"] or p["bad_cus"]:
-                        gpu["healthy"] = False
-                if mx6_gemm_probe:
-                    p = rep["mx6_gemm_probe"]
-                    gpu.update(
-                        mx6_gemm_probe_ok=bool(p["ok"]),
-                        mx6_gemm_tflops={name: round(s["tflops"], 1)
-                                         for name, s in p["cases"].items()},
-                        mx6_gemm_bad_cus=p["bad_cus"],
-                    )
+                # the three tiled GEMM probes report the same fields
+                for name, on in (("gemm", gemm_probe), ("mx_gemm", mx_gemm_probe),
+                                 ("mx6_gemm", mx6_gemm_probe)):
+                    if not on:
+                        continue
+                    p = rep[f"{name}_probe"]
+                    gpu.update({
+                        f"{name}_probe_ok": bool(p["ok"]),
+                        f"{name}_tflops": {case: round(s["tflops"], 1)
+                                           for case, s in p["cases"].items()},
+                        f"{name}_bad_cus": p["bad_cus"],
+                    })
                     if not p["ok"] or p["bad_cus"]:
                         gpu["healthy"] = False
             except Exception as e:

@@ -16,8 +16,11 @@ GEMM_TILE = 128
 LDS_TR_WIDTHS = (16, 8, 4, 6)
 _ELEM_BYTES = {"bf16": 2, "fp8": 1}
 _STEP_BYTES = 128  # bytes of K per row and K step
-# default shape and rounds (BENCHMARKS.md "GEMM probe"): 1024 workgroups, four
-# per CU of an MI355X; an odd number of rounds keeps the xor checksum non-zero
+# default shape and rounds of the three tiled GEMM probes (BENCHMARKS.md "GEMM
+# probe", "MX GEMM probe", "MX6 GEMM probe"): 1024 workgroups, four per CU of
+# an MI355X; 99 rounds put every MX6 case's timed launch at 27 to 31 ms, inside
+# what the GEMM probe's cases take; an odd number keeps the xor checksum
+# non-zero
 _DEFAULT_MNK = (4096, 4096, 8192)
 _DEFAULT_ROUNDS = 99
 
@@ -166,23 +169,18 @@ def gemm_probe_wave_checksums(expected, rounds: int):
     return out
 
 
-def summarize_gemm_probe(records, ms: float, fmt: str, b_layout: str, M: int, N: int, K: int,
-                         rounds: int, expected_cus: int) -> dict:
-    """Turn the per-wave records of one ops.gemm_pipe launch into a verdict.
-
-    records: [grid*4, 8] int32 rows {hw word, mismatched elements, first bad
-    round (-1), first bad element of the wave's 64x64 block (-1), xor checksum,
-    0, 0, 0}. `operand_gbps` is the bytes the workgroups load into LDS over the
-    time, not HBM bandwidth: L2 and the Infinity Cache serve the reuse. The
-    rates are reported, never judged. Pure numpy; needs no GPU.
-    """
+def _summarize_tiled_gemm(records, ms: float, M: int, N: int, K: int, rounds: int,
+                          expected_cus: int, steps: int, step_bytes: int) -> dict:
+    """The verdict of one launch of a tiled GEMM probe (gemm_pipe, mx_gemm_pipe,
+    mx6_gemm_pipe: the same records). `steps` K steps per round, in each of which
+    a workgroup loads `step_bytes`."""
     import numpy as np
 
     rec = np.asarray(records).reshape(-1, 4, 8).astype(np.int64)
     grid = int(rec.shape[0])
     sec = ms * 1e-3
     flop = 2.0 * M * N * K * rounds
-    loaded = float(grid) * (K // gemm_probe_bk(fmt)) * 2 * GEMM_TILE * _STEP_BYTES * rounds
+    loaded = float(grid) * steps * step_bytes * rounds
     bad = BadUnits()
     flat = rec.reshape(-1, 8)
     for word, mism, first, index in flat[flat[:, 1] != 0][:, :4]:
@@ -203,6 +201,20 @@ def summarize_gemm_probe(records, ms: float, fmt: str, b_layout: str, M: int, N:
         "checksum_spread": checksum_spread,
         "ok": bool(mismatched_waves == 0 and not checksum_spread and cus_seen >= expected_cus),
     }
+
+
+def summarize_gemm_probe(records, ms: float, fmt: str, b_layout: str, M: int, N: int, K: int,
+                         rounds: int, expected_cus: int) -> dict:
+    """Turn the per-wave records of one ops.gemm_pipe launch into a verdict.
+
+    records: [grid*4, 8] int32 rows {hw word, mismatched elements, first bad
+    round (-1), first bad element of the wave's 64x64 block (-1), xor checksum,
+    0, 0, 0}. `operand_gbps` is the bytes the workgroups load into LDS over the
+    time, not HBM bandwidth: L2 and the Infinity Cache serve the reuse. The
+    rates are reported, never judged. Pure numpy; needs no GPU.
+    """
+    return _summarize_tiled_gemm(records, ms, M, N, K, rounds, expected_cus,
+                                 K // gemm_probe_bk(fmt), 2 * GEMM_TILE * _STEP_BYTES)
 
 
 def lds_tr_map_report(device: int = 0) -> dict:
@@ -231,16 +243,12 @@ def lds_tr_map_report(device: int = 0) -> dict:
     return out
 
 
-def gemm_probe_report(device: int = 0, cases=GEMM_PROBE_CASES, M: int = None, N: int = None,
-                      K: int = None, rounds: int = None, inject=None) -> dict:
-    """Run the GEMM probe's cases and the transpose-read map on one GPU.
-
-    Returns {"cases": {"<fmt>_<layout>": summarize_gemm_probe(...)}, "tr_map":
-    {width: bool}, "ok", "bad_cus"} where `ok` is the AND and `bad_cus` the
-    union ((xcc, se, sh, cu) dicts, sorted). `inject=(block, round)` flips one
-    accumulator bit in wave 0 of that workgroup in that round (register
-    arithmetic only) to exercise detection on healthy hardware.
-    """
+def _tiled_gemm_report(device: int, cases, M, N, K, rounds, inject, op: str, operands,
+                       summarize, case_name) -> dict:
+    """What the three tiled GEMM probes' report functions share: every case's
+    `operands(*case, M, N, K)` through ops.<op>, its records through
+    `summarize`, under `case_name(*case)`; `ok` the AND and `bad_cus` the union
+    over the cases."""
     from . import _ops_on
 
     ops = _ops_on(device)
@@ -252,15 +260,32 @@ def gemm_probe_report(device: int = 0, cases=GEMM_PROBE_CASES, M: int = None, N:
     expected_cus = ops.device_info(device)["multiProcessorCount"]
     out: dict = {"M": M, "N": N, "K": K, "rounds": rounds, "cases": {}}
     bad = set()
-    for fmt, b_layout in cases:
-        A, B, expected = gemm_probe_operands(fmt, b_layout, M, N, K)
-        records, _, ms = ops.gemm_pipe(A.cuda(device), B.cuda(device), expected.cuda(device),
-                                       fmt, b_layout, rounds, False, inject_block, inject_round)
-        s = summarize_gemm_probe(records.cpu().numpy(), ms, fmt, b_layout, M, N, K, rounds,
-                                 expected_cus)
-        out["cases"][f"{fmt}_{b_layout}"] = s
+    for case in cases:
+        tensors = operands(*case, M, N, K)
+        records, _, ms = getattr(ops, op)(*(t.cuda(device) for t in tensors), *case, rounds,
+                                          False, inject_block, inject_round)
+        s = summarize(records.cpu().numpy(), ms, *case, M, N, K, rounds, expected_cus)
+        out["cases"][case_name(*case)] = s
         bad |= place_keys(s["bad_cus"], 4)
-    out["tr_map"] = lds_tr_map_report(device)
-    out["ok"] = bool(all(s["ok"] for s in out["cases"].values()) and all(out["tr_map"].values()))
+    out["ok"] = bool(all(s["ok"] for s in out["cases"].values()))
     out["bad_cus"] = place_dicts(bad)
+    return out
+
+
+def gemm_probe_report(device: int = 0, cases=GEMM_PROBE_CASES, M: int = None, N: int = None,
+                      K: int = None, rounds: int = None, inject=None) -> dict:
+    """Run the GEMM probe's cases and the transpose-read map on one GPU.
+
+    Returns {"cases": {"<fmt>_<layout>": summarize_gemm_probe(...)}, "tr_map":
+    {width: bool}, "ok", "bad_cus"} where `ok` is the AND and `bad_cus` the
+    union ((xcc, se, sh, cu) dicts, sorted). `inject=(block, round)` flips one
+    accumulator bit in wave 0 of that workgroup in that round (register
+    arithmetic only) to exercise detection on healthy hardware.
+    """
+    out = _tiled_gemm_report(device, cases, M, N, K, rounds, inject, "gemm_pipe",
+                             gemm_probe_operands, summarize_gemm_probe, "{}_{}".format)
+    ok, bad_cus = out.pop("ok"), out.pop("bad_cus")  # they follow tr_map, as ever
+    out["tr_map"] = lds_tr_map_report(device)
+    out["ok"] = bool(ok and all(out["tr_map"].values()))
+    out["bad_cus"] = bad_cus
     return out

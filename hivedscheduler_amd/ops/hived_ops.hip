@@ -6023,8 +6023,10 @@ std::tuple<torch::Tensor, double> cvt_burn(const std::string& section, torch::Te
 // MFMAs (low and high 8 bytes); the transposed B reads follow that k order.
 // Any consistent K order gives the same bits, the sums being exact.
 //
-// Verification in registers: per round the accumulators are zeroed (opaque to
-// the optimiser), the K loop runs, every element is compared bitwise with
+// Verification in registers, the same code in this kernel, mx_gemm_pipe_kernel
+// and mx6_gemm_pipe_kernel (GP_ZERO_ACC, gp_inject, gp_compare_round,
+// gp_store_c, gp_store_record): per round the accumulators are zeroed (opaque
+// to the optimiser), the K loop runs, every element is compared bitwise with
 // expected[128,128] and xor-ed into a checksum. Lane 0 of each wave writes
 // (store_record8): [0] placement word, [1] mismatched elements, [2] first bad
 // round (-1), [3] index of the first bad element of that round in the wave's
@@ -6032,6 +6034,8 @@ std::tuple<torch::Tensor, double> cvt_burn(const std::string& section, torch::Te
 // store_c: the last round's tile also goes to C[M,N]. inject_block /
 // inject_round: lane 0 of wave 0 of that workgroup flips the low mantissa bit
 // of its first accumulator element before the compare: register arithmetic only.
+// The addresses of the compare and of the store are worked out after the K
+// loop from a lane index made opaque there, so that none is held over it.
 //
 // Checked in the gfx950 disassembly: per K step and wave eight
 // global_load_lds_dwordx4, then s_waitcnt vmcnt(8) and no other vmcnt wait
@@ -6200,6 +6204,130 @@ __device__ __forceinline__ void gp_mma_half(const GpFrags<BL>& f, f32x4 (&acc)[4
     }
 }
 
+// LDS byte offsets of this lane's fragment reads inside a stage (the B tile's
+// 16 KiB are in the instruction's offset), where gemm_pipe_kernel and
+// mx_gemm_pipe_kernel read alike: A and B nk through ds_read_b128, B kn fp8
+// through tr_b8 (a kn B of another width fills b_at itself). The keys do not
+// depend on the tile (A, B nk) or on the half and the read (B kn), so the
+// other reads are a constant number of bytes on; half 1 (chunk g + 4) of A
+// and B nk is chunk q ^ 4.
+template <int BL>
+__device__ __forceinline__ void gp_frag_addrs(unsigned (&a_at)[2], unsigned (&b_at)[4], int wm,
+                                              int wn, int i16, int g) {
+  const int ra = wm * 64 + i16;
+  a_at[0] = ra * 128 + ((g ^ gp_key_b128(ra)) << 4);
+  a_at[1] = a_at[0] ^ 64;
+  if constexpr (BL == GP_NK) {
+    const int rb = wn * 64 + i16;
+    b_at[0] = rb * 128 + ((g ^ gp_key_b128(rb)) << 4);
+    b_at[1] = b_at[0] ^ 64;
+    b_at[2] = b_at[3] = 0;
+  } else {
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+      const int nb = wn * 64 + t * 16;
+      const int k = g * 16 + (i16 >> 1);
+      b_at[t] = k * 128 + (((nb >> 4) ^ gp_key_tr8(k)) << 4) + (i16 & 1) * 8;
+    }
+  }
+}
+
+// --- around the K loop: what gemm_pipe_kernel, mx_gemm_pipe_kernel and
+// mx6_gemm_pipe_kernel do with the wave's 4x4 accumulator tiles (see
+// "Verification in registers" above) ---
+struct GpVerdict {  // fields [1..4] of the wave's record
+  int mismatched = 0, first_round = -1;
+  unsigned first_index = 0xFFFFFFFFu, checksum = 0;
+};
+
+// Zeroes the accumulators, opaque to the optimiser: every round really
+// recomputes its tile. A macro: the same statements inlined from a function
+// cost mx6_gemm_pipe_kernel<8, 4, nk> one VGPR more (184), outside the K loop.
+#define GP_ZERO_ACC(ACC)                                \
+  _Pragma("unroll") for (int i = 0; i < 4; i++) {       \
+    _Pragma("unroll") for (int j = 0; j < 4; j++) {     \
+      ACC[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};          \
+      asm volatile("" : "+v"(ACC[i][j]));               \
+    }                                                   \
+  }
+
+// the injected fault: the low mantissa bit of the lane's first element
+__device__ __forceinline__ void gp_inject(f32x4 (&acc)[4][4]) {
+  acc[0][0][0] = __uint_as_float(__float_as_uint(acc[0][0][0]) ^ 1u);
+}
+
+// One round's compare. expected is read again every round (kept in registers
+// it would cost 64 of them), and the lane's place in it is worked out again:
+// both are opaque to the optimiser, which would otherwise keep the addresses
+// of the compare in registers over the K loop.
+__device__ __forceinline__ void gp_compare_round(const f32x4 (&acc)[4][4],
+                                                 const float* expected, int wm,
+                                                 int wn, int lane, int round, GpVerdict& v) {
+  int again = 0;
+  asm volatile("" : "+s"(again), "+v"(lane));
+  const int i16 = lane & 15, g = lane >> 4;
+  // expected element of accumulator (i, j, r): want_lane[(16 i + r) * 128 + 16 j]
+  const float* want_lane = expected + (wm * 64 + g * 4) * GP_TILE + wn * 64 + i16;
+  const float* want = want_lane + again;
+  unsigned bad = 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const unsigned bits = __float_as_uint(acc[i][j][r]);
+        bad += bits != __float_as_uint(want[(i * 16 + r) * GP_TILE + j * 16]);
+        v.checksum ^= bits;
+      }
+    asm volatile("" ::: "memory");  // 16 expected values in registers at a time, not 64
+  }
+  bad = wave_add(bad);
+  if (bad) {  // wave-uniform, and rare
+    if (v.first_round < 0) {
+      v.first_round = round;
+      asm volatile("" : "+s"(again));  // a second read, not the first one's compare masks
+      want = want_lane + again;
+      unsigned index = 0xFFFFFFFFu;
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+#pragma unroll
+          for (int r = 0; r < 4; r++)
+            if (__float_as_uint(acc[i][j][r]) !=
+                __float_as_uint(want[(i * 16 + r) * GP_TILE + j * 16]))
+              index = min(index, (unsigned)((i * 16 + g * 4 + r) * 64 + j * 16 + i16));
+      v.first_index = wave_min(index);
+    }
+    v.mismatched += (int)bad;
+  }
+}
+
+// the last round's tile to C[M,N]; m0, n0: the workgroup's first element. The
+// lane is opaque for the reason gp_compare_round gives.
+__device__ __forceinline__ void gp_store_c(const f32x4 (&acc)[4][4], float* C, int N,
+                                           int m0, int n0, int wm, int wn, int lane) {
+  asm volatile("" : "+v"(lane));
+  const int i16 = lane & 15, g = lane >> 4;
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+      for (int r = 0; r < 4; r++)
+        C[(size_t)(m0 + wm * 64 + i * 16 + g * 4 + r) * N + n0 + wn * 64 + j * 16 + i16] =
+            acc[i][j][r];
+}
+
+__device__ __forceinline__ void gp_store_record(int4* records, int wave, int lane,
+                                                unsigned place, const GpVerdict& v) {
+  const unsigned checksum = wave_xor(v.checksum);
+  if (lane == 0)
+    store_record8(records, blockIdx.x * 4 + wave, (int)place, v.mismatched, v.first_round,
+                  (int)v.first_index, (int)checksum, 0, 0, 0);
+}
+
 template <int FMT, int BL>
 __global__ void __launch_bounds__(256, 2)
 gemm_pipe_kernel(const char* __restrict__ A, const char* __restrict__ B,
@@ -6239,53 +6367,27 @@ gemm_pipe_kernel(const char* __restrict__ A, const char* __restrict__ B,
   const size_t a_step = GP_STEP_BYTES;
   const size_t b_step = BL == GP_NK ? (size_t)GP_STEP_BYTES : (size_t)BK * N * ES;
 
-  // LDS byte offsets of this lane's fragment reads inside a stage (the B tile's
-  // 16 KiB are in the instruction's offset). The keys do not depend on the
-  // tile (A, B nk) or on the half and the read (B kn), so the other reads are
-  // a constant number of bytes on; half 1 of A and B nk is chunk q ^ 4.
+  // LDS byte offsets of this lane's fragment reads inside a stage; bf16 kn:
+  // tile t's first tr_b16 read
   unsigned a_at[2], b_at[4];
-  {
-    const int ra = wm * 64 + i16;
-    a_at[0] = ra * 128 + ((g ^ gp_key_b128(ra)) << 4);
-    a_at[1] = a_at[0] ^ 64;
-  }
-  if constexpr (BL == GP_NK) {
-    const int rb = wn * 64 + i16;
-    b_at[0] = rb * 128 + ((g ^ gp_key_b128(rb)) << 4);
-    b_at[1] = b_at[0] ^ 64;
-    b_at[2] = b_at[3] = 0;
-  } else {
+  gp_frag_addrs<BL>(a_at, b_at, wm, wn, i16, g);
+  if constexpr (BL == GP_KN && FMT == GP_BF16) {
 #pragma unroll
     for (int t = 0; t < 4; t++) {
       const int nb = wn * 64 + t * 16;
-      if constexpr (FMT == GP_FP8) {
-        const int k = g * 16 + (i16 >> 1);
-        b_at[t] = k * 128 + (((nb >> 4) ^ gp_key_tr8(k)) << 4) + (i16 & 1) * 8;
-      } else {
-        const int k = g * 8 + (i16 >> 2);
-        const int chunk = (nb >> 3) + ((i16 & 3) >> 1);
-        b_at[t] = k * 256 + ((chunk ^ (gp_key_tr16(k) << 1)) << 4) + (i16 & 1) * 8;
-      }
+      const int k = g * 8 + (i16 >> 2);
+      const int chunk = (nb >> 3) + ((i16 & 3) >> 1);
+      b_at[t] = k * 256 + ((chunk ^ (gp_key_tr16(k) << 1)) << 4) + (i16 & 1) * 8;
     }
   }
 
   GP_LDS_AS char* lds = (GP_LDS_AS char*)gp_lds;
   const unsigned lds_base = (unsigned)reinterpret_cast<__UINTPTR_TYPE__>(lds);
-  // expected element of accumulator (i, j, r): want_lane[(16 i + r) * 128 + 16 j]
-  const float* want_lane = expected + (wm * 64 + g * 4) * GP_TILE + wn * 64 + i16;
   const bool inject_here = (int)blockIdx.x == inject_block && threadIdx.x == 0;
-  int mismatched = 0, first_round = -1;
-  unsigned first_index = 0xFFFFFFFFu, checksum = 0;
+  GpVerdict verdict;
   f32x4 acc[4][4];
   for (int round = 0; round < rounds; round++) {
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        // opaque to the optimiser: every round really recomputes its tile
-        asm volatile("" : "+v"(acc[i][j]));
-      }
+    GP_ZERO_ACC(acc)
     const char* a_src = a_tile;
     const char* b_src = b_tile;
     // stage 0 may still be read by a wave that is finishing the last round
@@ -6324,61 +6426,11 @@ gemm_pipe_kernel(const char* __restrict__ A, const char* __restrict__ B,
       gp_wait_half<BL, false>(f1);
       gp_mma_half<FMT, BL>(f1, acc);
     }
-    if (inject_here && round == inject_round)
-      acc[0][0][0] = __uint_as_float(__float_as_uint(acc[0][0][0]) ^ 1u);
-    // expected is read again every round (kept in registers it would cost 64
-    // of them): the offset is opaque to the optimiser
-    int again = 0;
-    asm volatile("" : "+s"(again));
-    const float* want = want_lane + again;
-    unsigned bad = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const unsigned bits = __float_as_uint(acc[i][j][r]);
-          bad += bits != __float_as_uint(want[(i * 16 + r) * GP_TILE + j * 16]);
-          checksum ^= bits;
-        }
-      asm volatile("" ::: "memory");  // 16 expected values in registers at a time, not 64
-    }
-    bad = wave_add(bad);
-    if (bad) {  // wave-uniform, and rare
-      if (first_round < 0) {
-        first_round = round;
-        asm volatile("" : "+s"(again));  // a second read, not the first one's compare masks
-        want = want_lane + again;
-        unsigned index = 0xFFFFFFFFu;
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-          for (int j = 0; j < 4; j++)
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-              if (__float_as_uint(acc[i][j][r]) !=
-                  __float_as_uint(want[(i * 16 + r) * GP_TILE + j * 16]))
-                index = min(index, (unsigned)((i * 16 + g * 4 + r) * 64 + j * 16 + i16));
-        first_index = wave_min(index);
-      }
-      mismatched += (int)bad;
-    }
+    if (inject_here && round == inject_round) gp_inject(acc);
+    gp_compare_round(acc, expected, wm, wn, lane, round, verdict);
   }
-  if (store_c) {
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-          C[(size_t)(m0 + wm * 64 + i * 16 + g * 4 + r) * N + n0 + wn * 64 + j * 16 + i16] =
-              acc[i][j][r];
-  }
-  checksum = wave_xor(checksum);
-  if (lane == 0)
-    store_record8(records, blockIdx.x * 4 + wave, (int)place, mismatched, first_round,
-                  (int)first_index, (int)checksum, 0, 0, 0);
+  if (store_c) gp_store_c(acc, C, N, m0, n0, wm, wn, lane);
+  gp_store_record(records, wave, lane, place, verdict);
 }
 
 // image: int32, at most 16 KiB, on the current GPU; addrs: 64 int32 byte
@@ -6419,6 +6471,61 @@ torch::Tensor lds_tr_read(long width, torch::Tensor image, torch::Tensor addrs) 
   return regs;
 }
 
+// What the wrappers of the three tiled GEMM probes share once M, N and K are
+// known: the kernels' common argument tail with the records and C it points to.
+struct GpRun {
+  torch::Tensor expected, records, C;
+  long N, K, tiles_n, grid, rounds, inject_block, inject_round;
+  bool store_c;
+};
+
+// Checks expected, the tiling, the length of the run and the injection,
+// leaves A and B contiguous and 16-byte aligned, allocates records and C.
+static GpRun gp_prepare(torch::Tensor& A, torch::Tensor& B, const torch::Tensor& expected, long M,
+                        long N, long K, long rounds, bool store_c, long inject_block,
+                        long inject_round) {
+  TORCH_CHECK(expected.dtype() == torch::kFloat32 &&
+                  expected.sizes() == torch::IntArrayRef({GP_TILE, GP_TILE}),
+              "expected must be float32 [128,128]");
+  TORCH_CHECK(M >= GP_TILE && N >= GP_TILE && M % GP_TILE == 0 && N % GP_TILE == 0,
+              "M and N must be positive multiples of 128; got ", M, ", ", N);
+  const long tiles_n = N / GP_TILE, grid = (M / GP_TILE) * tiles_n;
+  TORCH_CHECK(rounds >= 1, "rounds must be >= 1");
+  // bounded run: 2^33 tile-K-elements are 2.8e14 FLOP, about a second at the
+  // rate the pipeline reaches (BENCHMARKS.md "GEMM probe")
+  TORCH_CHECK(grid <= (1L << 20) && rounds <= (1L << 22) && rounds * K * grid <= (1L << 33),
+              "rounds*K*grid must be <= 2^33; got ", rounds, "*", K, "*", grid);
+  TORCH_CHECK(inject_block >= -1 && inject_block < grid && inject_round >= -1 &&
+                  inject_round < rounds,
+              "inject_block/inject_round out of range");
+  A = A.contiguous();
+  B = B.contiguous();
+  // a direct-to-LDS load fetches 16 aligned bytes (mx6 B kn: 4); every row
+  // pitch is a multiple of 16
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(A.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(B.data_ptr()) % 16 == 0,
+              "A and B must be 16-byte aligned");
+  GpRun run;
+  run.expected = expected.contiguous();
+  run.records = zero_records(grid * 4, 8, A.device());
+  run.C = store_c ? torch::zeros({M, N}, expected.options())
+                  : torch::empty({0}, expected.options());
+  run.N = N, run.K = K, run.tiles_n = tiles_n, run.grid = grid, run.rounds = rounds;
+  run.inject_block = inject_block, run.inject_round = inject_round, run.store_c = store_c;
+  return run;
+}
+
+// `lead`: the kernel's arguments in front of the common tail (A, B, the scales)
+template <typename Kernel, typename... Lead>
+static void gp_launch(Kernel kernel, const GpRun& run, hipStream_t stream, Lead... lead) {
+  hipLaunchKernelGGL(kernel, dim3(run.grid), dim3(256), 0, stream, lead...,
+                     run.expected.data_ptr<float>(),
+                     reinterpret_cast<int4*>(run.records.data_ptr<int>()),
+                     run.store_c ? run.C.data_ptr<float>() : nullptr, (int)run.N, (int)run.K,
+                     (int)run.tiles_n, (int)run.rounds, (int)run.store_c, (int)run.inject_block,
+                     (int)run.inject_round);
+}
+
 // A [M,K]; B [K,N] (b_layout "kn") or [N,K] ("nk"); fmt "bf16": bfloat16
 // tensors, "fp8": uint8 raw e4m3 bytes; expected [128,128] fp32, the tile every
 // workgroup must compute. One untimed warm-up launch, then one timed launch
@@ -6442,17 +6549,12 @@ std::tuple<torch::Tensor, torch::Tensor, double> gemm_pipe(
     TORCH_CHECK(A.dtype() == torch::kUInt8 && B.dtype() == torch::kUInt8,
                 "fp8: A/B must be uint8 (raw e4m3 bytes)");
   }
-  TORCH_CHECK(expected.dtype() == torch::kFloat32 &&
-                  expected.sizes() == torch::IntArrayRef({GP_TILE, GP_TILE}),
-              "expected must be float32 [128,128]");
   TORCH_CHECK(A.dim() == 2 && B.dim() == 2, "A and B must be 2-D");
   const long M = A.size(0), K = A.size(1);
   const long N = bl == GP_KN ? B.size(1) : B.size(0);
   TORCH_CHECK((bl == GP_KN ? B.size(0) : B.size(1)) == K, "B must be ",
               bl == GP_KN ? "[K,N]" : "[N,K]", " with K=", K);
   const long BK = f == GP_BF16 ? 64 : 128;
-  TORCH_CHECK(M >= GP_TILE && N >= GP_TILE && M % GP_TILE == 0 && N % GP_TILE == 0,
-              "M and N must be positive multiples of 128; got ", M, ", ", N);
   TORCH_CHECK(K >= BK && K % BK == 0, "K must be a positive multiple of ", BK, "; got ", K);
   // |operand| <= 2, so every partial sum is an integer <= 4*K: exact in fp32
   // only up to 2^24. For fp8 it is also inside the window the pipe keeps
@@ -6462,34 +6564,17 @@ std::tuple<torch::Tensor, torch::Tensor, double> gemm_pipe(
   TORCH_CHECK(4 * K <= (1L << 24), "K ", K, " breaks fp32 exactness (need 4*K <= 2^24)");
   // the kernel's per-lane offsets into a tile's rows are 32-bit
   TORCH_CHECK(M <= (1L << 22) && N <= (1L << 22), "M and N must be <= 2^22");
-  const long tiles_n = N / GP_TILE, grid = (M / GP_TILE) * tiles_n;
-  TORCH_CHECK(rounds >= 1, "rounds must be >= 1");
-  // bounded run: 2^33 tile-K-elements are 2.8e14 FLOP, about a second at the
-  // rate the pipeline reaches (BENCHMARKS.md "GEMM probe")
-  TORCH_CHECK(grid <= (1L << 20) && rounds <= (1L << 22) && rounds * K * grid <= (1L << 33),
-              "rounds*K*grid must be <= 2^33; got ", rounds, "*", K, "*", grid);
-  TORCH_CHECK(inject_block >= -1 && inject_block < grid && inject_round >= -1 &&
-                  inject_round < rounds,
-              "inject_block/inject_round out of range");
-  A = A.contiguous();
-  B = B.contiguous();
-  expected = expected.contiguous();
-  auto records = zero_records(grid * 4, 8, A.device());
-  auto C = store_c ? torch::zeros({M, N}, expected.options())
-                   : torch::empty({0}, expected.options());
+  const GpRun run =
+      gp_prepare(A, B, expected, M, N, K, rounds, store_c, inject_block, inject_round);
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
   const double ms = warm_then_timed_ms(stream, [&]() {
     dispatch_int<4>(2 * f + bl, [&](auto case_c) {
       constexpr int c = decltype(case_c)::value;
-      hipLaunchKernelGGL((gemm_pipe_kernel<c / 2, c % 2>), dim3(grid), dim3(256), 0, stream,
-                         static_cast<const char*>(A.data_ptr()),
-                         static_cast<const char*>(B.data_ptr()), expected.data_ptr<float>(),
-                         reinterpret_cast<int4*>(records.data_ptr<int>()),
-                         store_c ? C.data_ptr<float>() : nullptr, (int)N, (int)K, (int)tiles_n,
-                         (int)rounds, (int)store_c, (int)inject_block, (int)inject_round);
+      gp_launch(gemm_pipe_kernel<c / 2, c % 2>, run, stream,
+                static_cast<const char*>(A.data_ptr()), static_cast<const char*>(B.data_ptr()));
     });
   });
-  return std::make_tuple(records, C, ms);
+  return std::make_tuple(run.records, run.C, ms);
 }
 
 // ---------------------------------------------------------------------------
@@ -6569,7 +6654,8 @@ std::tuple<torch::Tensor, torch::Tensor, double> gemm_pipe(
 // 2-3 (4); lgkmcnt(4) before the 8 MFMAs of A tiles 0-1, lgkmcnt(0) before the
 // 8 of A tiles 2-3.
 //
-// Verification, records, store_c and inject are gemm_pipe's. Race and bounds:
+// Verification, records, store_c and inject are gemm_pipe's, by the same
+// helpers (see "Verification in registers" there). Race and bounds:
 // no wave waits for another workgroup; every loop bound is a launch argument;
 // the wrapper fixes every shape the offsets are computed from. Build for
 // gfx950 (register counts in BENCHMARKS.md "MX GEMM probe"): no scratch,
@@ -6890,46 +6976,23 @@ mx_gemm_pipe_kernel(const char* __restrict__ A, const char* __restrict__ B,
   // LDS byte offsets of this lane's fragment reads inside a stage, as in
   // gemm_pipe_kernel; fp4 kn: per tile, the chunk and the read are immediates
   unsigned a_at[2], b_at[4];
-  {
-    const int ra = wm * 64 + i16;
-    a_at[0] = ra * 128 + ((g ^ gp_key_b128(ra)) << 4);
-    a_at[1] = a_at[0] ^ 64;
-  }
-  if constexpr (BL == GP_NK) {
-    const int rb = wn * 64 + i16;
-    b_at[0] = rb * 128 + ((g ^ gp_key_b128(rb)) << 4);
-    b_at[1] = b_at[0] ^ 64;
-    b_at[2] = b_at[3] = 0;
-  } else {
+  gp_frag_addrs<BL>(a_at, b_at, wm, wn, i16, g);
+  if constexpr (BL == GP_KN && FMT == MXG_FP4) {
 #pragma unroll
     for (int t = 0; t < 4; t++) {
-      if constexpr (FMT == MXG_FP8) {
-        const int nb = wn * 64 + t * 16;
-        const int k = g * 16 + (i16 >> 1);
-        b_at[t] = k * 128 + (((nb >> 4) ^ gp_key_tr8(k)) << 4) + (i16 & 1) * 8;
-      } else {
-        const int k = g * 32 + i16;
-        b_at[t] = k * 64 + (((wn * 2 + (t >> 1)) ^ mxg_key_tr4(k)) << 4) + (t & 1) * 8;
-      }
+      const int k = g * 32 + i16;
+      b_at[t] = k * 64 + (((wn * 2 + (t >> 1)) ^ mxg_key_tr4(k)) << 4) + (t & 1) * 8;
     }
   }
 
   GP_LDS_AS char* lds = (GP_LDS_AS char*)mxg_lds;
   const unsigned lds_base = (unsigned)reinterpret_cast<__UINTPTR_TYPE__>(lds);
   const bool inject_here = (int)blockIdx.x == inject_block && threadIdx.x == 0;
-  int mismatched = 0, first_round = -1;
-  unsigned first_index = 0xFFFFFFFFu, checksum = 0;
+  GpVerdict verdict;
   unsigned raw_a[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, raw_b[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
   f32x4 acc[4][4];
   for (int round = 0; round < rounds; round++) {
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        // opaque to the optimiser: every round really recomputes its tile
-        asm volatile("" : "+v"(acc[i][j]));
-      }
+    GP_ZERO_ACC(acc)
     const char* a_src = a_tile;
     const char* b_src = b_tile;
     const unsigned char* sa_src = sa_tile;
@@ -7004,67 +7067,48 @@ mx_gemm_pipe_kernel(const char* __restrict__ A, const char* __restrict__ B,
     };
     for (int k = 0; k + 1 < steps; k++) step(std::true_type{}, k);
     step(std::false_type{}, steps - 1);
-    if (inject_here && round == inject_round)
-      acc[0][0][0] = __uint_as_float(__float_as_uint(acc[0][0][0]) ^ 1u);
-    // expected is read again every round, and the lane's place in it is worked
-    // out again: both are opaque to the optimiser, which would otherwise keep
-    // the addresses of the compare and of the store in registers over the K loop
-    int again = 0, lane_v = lane;
-    asm volatile("" : "+s"(again), "+v"(lane_v));
-    const int i16v = lane_v & 15, gv = lane_v >> 4;
-    const float* want_lane = expected + (wm * 64 + gv * 4) * GP_TILE + wn * 64 + i16v;
-    const float* want = want_lane + again;
-    unsigned bad = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const unsigned bits = __float_as_uint(acc[i][j][r]);
-          bad += bits != __float_as_uint(want[(i * 16 + r) * GP_TILE + j * 16]);
-          checksum ^= bits;
-        }
-      asm volatile("" ::: "memory");  // 16 expected values in registers at a time, not 64
-    }
-    bad = wave_add(bad);
-    if (bad) {  // wave-uniform, and rare
-      if (first_round < 0) {
-        first_round = round;
-        asm volatile("" : "+s"(again));  // a second read, not the first one's compare masks
-        want = want_lane + again;
-        unsigned index = 0xFFFFFFFFu;
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-          for (int j = 0; j < 4; j++)
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-              if (__float_as_uint(acc[i][j][r]) !=
-                  __float_as_uint(want[(i * 16 + r) * GP_TILE + j * 16]))
-                index = min(index, (unsigned)((i * 16 + gv * 4 + r) * 64 + j * 16 + i16v));
-        first_index = wave_min(index);
-      }
-      mismatched += (int)bad;
-    }
+    if (inject_here && round == inject_round) gp_inject(acc);
+    gp_compare_round(acc, expected, wm, wn, lane, round, verdict);
   }
-  if (store_c) {
-    int lane_v = lane;
-    asm volatile("" : "+v"(lane_v));  // as above
-    const int i16v = lane_v & 15, gv = lane_v >> 4;
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-          C[(size_t)(m0 + wm * 64 + i * 16 + gv * 4 + r) * N + n0 + wn * 64 + j * 16 + i16v] =
-              acc[i][j][r];
+  if (store_c) gp_store_c(acc, C, N, m0, n0, wm, wn, lane);
+  gp_store_record(records, wave, lane, place, verdict);
+}
+
+// The operand checks mx_gemm_pipe and mx6_gemm_pipe share: five 2-D tensors on
+// one GPU, uint8 but expected; M, N and K from the packed rows of a_bits and
+// b_bits per code (A [M, K a_bits/8]; B nk [N, ...], kn [K, N b_bits/8]); the
+// scales' shapes. Leaves the scales contiguous. B's other dimension and the
+// K step are the caller's to check.
+struct MxgDims { long M, N, K; };
+static MxgDims mxg_check_operands(const torch::Tensor& A, const torch::Tensor& B,
+                                  torch::Tensor& scale_a, torch::Tensor& scale_b,
+                                  const torch::Tensor& expected, int bl, long a_bits,
+                                  long b_bits) {
+  for (const torch::Tensor& t : {A, B, scale_a, scale_b, expected}) {
+    TORCH_CHECK(t.is_cuda() && t.device() == A.device(),
+                "A, B, the scales and expected must be on one GPU");
+    TORCH_CHECK(t.dim() == 2, "A, B, the scales and expected must be 2-D");
   }
-  checksum = wave_xor(checksum);
-  if (lane == 0)
-    store_record8(records, blockIdx.x * 4 + wave, (int)place, mismatched, first_round,
-                  (int)first_index, (int)checksum, 0, 0, 0);
+  TORCH_CHECK(A.dtype() == torch::kUInt8 && B.dtype() == torch::kUInt8 &&
+                  scale_a.dtype() == torch::kUInt8 && scale_b.dtype() == torch::kUInt8,
+              "A, B and the scales must be uint8");
+  const long M = A.size(0), K = A.size(1) * 8 / a_bits;
+  const long N = bl == GP_NK ? B.size(0) : B.size(1) * 8 / b_bits;
+  // the kernel's per-lane offsets into a tile's rows are 32-bit
+  TORCH_CHECK(M <= (1L << 22) && N <= (1L << 22) && K <= (1L << 22),
+              "M, N and K must be <= 2^22");
+  if (bl == GP_NK) {
+    TORCH_CHECK(scale_b.sizes() == torch::IntArrayRef({N, K / 32}), "scale_b must be [", N, ",",
+                K / 32, "]");
+  } else {
+    TORCH_CHECK(scale_b.sizes() == torch::IntArrayRef({K / 32, N}), "scale_b must be [", K / 32,
+                ",", N, "]");
+  }
+  TORCH_CHECK(scale_a.sizes() == torch::IntArrayRef({M, K / 32}), "scale_a must be [", M, ",",
+              K / 32, "]");
+  scale_a = scale_a.contiguous();
+  scale_b = scale_b.contiguous();
+  return {M, N, K};
 }
 
 // fmt "mxfp8": e4m3, one code per byte; "mxfp4": e2m1, two codes per byte along
@@ -7082,73 +7126,28 @@ std::tuple<torch::Tensor, torch::Tensor, double> mx_gemm_pipe(
   TORCH_CHECK(f >= 0, "fmt must be one of mxfp8, mxfp4; got ", fmt);
   const int bl = b_layout == "kn" ? GP_KN : b_layout == "nk" ? GP_NK : -1;
   TORCH_CHECK(bl >= 0, "b_layout must be one of kn, nk; got ", b_layout);
-  for (const torch::Tensor* t : {&A, &B, &scale_a, &scale_b, &expected}) {
-    TORCH_CHECK(t->is_cuda() && t->device() == A.device(),
-                "A, B, the scales and expected must be on one GPU");
-    TORCH_CHECK(t->dim() == 2, "A, B, the scales and expected must be 2-D");
-  }
-  TORCH_CHECK(A.dtype() == torch::kUInt8 && B.dtype() == torch::kUInt8 &&
-                  scale_a.dtype() == torch::kUInt8 && scale_b.dtype() == torch::kUInt8,
-              "A, B and the scales must be uint8");
-  TORCH_CHECK(expected.dtype() == torch::kFloat32 &&
-                  expected.sizes() == torch::IntArrayRef({GP_TILE, GP_TILE}),
-              "expected must be float32 [128,128]");
-  const long pack = f == MXG_FP4 ? 2 : 1;  // codes per byte
+  const long bits = f == MXG_FP4 ? 4 : 8;
   const long BK = f == MXG_FP4 ? 256 : 128;
-  const long M = A.size(0), K = A.size(1) * pack;
-  const long N = bl == GP_NK ? B.size(0) : B.size(1) * pack;
-  TORCH_CHECK(M >= GP_TILE && N >= GP_TILE && M % GP_TILE == 0 && N % GP_TILE == 0,
-              "M and N must be positive multiples of 128; got ", M, ", ", N);
-  TORCH_CHECK(K >= BK && K % BK == 0, "K must be a positive multiple of ", BK, "; got ", K);
-  // the kernel's per-lane offsets into a tile's rows are 32-bit
-  TORCH_CHECK(M <= (1L << 22) && N <= (1L << 22) && K <= (1L << 22),
-              "M, N and K must be <= 2^22");
+  const MxgDims d = mxg_check_operands(A, B, scale_a, scale_b, expected, bl, bits, bits);
+  TORCH_CHECK(d.K >= BK && d.K % BK == 0, "K must be a positive multiple of ", BK, "; got ", d.K);
   if (bl == GP_NK) {
-    TORCH_CHECK(B.size(1) * pack == K, "B must be [N,K] in ", K / pack, " bytes per row");
-    TORCH_CHECK(scale_b.sizes() == torch::IntArrayRef({N, K / 32}), "scale_b must be [", N, ",",
-                K / 32, "]");
+    TORCH_CHECK(B.size(1) * 8 == d.K * bits, "B must be [N,K] in ", d.K * bits / 8,
+                " bytes per row");
   } else {
-    TORCH_CHECK(B.size(0) == K, "B must be [K,N] with K=", K);
-    TORCH_CHECK(scale_b.sizes() == torch::IntArrayRef({K / 32, N}), "scale_b must be [", K / 32,
-                ",", N, "]");
+    TORCH_CHECK(B.size(0) == d.K, "B must be [K,N] with K=", d.K);
   }
-  TORCH_CHECK(scale_a.sizes() == torch::IntArrayRef({M, K / 32}), "scale_a must be [", M, ",",
-              K / 32, "]");
-  const long tiles_n = N / GP_TILE, grid = (M / GP_TILE) * tiles_n;
-  TORCH_CHECK(rounds >= 1, "rounds must be >= 1");
-  // bounded run, as for gemm_pipe
-  TORCH_CHECK(grid <= (1L << 20) && rounds <= (1L << 22) && rounds * K * grid <= (1L << 33),
-              "rounds*K*grid must be <= 2^33; got ", rounds, "*", K, "*", grid);
-  TORCH_CHECK(inject_block >= -1 && inject_block < grid && inject_round >= -1 &&
-                  inject_round < rounds,
-              "inject_block/inject_round out of range");
-  A = A.contiguous();
-  B = B.contiguous();
-  scale_a = scale_a.contiguous();
-  scale_b = scale_b.contiguous();
-  expected = expected.contiguous();
-  // a direct-to-LDS load fetches 16 aligned bytes
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(A.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(B.data_ptr()) % 16 == 0,
-              "A and B must be 16-byte aligned");
-  auto records = zero_records(grid * 4, 8, A.device());
-  auto C = store_c ? torch::zeros({M, N}, expected.options())
-                   : torch::empty({0}, expected.options());
+  const GpRun run =
+      gp_prepare(A, B, expected, d.M, d.N, d.K, rounds, store_c, inject_block, inject_round);
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
   const double ms = warm_then_timed_ms(stream, [&]() {
     dispatch_int<4>(2 * f + bl, [&](auto case_c) {
       constexpr int c = decltype(case_c)::value;
-      hipLaunchKernelGGL((mx_gemm_pipe_kernel<c / 2, c % 2>), dim3(grid), dim3(256), 0, stream,
-                         static_cast<const char*>(A.data_ptr()),
-                         static_cast<const char*>(B.data_ptr()),
-                         scale_a.data_ptr<unsigned char>(), scale_b.data_ptr<unsigned char>(),
-                         expected.data_ptr<float>(),
-                         reinterpret_cast<int4*>(records.data_ptr<int>()),
-                         store_c ? C.data_ptr<float>() : nullptr, (int)N, (int)K, (int)tiles_n,
-                         (int)rounds, (int)store_c, (int)inject_block, (int)inject_round);
+      gp_launch(mx_gemm_pipe_kernel<c / 2, c % 2>, run, stream,
+                static_cast<const char*>(A.data_ptr()), static_cast<const char*>(B.data_ptr()),
+                scale_a.data_ptr<unsigned char>(), scale_b.data_ptr<unsigned char>());
     });
   });
-  return std::make_tuple(records, C, ms);
+  return std::make_tuple(run.records, run.C, ms);
 }
 
 // ---------------------------------------------------------------------------
@@ -7164,7 +7163,7 @@ std::tuple<torch::Tensor, torch::Tensor, double> mx_gemm_pipe(
 // scale bytes (one K chunk of four blocks per step: 4 A and 4 B
 // global_load_ubyte per lane, mx6_load_scales) a step ahead, gathered into one VGPR per
 // side and selected with op_sel; the last step peeled; verification, records,
-// store_c and inject.
+// store_c and inject (gemm_pipe's helpers).
 //
 // New: a K step is 128 *elements* in every case, one scaled MFMA deep, so a
 // side's tile of a step is 128 rows of 128 (8-bit), 96 (6-bit) or 64 (4-bit)
@@ -7526,19 +7525,11 @@ mx6_gemm_pipe_kernel(const char* __restrict__ A, const char* __restrict__ B,
   GP_LDS_AS char* lds = (GP_LDS_AS char*)mx6_lds;
   const unsigned lds_base = (unsigned)reinterpret_cast<__UINTPTR_TYPE__>(lds);
   const bool inject_here = (int)blockIdx.x == inject_block && threadIdx.x == 0;
-  int mismatched = 0, first_round = -1;
-  unsigned first_index = 0xFFFFFFFFu, checksum = 0;
+  GpVerdict verdict;
   unsigned raw_a[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, raw_b[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
   f32x4 acc[4][4];
   for (int round = 0; round < rounds; round++) {
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        // opaque to the optimiser: every round really recomputes its tile
-        asm volatile("" : "+v"(acc[i][j]));
-      }
+    GP_ZERO_ACC(acc)
     const char* a_src = a_tile;
     const char* b_src = b_tile;
     const unsigned char* sa_src = sa_tile;
@@ -7614,69 +7605,15 @@ mx6_gemm_pipe_kernel(const char* __restrict__ A, const char* __restrict__ B,
     };
     for (int k = 0; k + 1 < steps; k++) step(std::true_type{}, k);
     step(std::false_type{}, steps - 1);
-    if (inject_here && round == inject_round)
-      acc[0][0][0] = __uint_as_float(__float_as_uint(acc[0][0][0]) ^ 1u);
-    // the compare, as in mx_gemm_pipe_kernel: expected is read again every
-    // round and the lane's place in it worked out again
-    int again = 0, lane_v = lane;
-    asm volatile("" : "+s"(again), "+v"(lane_v));
-    const int i16v = lane_v & 15, gv = lane_v >> 4;
-    const float* want_lane = expected + (wm * 64 + gv * 4) * GP_TILE + wn * 64 + i16v;
-    const float* want = want_lane + again;
-    unsigned bad = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const unsigned bits = __float_as_uint(acc[i][j][r]);
-          bad += bits != __float_as_uint(want[(i * 16 + r) * GP_TILE + j * 16]);
-          checksum ^= bits;
-        }
-      asm volatile("" ::: "memory");  // 16 expected values in registers at a time, not 64
-    }
-    bad = wave_add(bad);
-    if (bad) {  // wave-uniform, and rare
-      if (first_round < 0) {
-        first_round = round;
-        asm volatile("" : "+s"(again));  // a second read, not the first one's compare masks
-        want = want_lane + again;
-        unsigned index = 0xFFFFFFFFu;
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-          for (int j = 0; j < 4; j++)
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-              if (__float_as_uint(acc[i][j][r]) !=
-                  __float_as_uint(want[(i * 16 + r) * GP_TILE + j * 16]))
-                index = min(index, (unsigned)((i * 16 + gv * 4 + r) * 64 + j * 16 + i16v));
-        first_index = wave_min(index);
-      }
-      mismatched += (int)bad;
-    }
+    if (inject_here && round == inject_round) gp_inject(acc);
+    gp_compare_round(acc, expected, wm, wn, lane, round, verdict);
   }
-  if (store_c) {
-    int lane_v = lane;
-    asm volatile("" : "+v"(lane_v));  // as above
-    const int i16v = lane_v & 15, gv = lane_v >> 4;
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-          C[(size_t)(m0 + wm * 64 + i * 16 + gv * 4 + r) * N + n0 + wn * 64 + j * 16 + i16v] =
-              acc[i][j][r];
-  }
-  checksum = wave_xor(checksum);
-  if (lane == 0)
-    store_record8(records, blockIdx.x * 4 + wave, (int)place, mismatched, first_round,
-                  (int)first_index, (int)checksum, 0, 0, 0);
+  if (store_c) gp_store_c(acc, C, N, m0, n0, wm, wn, lane);
+  gp_store_record(records, wave, lane, place, verdict);
 }
 #undef MX6_MMA_ROW
 #undef MX6_MMA
+#undef GP_ZERO_ACC
 
 // the instantiated cases: operand formats by name, bits per code, the
 // instruction's format code
@@ -7714,70 +7651,26 @@ std::tuple<torch::Tensor, torch::Tensor, double> mx6_gemm_pipe(
     if (MX6_CASE[c][0] == fa && MX6_CASE[c][1] == fb && MX6_CASE[c][2] == bl) which = c;
   TORCH_CHECK(which >= 0, "unsupported case ", a_fmt, " x ", b_fmt, " ", b_layout,
               ": mxfp6 and mxbf6 with themselves (nk, kn), mxfp8 x mxfp6 and mxfp8 x mxfp4 (nk)");
-  for (const torch::Tensor* t : {&A, &B, &scale_a, &scale_b, &expected}) {
-    TORCH_CHECK(t->is_cuda() && t->device() == A.device(),
-                "A, B, the scales and expected must be on one GPU");
-    TORCH_CHECK(t->dim() == 2, "A, B, the scales and expected must be 2-D");
-  }
-  TORCH_CHECK(A.dtype() == torch::kUInt8 && B.dtype() == torch::kUInt8 &&
-                  scale_a.dtype() == torch::kUInt8 && scale_b.dtype() == torch::kUInt8,
-              "A, B and the scales must be uint8");
-  TORCH_CHECK(expected.dtype() == torch::kFloat32 &&
-                  expected.sizes() == torch::IntArrayRef({GP_TILE, GP_TILE}),
-              "expected must be float32 [128,128]");
   const long abits = MX6_FORMATS[fa].bits, bbits = MX6_FORMATS[fb].bits;
-  const long M = A.size(0), K = A.size(1) * 8 / abits;
-  TORCH_CHECK(K * abits == A.size(1) * 8, "A's ", A.size(1), " bytes per row hold no whole number of ",
-              abits, "-bit codes");
-  const long N = bl == GP_NK ? B.size(0) : B.size(1) * 8 / bbits;
-  TORCH_CHECK(M >= GP_TILE && N >= GP_TILE && M % GP_TILE == 0 && N % GP_TILE == 0,
-              "M and N must be positive multiples of 128; got ", M, ", ", N);
-  TORCH_CHECK(K >= MX6_BK && K % MX6_BK == 0, "K must be a positive multiple of 128; got ", K);
-  // the kernel's per-lane offsets into a tile's rows are 32-bit
-  TORCH_CHECK(M <= (1L << 22) && N <= (1L << 22) && K <= (1L << 22),
-              "M, N and K must be <= 2^22");
+  const MxgDims d = mxg_check_operands(A, B, scale_a, scale_b, expected, bl, abits, bbits);
+  TORCH_CHECK(d.K * abits == A.size(1) * 8, "A's ", A.size(1),
+              " bytes per row hold no whole number of ", abits, "-bit codes");
+  TORCH_CHECK(d.K >= MX6_BK && d.K % MX6_BK == 0, "K must be a positive multiple of 128; got ",
+              d.K);
   if (bl == GP_NK) {
-    TORCH_CHECK(B.size(1) * 8 == K * bbits, "B must be [N,K] in ", K * bbits / 8, " bytes per row");
-    TORCH_CHECK(scale_b.sizes() == torch::IntArrayRef({N, K / 32}), "scale_b must be [", N, ",",
-                K / 32, "]");
+    TORCH_CHECK(B.size(1) * 8 == d.K * bbits, "B must be [N,K] in ", d.K * bbits / 8,
+                " bytes per row");
   } else {
-    TORCH_CHECK(B.size(0) == K && B.size(1) * 8 == N * bbits, "B must be [K,N] with K=", K,
-                " in ", N * bbits / 8, " bytes per row");
-    TORCH_CHECK(scale_b.sizes() == torch::IntArrayRef({K / 32, N}), "scale_b must be [", K / 32,
-                ",", N, "]");
+    TORCH_CHECK(B.size(0) == d.K && B.size(1) * 8 == d.N * bbits, "B must be [K,N] with K=", d.K,
+                " in ", d.N * bbits / 8, " bytes per row");
   }
-  TORCH_CHECK(scale_a.sizes() == torch::IntArrayRef({M, K / 32}), "scale_a must be [", M, ",",
-              K / 32, "]");
-  const long tiles_n = N / GP_TILE, grid = (M / GP_TILE) * tiles_n;
-  TORCH_CHECK(rounds >= 1, "rounds must be >= 1");
-  // bounded run, as for gemm_pipe
-  TORCH_CHECK(grid <= (1L << 20) && rounds <= (1L << 22) && rounds * K * grid <= (1L << 33),
-              "rounds*K*grid must be <= 2^33; got ", rounds, "*", K, "*", grid);
-  TORCH_CHECK(inject_block >= -1 && inject_block < grid && inject_round >= -1 &&
-                  inject_round < rounds,
-              "inject_block/inject_round out of range");
-  A = A.contiguous();
-  B = B.contiguous();
-  scale_a = scale_a.contiguous();
-  scale_b = scale_b.contiguous();
-  expected = expected.contiguous();
-  // a direct-to-LDS load fetches 16 aligned bytes (B kn: 4); every row pitch
-  // is a multiple of 48
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(A.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(B.data_ptr()) % 16 == 0,
-              "A and B must be 16-byte aligned");
-  auto records = zero_records(grid * 4, 8, A.device());
-  auto C = store_c ? torch::zeros({M, N}, expected.options())
-                   : torch::empty({0}, expected.options());
+  const GpRun run =
+      gp_prepare(A, B, expected, d.M, d.N, d.K, rounds, store_c, inject_block, inject_round);
   hipStream_t stream = at::cuda::getCurrentCUDAStream();
   auto launch = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream,
-                       static_cast<const char*>(A.data_ptr()),
-                       static_cast<const char*>(B.data_ptr()), scale_a.data_ptr<unsigned char>(),
-                       scale_b.data_ptr<unsigned char>(), expected.data_ptr<float>(),
-                       reinterpret_cast<int4*>(records.data_ptr<int>()),
-                       store_c ? C.data_ptr<float>() : nullptr, (int)N, (int)K, (int)tiles_n,
-                       (int)rounds, (int)store_c, (int)inject_block, (int)inject_round);
+    gp_launch(kernel, run, stream, static_cast<const char*>(A.data_ptr()),
+              static_cast<const char*>(B.data_ptr()), scale_a.data_ptr<unsigned char>(),
+              scale_b.data_ptr<unsigned char>());
   };
   const double ms = warm_then_timed_ms(stream, [&]() {
     switch (which) {  // the order of MX6_CASE
@@ -7789,7 +7682,7 @@ std::tuple<torch::Tensor, torch::Tensor, double> mx6_gemm_pipe(
       default: launch(mx6_gemm_pipe_kernel<8, 4, GP_NK, 0, 4>); break;
     }
   });
-  return std::make_tuple(records, C, ms);
+  return std::make_tuple(run.records, run.C, ms);
 }
 
 py::dict device_info(int dev) {

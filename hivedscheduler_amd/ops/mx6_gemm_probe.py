@@ -9,11 +9,10 @@ report function.
 """
 from __future__ import annotations
 
-from .gemm_probe import GEMM_TILE, summarize_gemm_probe
-from .mfma_tiles import _lossless
-from .mx_gemm_probe import MX_GEMM_MAX_K, mx_gemm_pack, mx_gemm_unpack
-from .mx_scale import MX_SCALE_SPREAD, mx_encode, mx_scaled_product
-from .records import place_dicts, place_keys
+from .gemm_probe import GEMM_TILE, _summarize_tiled_gemm, _tiled_gemm_report
+from .mx_gemm_probe import (MX_GEMM_MAX_K, _mx_encode_ints,  # noqa: F401
+                            _mx_tiled_operands, mx_gemm_pack, mx_gemm_unpack)
+from .mx_scale import mx_scaled_product
 
 # format name: (bits per code, the instruction's format code (mx_scale.py))
 _MX6_FORMATS = {"mxfp8": (8, 0), "mxfp6": (6, 2), "mxbf6": (6, 3), "mxfp4": (4, 4)}
@@ -23,12 +22,6 @@ MX6_GEMM_CASES = (("mxfp6", "mxfp6", "nk"), ("mxfp6", "mxfp6", "kn"),
                   ("mxfp8", "mxfp6", "nk"), ("mxfp8", "mxfp4", "nk"))
 MX6_GEMM_BK = 128                       # elements of K per step, in every case
 MX6_GEMM_PERIOD = 4 * MX6_GEMM_BK       # as mx_gemm_period: a stale stage holds step k-2
-# default shape and rounds (BENCHMARKS.md "MX6 GEMM probe"): 1024 workgroups,
-# four per CU of an MI355X; 99 rounds put every case's timed launch at 27 to
-# 31 ms, inside what the GEMM probe's cases take; an odd number keeps the xor
-# checksum non-zero
-_DEFAULT_MNK = (4096, 4096, 8192)
-_DEFAULT_ROUNDS = 99
 
 
 def mx6_gemm_case_name(a_fmt: str, b_fmt: str, b_layout: str) -> str:
@@ -78,11 +71,7 @@ def _unpack(packed, fmt: str, axis: int = -1):
 
 
 def _encode(ints, fmt: str):
-    """Integers in {-2..2} as codes of the format, one per byte."""
-    import torch
-
-    table = mx_encode(_MX6_FORMATS[fmt][1], torch.arange(-2, 3).double())
-    return table[ints.long() + 2]
+    return _mx_encode_ints(ints, _MX6_FORMATS[fmt][1])
 
 
 def mx6_gemm_reference(a_fmt: str, b_fmt: str, b_layout: str, A, B, scale_a, scale_b):
@@ -104,31 +93,6 @@ def mx6_gemm_layout(a_fmt: str, b_fmt: str, b_layout: str, a, b, sa, sb):
             sb.contiguous())
 
 
-def _mx6_gemm_units(a_fmt: str, b_fmt: str, seed: int = 0):
-    """_mx_gemm_units with a format per side: one period a [128,P], b [P,128]
-    in {-2..2}, scales sa [128,P/32], sb [P/32,128] in 127 +- MX_SCALE_SPREAD
-    and the unit tile; rows of a redrawn until no element of it is zero."""
-    import torch
-
-    P = MX6_GEMM_PERIOD
-    ca, cb = _MX6_FORMATS[a_fmt][1], _MX6_FORMATS[b_fmt][1]
-    g = torch.Generator().manual_seed(seed)
-    k = torch.arange(P, dtype=torch.int64).unsqueeze(1)
-    n = torch.arange(GEMM_TILE, dtype=torch.int64).unsqueeze(0)
-    b = (3 * k + n + seed) % 5 - 2
-    lo, hi = 127 - MX_SCALE_SPREAD, 127 + MX_SCALE_SPREAD + 1
-    sa = torch.randint(lo, hi, (GEMM_TILE, P // 32), generator=g, dtype=torch.uint8)
-    sb = torch.randint(lo, hi, (P // 32, GEMM_TILE), generator=g, dtype=torch.uint8)
-    a = torch.randint(-2, 3, (GEMM_TILE, P), generator=g, dtype=torch.int64)
-    b_codes = _encode(b, b_fmt)
-    while True:
-        unit = mx_scaled_product(ca, cb, _encode(a, a_fmt), b_codes, sa, sb)
-        redraw = (unit == 0).any(dim=1)
-        if not redraw.any():
-            return a, b, sa, sb, unit
-        a[redraw] = torch.randint(-2, 3, (int(redraw.sum()), P), generator=g, dtype=torch.int64)
-
-
 def mx6_gemm_operands(a_fmt: str, b_fmt: str, b_layout: str, M: int, N: int, K: int,
                       seed: int = 0):
     """(A, B, scale_a, scale_b, expected [128,128] fp32) on the CPU, as the op
@@ -137,23 +101,10 @@ def mx6_gemm_operands(a_fmt: str, b_fmt: str, b_layout: str, M: int, N: int, K: 
     gives, which does not depend on the format: integers of magnitude <= 2
     (exact codes in e4m3, e2m3, e3m2 and e2m1) under scales 2^-2..2^2, every
     partial sum an integer of at most K * 2^10 units of 2^-4: K <= 16384."""
-    import torch
-
     _check_case(a_fmt, b_fmt, b_layout)
-    P = MX6_GEMM_PERIOD
-    if M % GEMM_TILE or N % GEMM_TILE or K % P or min(M, N, K) <= 0:
-        raise ValueError(f"M, N must be multiples of 128 and K of {P}; got {M}, {N}, {K}")
-    if K > MX_GEMM_MAX_K:
-        raise ValueError(f"K {K} breaks fp32 exactness (need K * 2^10 <= 2^24)")
-    a, b, sa, sb, unit = _mx6_gemm_units(a_fmt, b_fmt, seed)
-    expected = (K // P) * unit
-    assert float(expected.abs().max()) * 16 <= K << 10 <= 1 << 24
-    assert _lossless(expected.float(), expected) and not torch.equal(unit, unit.t())
-    A, B, scale_a, scale_b = mx6_gemm_layout(a_fmt, b_fmt, b_layout, a, b, sa, sb)
-    tiles_b = (K // P, N // GEMM_TILE) if b_layout == "kn" else (N // GEMM_TILE, K // P)
-    return (A.repeat(M // GEMM_TILE, K // P), B.repeat(*tiles_b),
-            scale_a.repeat(M // GEMM_TILE, K // P), scale_b.repeat(*tiles_b),
-            expected.float().contiguous())
+    return _mx_tiled_operands(_MX6_FORMATS[a_fmt][1], _MX6_FORMATS[b_fmt][1], MX6_GEMM_PERIOD,
+                              lambda *units: mx6_gemm_layout(a_fmt, b_fmt, b_layout, *units),
+                              b_layout, M, N, K, seed)
 
 
 def mx6_gemm_step_bytes(a_fmt: str, b_fmt: str, b_layout: str) -> int:
@@ -170,11 +121,8 @@ def summarize_mx6_gemm_probe(records, ms: float, a_fmt: str, b_fmt: str, b_layou
     and fields. `operand_gbps` counts what the workgroups load per K step
     (mx6_gemm_step_bytes) over the time. The rates are reported, never judged.
     Pure numpy; needs no GPU."""
-    s = summarize_gemm_probe(records, ms, "fp8", b_layout, M, N, K, rounds, expected_cus)
-    grid = (M // GEMM_TILE) * (N // GEMM_TILE)
-    loaded = float(grid) * (K // MX6_GEMM_BK) * mx6_gemm_step_bytes(a_fmt, b_fmt, b_layout) * rounds
-    s["operand_gbps"] = loaded / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-    return s
+    return _summarize_tiled_gemm(records, ms, M, N, K, rounds, expected_cus, K // MX6_GEMM_BK,
+                                 mx6_gemm_step_bytes(a_fmt, b_fmt, b_layout))
 
 
 def mx6_gemm_probe_report(device: int = 0, cases=MX6_GEMM_CASES, M: int = None, N: int = None,
@@ -187,25 +135,5 @@ def mx6_gemm_probe_report(device: int = 0, cases=MX6_GEMM_CASES, M: int = None, 
     one accumulator bit in wave 0 of that workgroup in that round (register
     arithmetic only) to exercise detection on healthy hardware.
     """
-    from . import _ops_on
-
-    ops = _ops_on(device)
-    M = _DEFAULT_MNK[0] if M is None else int(M)
-    N = _DEFAULT_MNK[1] if N is None else int(N)
-    K = _DEFAULT_MNK[2] if K is None else int(K)
-    rounds = _DEFAULT_ROUNDS if rounds is None else int(rounds)
-    inject_block, inject_round = (-1, -1) if inject is None else inject
-    expected_cus = ops.device_info(device)["multiProcessorCount"]
-    out: dict = {"M": M, "N": N, "K": K, "rounds": rounds, "cases": {}}
-    bad = set()
-    for case in cases:
-        operands = mx6_gemm_operands(*case, M, N, K)
-        records, _, ms = ops.mx6_gemm_pipe(*(t.cuda(device) for t in operands), *case, rounds,
-                                           False, inject_block, inject_round)
-        s = summarize_mx6_gemm_probe(records.cpu().numpy(), ms, *case, M, N, K, rounds,
-                                     expected_cus)
-        out["cases"][mx6_gemm_case_name(*case)] = s
-        bad |= place_keys(s["bad_cus"], 4)
-    out["ok"] = bool(all(s["ok"] for s in out["cases"].values()))
-    out["bad_cus"] = place_dicts(bad)
-    return out
+    return _tiled_gemm_report(device, cases, M, N, K, rounds, inject, "mx6_gemm_pipe",
+                              mx6_gemm_operands, summarize_mx6_gemm_probe, mx6_gemm_case_name)

@@ -8,10 +8,9 @@ Pure numpy / torch on the CPU apart from the report function.
 """
 from __future__ import annotations
 
-from .gemm_probe import GEMM_TILE, summarize_gemm_probe
+from .gemm_probe import GEMM_TILE, _summarize_tiled_gemm, _tiled_gemm_report
 from .mfma_tiles import _lossless
 from .mx_scale import MX_SCALE_SPREAD, mx_encode, mx_scaled_product
-from .records import place_dicts, place_keys
 
 MX_GEMM_FORMATS = ("mxfp8", "mxfp4")
 MX_GEMM_LAYOUTS = ("kn", "nk")
@@ -22,11 +21,6 @@ _STEP_BYTES = 128                       # bytes of K per row and K step
 # in units of 2^-4 (two scales of 2^-2) a term is an integer of at most
 # 2*2 * 2^8, so a partial sum is at most K * 2^10: fp32 holds it up to 2^24
 MX_GEMM_MAX_K = (1 << 24) >> (2 + 4 * MX_SCALE_SPREAD)
-# default shape and rounds (BENCHMARKS.md "MX GEMM probe"): 1024 workgroups,
-# four per CU of an MI355X; an odd number of rounds keeps the xor checksum
-# non-zero
-_DEFAULT_MNK = (4096, 4096, 8192)
-_DEFAULT_ROUNDS = 99
 
 
 def mx_gemm_bk(fmt: str) -> int:
@@ -73,12 +67,18 @@ def mx_gemm_reference(fmt: str, b_layout: str, A, B, scale_a, scale_b):
     return mx_scaled_product(_MX_CODE[fmt], _MX_CODE[fmt], a, b, scale_a, scale_b)
 
 
-def mx_gemm_encode(ints, fmt: str):
-    """Integers in {-2..2} as codes of the format, one per byte."""
+def _mx_encode_ints(ints, code: int):
+    """Integers in {-2..2} as codes of the format with the instruction's format
+    code `code`, one per byte."""
     import torch
 
-    table = mx_encode(_MX_CODE[fmt], torch.arange(-2, 3).double())
+    table = mx_encode(code, torch.arange(-2, 3).double())
     return table[ints.long() + 2]
+
+
+def mx_gemm_encode(ints, fmt: str):
+    """Integers in {-2..2} as codes of the format, one per byte."""
+    return _mx_encode_ints(ints, _MX_CODE[fmt])
 
 
 def mx_gemm_layout(fmt: str, b_layout: str, a, b, sa, sb):
@@ -89,16 +89,16 @@ def mx_gemm_layout(fmt: str, b_layout: str, a, b, sa, sb):
     return A, mx_gemm_pack(mx_gemm_encode(b, fmt), fmt), sa.contiguous(), sb.contiguous()
 
 
-def _mx_gemm_units(fmt: str, seed: int = 0):
-    """One period of the operands: int64 a [128,P], b [P,128] in {-2..2} and
-    uint8 scales sa [128,P/32], sb [P/32,128] in 127 +- MX_SCALE_SPREAD, drawn
-    per (row, block) and (block, column). b is the fixed asymmetric pattern of
-    _gemm_probe_units; rows of a are redrawn until no element of the scaled
-    product is zero, so a dead accumulator differs everywhere."""
+def _mx_units(code_a: int, code_b: int, P: int, seed: int = 0):
+    """One period of the operands, the sides in the formats with the
+    instruction's codes code_a and code_b: int64 a [128,P], b [P,128] in
+    {-2..2} and uint8 scales sa [128,P/32], sb [P/32,128] in 127 +-
+    MX_SCALE_SPREAD, drawn per (row, block) and (block, column), and the unit
+    tile. b is the fixed asymmetric pattern of _gemm_probe_units; rows of a are
+    redrawn until no element of the scaled product is zero, so a dead
+    accumulator differs everywhere."""
     import torch
 
-    P = mx_gemm_period(fmt)
-    c = _MX_CODE[fmt]
     g = torch.Generator().manual_seed(seed)
     k = torch.arange(P, dtype=torch.int64).unsqueeze(1)
     n = torch.arange(GEMM_TILE, dtype=torch.int64).unsqueeze(0)
@@ -107,13 +107,35 @@ def _mx_gemm_units(fmt: str, seed: int = 0):
     sa = torch.randint(lo, hi, (GEMM_TILE, P // 32), generator=g, dtype=torch.uint8)
     sb = torch.randint(lo, hi, (P // 32, GEMM_TILE), generator=g, dtype=torch.uint8)
     a = torch.randint(-2, 3, (GEMM_TILE, P), generator=g, dtype=torch.int64)
-    b_codes = mx_gemm_encode(b, fmt)
+    b_codes = _mx_encode_ints(b, code_b)
     while True:
-        unit = mx_scaled_product(c, c, mx_gemm_encode(a, fmt), b_codes, sa, sb)
+        unit = mx_scaled_product(code_a, code_b, _mx_encode_ints(a, code_a), b_codes, sa, sb)
         redraw = (unit == 0).any(dim=1)
         if not redraw.any():
             return a, b, sa, sb, unit
         a[redraw] = torch.randint(-2, 3, (int(redraw.sum()), P), generator=g, dtype=torch.int64)
+
+
+def _mx_tiled_operands(code_a: int, code_b: int, P: int, layout, b_layout: str, M: int, N: int,
+                       K: int, seed: int):
+    """The operands of an MX tiled GEMM probe from one period's units:
+    `layout(a, b, sa, sb)` brings the units into the op's form, and everything
+    repeats with period 128 in M and N and P in K."""
+    import torch
+
+    if M % GEMM_TILE or N % GEMM_TILE or K % P or min(M, N, K) <= 0:
+        raise ValueError(f"M, N must be multiples of 128 and K of {P}; got {M}, {N}, {K}")
+    if K > MX_GEMM_MAX_K:
+        raise ValueError(f"K {K} breaks fp32 exactness (need K * 2^10 <= 2^24)")
+    a, b, sa, sb, unit = _mx_units(code_a, code_b, P, seed)
+    expected = (K // P) * unit
+    assert float(expected.abs().max()) * 16 <= K << 10 <= 1 << 24
+    assert _lossless(expected.float(), expected) and not torch.equal(unit, unit.t())
+    A, B, scale_a, scale_b = layout(a, b, sa, sb)
+    tiles_b = (K // P, N // GEMM_TILE) if b_layout == "kn" else (N // GEMM_TILE, K // P)
+    return (A.repeat(M // GEMM_TILE, K // P), B.repeat(*tiles_b),
+            scale_a.repeat(M // GEMM_TILE, K // P), scale_b.repeat(*tiles_b),
+            expected.float().contiguous())
 
 
 def mx_gemm_operands(fmt: str, b_layout: str, M: int, N: int, K: int, seed: int = 0):
@@ -128,24 +150,11 @@ def mx_gemm_operands(fmt: str, b_layout: str, M: int, N: int, K: int, seed: int 
     K * 2^10, which fp32 holds up to 2^24: K <= 16384. Inside a 32-block all
     products share one power of two, within the window the fp8 pipes keep
     inside a lane group (the regime mx_scale_burn_operands runs)."""
-    import torch
-
     if fmt not in MX_GEMM_FORMATS or b_layout not in MX_GEMM_LAYOUTS:
         raise ValueError(f"unknown case {fmt}/{b_layout}")
-    P = mx_gemm_period(fmt)
-    if M % GEMM_TILE or N % GEMM_TILE or K % P or min(M, N, K) <= 0:
-        raise ValueError(f"M, N must be multiples of 128 and K of {P}; got {M}, {N}, {K}")
-    if K > MX_GEMM_MAX_K:
-        raise ValueError(f"K {K} breaks fp32 exactness (need K * 2^10 <= 2^24)")
-    a, b, sa, sb, unit = _mx_gemm_units(fmt, seed)
-    expected = (K // P) * unit
-    assert float(expected.abs().max()) * 16 <= K << 10 <= 1 << 24
-    assert _lossless(expected.float(), expected) and not torch.equal(unit, unit.t())
-    A, B, scale_a, scale_b = mx_gemm_layout(fmt, b_layout, a, b, sa, sb)
-    tiles_b = (K // P, N // GEMM_TILE) if b_layout == "kn" else (N // GEMM_TILE, K // P)
-    return (A.repeat(M // GEMM_TILE, K // P), B.repeat(*tiles_b),
-            scale_a.repeat(M // GEMM_TILE, K // P), scale_b.repeat(*tiles_b),
-            expected.float().contiguous())
+    return _mx_tiled_operands(_MX_CODE[fmt], _MX_CODE[fmt], mx_gemm_period(fmt),
+                              lambda *units: mx_gemm_layout(fmt, b_layout, *units), b_layout,
+                              M, N, K, seed)
 
 
 def summarize_mx_gemm_probe(records, ms: float, fmt: str, b_layout: str, M: int, N: int, K: int,
@@ -154,12 +163,9 @@ def summarize_mx_gemm_probe(records, ms: float, fmt: str, b_layout: str, M: int,
     and fields. `operand_gbps` counts what the workgroups load per K step, 32
     KiB of operands and 256 rows' scale bytes, over the time. The rates are
     reported, never judged. Pure numpy; needs no GPU."""
-    s = summarize_gemm_probe(records, ms, "fp8", b_layout, M, N, K, rounds, expected_cus)
     bk = mx_gemm_bk(fmt)
-    grid = (M // GEMM_TILE) * (N // GEMM_TILE)
-    loaded = float(grid) * (K // bk) * 2 * GEMM_TILE * (_STEP_BYTES + bk // 32) * rounds
-    s["operand_gbps"] = loaded / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-    return s
+    return _summarize_tiled_gemm(records, ms, M, N, K, rounds, expected_cus, K // bk,
+                                 2 * GEMM_TILE * (_STEP_BYTES + bk // 32))
 
 
 def mx_gemm_probe_report(device: int = 0, cases=MX_GEMM_CASES, M: int = None, N: int = None,
@@ -172,25 +178,5 @@ def mx_gemm_probe_report(device: int = 0, cases=MX_GEMM_CASES, M: int = None, N:
     of that workgroup in that round (register arithmetic only) to exercise
     detection on healthy hardware.
     """
-    from . import _ops_on
-
-    ops = _ops_on(device)
-    M = _DEFAULT_MNK[0] if M is None else int(M)
-    N = _DEFAULT_MNK[1] if N is None else int(N)
-    K = _DEFAULT_MNK[2] if K is None else int(K)
-    rounds = _DEFAULT_ROUNDS if rounds is None else int(rounds)
-    inject_block, inject_round = (-1, -1) if inject is None else inject
-    expected_cus = ops.device_info(device)["multiProcessorCount"]
-    out: dict = {"M": M, "N": N, "K": K, "rounds": rounds, "cases": {}}
-    bad = set()
-    for fmt, b_layout in cases:
-        operands = mx_gemm_operands(fmt, b_layout, M, N, K)
-        records, _, ms = ops.mx_gemm_pipe(*(t.cuda(device) for t in operands), fmt, b_layout,
-                                          rounds, False, inject_block, inject_round)
-        s = summarize_mx_gemm_probe(records.cpu().numpy(), ms, fmt, b_layout, M, N, K, rounds,
-                                    expected_cus)
-        out["cases"][f"{fmt}_{b_layout}"] = s
-        bad |= place_keys(s["bad_cus"], 4)
-    out["ok"] = bool(all(s["ok"] for s in out["cases"].values()))
-    out["bad_cus"] = place_dicts(bad)
-    return out
+    return _tiled_gemm_report(device, cases, M, N, K, rounds, inject, "mx_gemm_pipe",
+                              mx_gemm_operands, summarize_mx_gemm_probe, "{}_{}".format)
